@@ -11,12 +11,22 @@ and "decode box" (run.py:219-263).  Inputs (xyz, intensity) are resident in
 HBM before the timed region.  Frames are independent: rank r of N processes
 takes frames r, r+N, ... (weak scaling, no collective on the data path).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra
-objects: `roofline` (standalone scatter-max kernel, HBM-bound, timed with
-events on the launch stream) and `cpu_baseline` (the oracle = CPU port of the
-reference path, timed on the host cores on a bounded sample).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly
+--steps steps in one region and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`).  `--full` adds every
+other measurement to the same line: the repeat spread and host-enqueue time
+of the headline, the secondary workloads (preset 'car', ped_cyl, training,
+files-to-files loop, the 16-bit edge arithmetics), per-phase and latency
+figures, `roofline` (standalone kernels timed with events, live rocprofv3
+child passes) and `cpu_baseline` (the oracle = CPU port of the reference
+path, timed on the host cores on a bounded sample).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller
+(each frame's logits and box encodings) as DIR/<name>.npy; inputs and weights
+are seeded, so two builds can be compared output for output.
 """
 import argparse
+import collections
 import json
 import os
 import sys
@@ -181,7 +191,7 @@ def live_kernel_trace(config, preset, edge_arith="f32", steps=8, warmup=2,
            "--preset", preset, "--edge-arith", edge_arith, "--steps",
            str(steps), "--warmup", str(warmup), "--frames", "1",
            "--frames-per-step", "1", "--repeats", "1", "--no-pipeline",
-           "--no-cpu-baseline", "--no-secondary", "--no-live-pmc",
+           "--full", "--no-cpu-baseline", "--no-secondary", "--no-live-pmc",
            "--no-roofline", "--no-capture"]
     try:
         p = subprocess.run([rocprof, "--kernel-trace", "-d", tmp, "-o", "run",
@@ -1193,10 +1203,21 @@ def parse_args(argv=None):
                          "timed region of a 20-step run ~0.5 s per rank, so "
                          "a few ms of rank skew at the closing barrier is "
                          "<1 %% of it")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="barrier-bracketed timed regions of exactly --steps "
                          "steps; the FIRST is the headline `value`, the "
-                         "spread of all of them is reported beside it")
+                         "spread of all of them is reported beside it "
+                         "(default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement besides the headline: repeat "
+                         "spread, host enqueue time, secondary workloads, "
+                         "phase / latency figures, rooflines with their "
+                         "rocprofv3 child passes, CPU baseline (each still "
+                         "subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits and box encodings of every frame "
+                         "of the last timed step as DIR/<name>.npy (float32, "
+                         "at most 64 MB in all; inference only)")
     ap.add_argument("--edge-arith", choices=("f32", "bf16x3", "f16x2"), default="f32",
                     help="arithmetic of the per-edge 300x300 product: f32 = "
                          "fp32 MFMA (the headline); bf16x3 = the SECONDARY "
@@ -1265,6 +1286,10 @@ def parse_args(argv=None):
     ap.add_argument("--tune", action="append", default=[],
                     help="key=value library tunable (experiments; repeatable)")
     args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.dump_outputs and (args.train or args.e2e):
+        ap.error("--dump-outputs covers the inference benchmark only")
     if args.preset is None:
         args.preset = "ped_dense" if args.config.startswith("ped") else (
             "car" if args.train else "car_600k")
@@ -1460,6 +1485,29 @@ def _gather_shapes(torch, dist, dev, shapes, world):
     out = [torch.zeros_like(a) for _ in range(world)]
     dist.all_gather(out, a)
     return torch.cat(out).tolist()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, step_outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: frame j of the last timed step as
+    out_dir/frame<j>_logits.npy [K, nc] and frame<j>_box_encodings.npy
+    [K, nc, len], float32.  Past `limit` bytes in all, every array keeps the
+    same fixed, seeded (numpy seed 0), sorted sample of its rows."""
+    arrays = {}
+    for j, (logits, boxes) in enumerate(step_outputs):
+        arrays["frame%d_logits" % j] = logits
+        arrays["frame%d_box_encodings" % j] = boxes
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > limit and len(a):
+            keep = max(1, len(a) * limit // total)
+            rows = np.random.default_rng(0).choice(len(a), keep, replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def dist_info(dist, world):
@@ -1801,27 +1849,31 @@ def main(argv=None):
                        torch.from_numpy(inten).to(dev), xyz, inten)
 
         def run(lo, hi):
-            """Frames lo..hi-1 of this rank's stream.  Default: software
-            pipeline on HIP streams (graph build of frame i+1 overlaps the GNN
-            of frame i); --no-pipeline runs them strictly one after the other."""
+            """Frames lo..hi-1 of this rank's stream; returns the (logits,
+            box_encodings) of at least the last `fps` frames (one step).
+            Default: software pipeline on HIP streams (graph build of frame
+            i+1 overlaps the GNN of frame i); --no-pipeline runs them strictly
+            one after the other."""
             fr = [pool[seed_of(i)][:2] for i in range(lo, hi)]
             deferred = not args.host_sized
             if args.no_pipeline:
                 if deferred:
                     outs = [engine.run_frame_deferred(x, f) for x, f in fr]
-                    return [d.result() for d in outs][-1]
-                out = None
+                    return [d.result() for d in outs]
+                # (only one step's outputs held: earlier ones are freed as
+                # the frames go, as before)
+                last = collections.deque(maxlen=fps)
                 for x, f in fr:
-                    out = engine.run_frame(x, f)
-                return out
+                    last.append(engine.run_frame(x, f))
+                return list(last)
             n_fs = frame_streams_for(args, engine.config_name)
             if deferred and n_fs > 0 and args.graph_cus <= 0:
                 return engine.run_frames_on_streams(
-                    fr, n_fs, gnn_priority=args.gnn_priority)[-1]
+                    fr, n_fs, gnn_priority=args.gnn_priority)
             return engine.run_frames_pipelined(
                 fr, compute_streams=args.compute_streams,
                 graph_cus=args.graph_cus, lookahead=args.lookahead,
-                deferred=deferred, graph_streams=args.graph_streams)[-1]
+                deferred=deferred, graph_streams=args.graph_streams)
 
         if warmup:
             run(0, warmup * fps)
@@ -1831,23 +1883,25 @@ def main(argv=None):
             engine.frame_shapes = []
             _sync(torch, dist)
             t0 = time.perf_counter()
-            out = run(lo, lo + per_region)
+            outs = run(lo, lo + per_region)
             _sync(torch, dist)
             el, = _max_over_ranks(torch, dist, dev,
                                   [time.perf_counter() - t0])
             regions.append(el)
-            assert torch.isfinite(out[0]).all()
+            assert torch.isfinite(outs[-1][0]).all()
             assert len(engine.frame_shapes) == per_region
             if r == 0:
                 shapes = _gather_shapes(
                     torch, dist, dev, [s[:3] for s in engine.frame_shapes],
                     world)
         measure.regions = regions
+        # what the last timed step returned to its caller (--dump-outputs)
+        measure.last_step = outs[-fps:]
         # Python time to ENQUEUE one frame (~110 ctypes launches: graph build
         # + GNN), nothing read back: 16 frames onto an idle device -- far
         # below any queue depth, so the host never waits for the device here
         measure.enqueue_ms = None
-        if not args.no_pipeline and not args.host_sized and \
+        if args.full and not args.no_pipeline and not args.host_sized and \
                 frame_streams_for(args, engine.config_name) > 0 and \
                 args.graph_cus <= 0:
             n_enq = min(16, per_region)
@@ -1865,8 +1919,12 @@ def main(argv=None):
     elapsed, shapes, pool = measure(args.preset, args.steps, args.warmup,
                                     fps=fps_h, repeats=max(1, args.repeats))
     regions_h, enqueue_ms_h = list(measure.regions), measure.enqueue_ms
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, measure.last_step)
+    measure.last_step = None
     second = None
-    if world == 1 and not args.no_secondary and args.preset == "car_600k":
+    if args.full and world == 1 and not args.no_secondary and \
+            args.preset == "car_600k":
         s2 = max(8, args.steps // 2)
         e2, sh2, _ = measure("car", s2, 4)
         st2 = pool_statistics(cfg, sh2)
@@ -1882,8 +1940,8 @@ def main(argv=None):
     # headline command only; `--config ped_cyl_auto_T3` / `--train` are the
     # full-length forms): the ped_cyl dense-scan stress and the training step
     ped = trn = e2e = None
-    if world == 1 and not args.no_secondary and args.preset == "car_600k" \
-            and args.config == "car_auto_T3":
+    if args.full and world == 1 and not args.no_secondary and \
+            args.preset == "car_600k" and args.config == "car_auto_T3":
         ped = secondary_ped(args, torch, dev, measure)
         trn = secondary_train(args, torch, dev)
         e2e = secondary_e2e(args, torch, dev,
@@ -1896,8 +1954,9 @@ def main(argv=None):
     # significand bits, three products; csrc/edge_ws_f16.h) -- next to how far
     # their logits are from the fp32-MFMA path's on the pool's first frame
     sec16 = {}
-    if world == 1 and not args.no_secondary and args.edge_arith == "f32" \
-            and args.preset == "car_600k" and args.config == "car_auto_T3":
+    if args.full and world == 1 and not args.no_secondary and \
+            args.edge_arith == "f32" and args.preset == "car_600k" and \
+            args.config == "car_auto_T3":
         first = sorted(pool)[0]
         x0_, f0_ = pool[first][:2]
         lg32, bx32 = [t.clone() for t in engine.run_frame(x0_, f0_)]
@@ -1976,87 +2035,92 @@ def main(argv=None):
         # standalone kernel measurements
         first = sorted(pool)[0]
         x, f, xyz_np, inten_np = pool[first]
-        engine.time_dict = {}
-        for _ in range(3):
-            engine.run_frame(x, f, timed=True)
-        coords, kps, edges = engine.last_graph
-        n_k = int(coords[1].shape[0])
-        n_e1 = int(edges[1].shape[0])
-        frames = engine.time_dict['frames']
-        # one frame alone, enqueue to results on the host: host-sized graph
-        # (the builder waits twice for sizes) vs capacity form (one read, at
-        # the end)
-        lat = {"host-sized": [], "capacity form": [],
-               "capacity form, overlapped build": []}
-        captured = captured_ov = capture_note = None
-        if not args.no_capture:
-            lat["capacity form, one hipGraph"] = []
-            captured = engine.capture_frame(x, f)
-            if not args.no_capture_overlap:
-                try:
-                    captured_ov = engine.capture_frame(x, f,
-                                                       overlap_build=True)
-                    lat["capacity form, overlapped build, one hipGraph"] = []
-                except Exception as exc:   # reported, never fatal to the line
-                    capture_note = "overlapped-build capture failed: %r" % (
-                        exc,)
-        for _ in range(9):
-            for key in lat:
+        if args.full:
+            engine.time_dict = {}
+            for _ in range(3):
+                engine.run_frame(x, f, timed=True)
+            coords, kps, edges = engine.last_graph
+            n_k = int(coords[1].shape[0])
+            n_e1 = int(edges[1].shape[0])
+            frames = engine.time_dict['frames']
+            # one frame alone, enqueue to results on the host: host-sized
+            # graph (the builder waits twice for sizes) vs capacity form (one
+            # read, at the end)
+            lat = {"host-sized": [], "capacity form": [],
+                   "capacity form, overlapped build": []}
+            captured = captured_ov = capture_note = None
+            if not args.no_capture:
+                lat["capacity form, one hipGraph"] = []
+                captured = engine.capture_frame(x, f)
+                if not args.no_capture_overlap:
+                    try:
+                        captured_ov = engine.capture_frame(x, f,
+                                                           overlap_build=True)
+                        lat["capacity form, overlapped build, one "
+                            "hipGraph"] = []
+                    except Exception as exc:   # reported, never fatal
+                        capture_note = "overlapped-build capture failed: " \
+                                       "%r" % (exc,)
+            for _ in range(9):
+                for key in lat:
+                    torch.cuda.synchronize()
+                    tp = time.perf_counter()
+                    if key == "host-sized":
+                        engine.run_frame(x, f)
+                    elif key == "capacity form":
+                        engine.run_frame_deferred(x, f).result()
+                    elif key == "capacity form, overlapped build":
+                        engine.run_frame_deferred(x, f,
+                                                  overlap_build=True).result()
+                    elif key == "capacity form, one hipGraph":
+                        captured.replay(x, f).result()
+                    else:
+                        captured_ov.replay(x, f).result()
+                    torch.cuda.synchronize()
+                    lat[key].append((time.perf_counter() - tp) * 1e3)
+            del captured, captured_ov
+            lat = {k_: float(np.median(v[2:])) for k_, v in lat.items()}
+            if capture_note:
+                lat["note"] = capture_note
+            # the graph build alone in capacity form (enqueue to idle device):
+            # in order on one stream vs its independent parts on side streams
+            build = {"capacity form": [],
+                     "capacity form, overlapped build": []}
+            for _ in range(9):
+                for key in build:
+                    torch.cuda.synchronize()
+                    tp = time.perf_counter()
+                    g_ = engine.build_graph_deferred(
+                        x, overlap=key.endswith("overlapped build"))
+                    torch.cuda.synchronize()
+                    build[key].append((time.perf_counter() - tp) * 1e3)
+                    del g_
+            build = {k_: float(np.median(v[2:])) for k_, v in build.items()}
+            engine.run_frame(x, f)   # last_graph back to the host-sized form
+            coords, kps, edges = engine.last_graph
+            # run.py's last two phases ("decode box", "nms", run.py:264-326) on
+            # this frame's outputs -- reported beside the metric, not part
+            # of it (the metric excludes NMS)
+            from pointgnn_amd import kitti_output, nms as pg_nms
+            logits, box_enc = engine.run_frame(x, f)
+            probs = torch.softmax(logits, dim=1)
+            lmap = kitti_output.LABEL_MAPS[cfg.get('label_method', 'Car')]
+            post_ms = []
+            for _ in range(5):
                 torch.cuda.synchronize()
                 tp = time.perf_counter()
-                if key == "host-sized":
-                    engine.run_frame(x, f)
-                elif key == "capacity form":
-                    engine.run_frame_deferred(x, f).result()
-                elif key == "capacity form, overlapped build":
-                    engine.run_frame_deferred(x, f,
-                                              overlap_build=True).result()
-                elif key == "capacity form, one hipGraph":
-                    captured.replay(x, f).result()
-                else:
-                    captured_ov.replay(x, f).result()
+                det = pg_nms.detect_boxes(
+                    probs, box_enc, coords[-1], lmap,
+                    cfg.get('nms_overlapped_thres', 0.01))
                 torch.cuda.synchronize()
-                lat[key].append((time.perf_counter() - tp) * 1e3)
-        del captured, captured_ov
-        lat = {k_: float(np.median(v[2:])) for k_, v in lat.items()}
-        if capture_note:
-            lat["note"] = capture_note
-        # the graph build alone in capacity form (enqueue to idle device):
-        # in order on one stream vs its independent parts on side streams
-        build = {"capacity form": [], "capacity form, overlapped build": []}
-        for _ in range(9):
-            for key in build:
-                torch.cuda.synchronize()
-                tp = time.perf_counter()
-                g_ = engine.build_graph_deferred(
-                    x, overlap=key.endswith("overlapped build"))
-                torch.cuda.synchronize()
-                build[key].append((time.perf_counter() - tp) * 1e3)
-                del g_
-        build = {k_: float(np.median(v[2:])) for k_, v in build.items()}
-        engine.run_frame(x, f)   # last_graph back to the host-sized form
-        coords, kps, edges = engine.last_graph
-        # run.py's last two phases ("decode box", "nms", run.py:264-326) on
-        # this frame's outputs -- reported beside the metric, not part of it
-        # (the metric excludes NMS)
-        from pointgnn_amd import kitti_output, nms as pg_nms
-        logits, box_enc = engine.run_frame(x, f)
-        probs = torch.softmax(logits, dim=1)
-        lmap = kitti_output.LABEL_MAPS[cfg.get('label_method', 'Car')]
-        post_ms = []
-        for _ in range(5):
-            torch.cuda.synchronize()
-            tp = time.perf_counter()
-            det = pg_nms.detect_boxes(probs, box_enc, coords[-1], lmap,
-                                      cfg.get('nms_overlapped_thres', 0.01))
-            torch.cuda.synchronize()
-            post_ms.append((time.perf_counter() - tp) * 1e3)
-        post = {"ms": float(np.median(post_ms[1:])),
-                "candidates": int(pg_nms.select_candidates(probs)[0].numel()),
-                "kept": int(det[0].numel()),
-                "note": "seeded weights give near-uniform class "
-                        "probabilities: thousands of candidates, a stress "
-                        "case for the NMS"}
+                post_ms.append((time.perf_counter() - tp) * 1e3)
+            post = {"ms": float(np.median(post_ms[1:])),
+                    "candidates":
+                        int(pg_nms.select_candidates(probs)[0].numel()),
+                    "kept": int(det[0].numel()),
+                    "note": "seeded weights give near-uniform class "
+                            "probabilities: thousands of candidates, a stress "
+                            "case for the NMS"}
         st = pool_statistics(cfg, shapes)
         assert st["frames"] == world * args.steps * fps_h
         n_builders = 1 if (args.host_sized or args.graph_cus > 0) else \
@@ -2098,11 +2162,6 @@ def main(argv=None):
                     "n": len(rep_ms), "min": min(rep_ms),
                     "median": float(np.median(rep_ms)), "max": max(rep_ms),
                     "all": rep_ms},
-                "host_enqueue_ms_per_frame": enqueue_ms_h,
-                "host_enqueue_note": "Python time to enqueue one frame "
-                    "(graph build + GNN, ~110 C-ABI launches) with nothing "
-                    "read back, max over ranks; the device needs "
-                    "ms_per_frame_per_gpu, the ratio is the host's headroom",
                 "cpu_affinity": getattr(args, "cpu_affinity", None),
                 "sizes": "host-read (two waits per frame in the graph "
                          "builder)" if args.host_sized else
@@ -2132,6 +2191,16 @@ def main(argv=None):
                 "executed_tflops": st["exe_flops_mean"] * fps / world / 1e12,
                 "executed_frac_of_fp32_mfma_peak":
                     st["exe_flops_mean"] * fps / world / 1e12 / FP32_MFMA_PEAK_TF,
+                "capacity_overflow_rebuilds": engine.deferred_overflows,
+            },
+        }
+        if args.full:
+            res["config"].update({
+                "host_enqueue_ms_per_frame": enqueue_ms_h,
+                "host_enqueue_note": "Python time to enqueue one frame "
+                    "(graph build + GNN, ~110 C-ABI launches) with nothing "
+                    "read back, max over ranks; the device needs "
+                    "ms_per_frame_per_gpu, the ratio is the host's headroom",
                 "phase_ms_frame_seed%d" % first: {
                     "gen graph": engine.time_dict['gen graph'] / frames * 1e3,
                     "gnn inference":
@@ -2139,10 +2208,8 @@ def main(argv=None):
                     "decode box + nms": post["ms"]},
                 "latency_ms_frame_seed%d" % first: lat,
                 "graph_build_ms_frame_seed%d" % first: build,
-                "capacity_overflow_rebuilds": engine.deferred_overflows,
                 "postprocess": post,
-            },
-        }
+            })
         if second is not None:
             res["config"]["secondary"] = second
         for arith, line in sec16.items():
@@ -2153,7 +2220,7 @@ def main(argv=None):
             res["config"]["secondary_train"] = trn
         if e2e is not None:
             res["config"]["secondary_e2e"] = e2e
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             width = cfg['model_kwargs']['layer_configs'][1]['kwargs'][
                 'edge_MLP_depth_list'][-1] if len(
                 cfg['model_kwargs']['layer_configs']) > 2 else 300
@@ -2202,7 +2269,7 @@ def main(argv=None):
                     "total": sum(per_frame.values()),
                     "top": {k: round(v, 1) for k, v in top}}
             res["roofline_graph"] = roofline_graph(torch, cfg, coords)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(cfg, params, xyz_np, inten_np,
                                                args.cpu_budget)
         print(json.dumps(res), flush=True)

@@ -85,7 +85,7 @@ def test_bench_two_ranks_real_engine_on_one_gpu():
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
            "--steps", "3", "--warmup", "1", "--frames-per-step", "4",
            "--repeats", "2", "--preset", "car", "--frames", "2",
-           "--no-roofline", "--no-cpu-baseline", "--no-capture"]
+           "--full", "--no-roofline", "--no-cpu-baseline", "--no-capture"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True,
                        timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]

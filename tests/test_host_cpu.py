@@ -14,7 +14,20 @@ from pointgnn_amd.synthetic import synthetic_cloud
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
-REF = "/root/reference"
+# what the reference checkout holds, computed by
+# tests/golden/make_golden_reference.py
+REF_DIGESTS = os.path.join(GOLD, "ref_digests.json")
+
+
+def _ref_digests():
+    with open(REF_DIGESTS) as f:
+        return json.load(f)
+
+
+def _sha256(path):
+    import hashlib
+    with open(path, "rb") as f:
+        return hashlib.sha256(f.read()).hexdigest()
 
 
 def test_param_counts_match_reference_checkpoints():
@@ -35,8 +48,9 @@ def test_variable_names_match_golden_weights():
             assert w[k].shape == tuple(shape)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree absent")
 def test_generated_configs_equal_reference_json():
+    from golden.make_golden_reference import config_digest
+    ref = _ref_digests()["configs"]
     pairs = [("car_auto_T0", "car_auto_T0_train_config"),
              ("car_auto_T1", "car_auto_T1_train_config"),
              ("car_auto_T2", "car_auto_T2_train_config"),
@@ -45,19 +59,17 @@ def test_generated_configs_equal_reference_json():
              ("car_fixed_T3", "car_fixed_T3_train_config"),
              ("ped_cyl_auto_T3", "ped_cyl_auto_T3_trainval_config")]
     for name, fname in pairs:
-        ref = configs.load_config(os.path.join(REF, "configs", fname))
-        assert ref == configs.get_config(name), fname
+        assert ref[fname] == config_digest(configs.get_config(name)), fname
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree absent")
 def test_generated_train_and_eval_configs_equal_reference_json(tmp_path):
+    from golden.make_golden_reference import config_digest
+    ref = _ref_digests()["configs"]
     for name in configs._TRAIN_TABLE:
-        ref = configs.load_train_config(
-            os.path.join(REF, "configs", name + "_train_config"))
-        assert ref == configs.get_train_config(name), name
-        ev = configs.load_config(os.path.join(REF, "configs",
-                                              name + "_eval_config"))
-        assert ev == configs.get_eval_config(name), name
+        assert ref[name + "_train_config"] == config_digest(
+            configs.get_train_config(name)), name
+        assert ref[name + "_eval_config"] == config_digest(
+            configs.get_eval_config(name)), name
     # save/load round trip in the reference's JSON form
     path = str(tmp_path / "train_config")
     configs.save_train_config(path, configs.get_train_config("car_auto_T3_train"))
@@ -65,20 +77,38 @@ def test_generated_train_and_eval_configs_equal_reference_json(tmp_path):
         configs.get_train_config("car_auto_T3_train")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree absent")
-def test_tf_bundle_reader_on_reference_checkpoints():
+def _reference_checkpoint(tmp_path, t):
+    """checkpoints/car_auto_T<t>_train re-encoded from the golden weights and
+    proven byte-identical to the TF-written files by their SHA-256."""
+    gold = np.load(os.path.join(GOLD, "weights_car_auto_T%d.npz" % t))
+    d = str(tmp_path / ("t%d" % t))
+    prefix = tf_bundle.save_checkpoint(d, {k: gold[k] for k in gold.files},
+                                       global_step=1400000)
+    want = _ref_digests()["checkpoints"]["car_auto_T%d_train" % t]
+    assert sorted(want) == sorted(os.listdir(d))
+    for f in want:
+        assert _sha256(os.path.join(d, f)) == want[f], f
+    return d, prefix
+
+
+def test_tf_bundle_reader_on_reference_checkpoints(tmp_path):
     for t in (0, 1):
-        ck = tf_bundle.load_checkpoint(
-            os.path.join(REF, "checkpoints", "car_auto_T%d_train" % t))
+        src, prefix = _reference_checkpoint(tmp_path, t)
+        ck = tf_bundle.load_checkpoint(src)
         assert int(ck["Variable"]) == 1400000
         gold = np.load(os.path.join(GOLD, "weights_car_auto_T%d.npz" % t))
         for k in gold.files:
             assert np.array_equal(ck[k], gold[k])
-    # index-only checkpoints still list names/shapes
-    names = tf_bundle.list_variables(os.path.join(
-        REF, "checkpoints", "car_auto_T3_train", "model-1400000"))
+        # index-only checkpoints still list names/shapes
+        os.remove(prefix + ".data-00000-of-00001")
+        spec = dict(weights.variable_specs(configs.car_auto_config(t)))
+        got = {n: s for n, _, s, _, _ in tf_bundle.list_variables(prefix)
+               if n != "Variable"}
+        assert got == {k: tuple(v) for k, v in spec.items()}
+    # what the reader listed from the reference's index-only T3 checkpoint
+    names = _ref_digests()["car_auto_T3_train_variables"]
     spec = dict(weights.variable_specs(configs.car_auto_config(3)))
-    got = {n: s for n, _, s, _, _ in names if n != "Variable"}
+    got = {n: tuple(s) for n, s in names.items() if n != "Variable"}
     assert got == {k: tuple(v) for k, v in spec.items()}
 
 
@@ -104,24 +134,13 @@ def test_checkpoint_writer_round_trip(tmp_path):
     assert names == sorted(names)                      # SSTable key order
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree absent")
 def test_checkpoint_writer_is_byte_identical_to_tensorflow(tmp_path):
     """Re-encoding the variables of the reference's TF-written checkpoints
-    reproduces both files bit for bit (table layout, prefix compression,
-    masked crc32c of every tensor and block)."""
+    reproduces both files and the `checkpoint` file bit for bit (table
+    layout, prefix compression, masked crc32c of every tensor and block):
+    SHA-256 of the reference's files in ref_digests.json."""
     for t in (0, 1):
-        src = os.path.join(REF, "checkpoints", "car_auto_T%d_train" % t)
-        v = tf_bundle.load_checkpoint(src)
-        step = int(v.pop("Variable"))
-        d = tmp_path / ("t%d" % t)
-        prefix = tf_bundle.save_checkpoint(str(d), v, global_step=step)
-        for ext in (".index", ".data-00000-of-00001"):
-            with open(prefix + ext, "rb") as a, \
-                    open(os.path.join(src, "model-%d%s" % (step, ext)), "rb") as b:
-                assert a.read() == b.read(), ext
-        with open(os.path.join(str(d), "checkpoint")) as a, \
-                open(os.path.join(src, "checkpoint")) as b:
-            assert a.read() == b.read()
+        _reference_checkpoint(tmp_path, t)
 
 
 def test_synthetic_cloud_is_deterministic_and_shaped():

@@ -1,7 +1,7 @@
 """Pins the oracle (oracle/*.py, oracle/*.c) against the committed golden
 fixtures, which hold outputs of the REFERENCE's real graph_gen.py run in the
-build container (tests/golden/make_golden.py), and against the reference
-itself when /root/reference is present.  No GPU."""
+build container (tests/golden/make_golden.py, make_golden_reference.py).
+No GPU."""
 import os
 import random
 
@@ -13,7 +13,6 @@ from pointgnn_amd import configs
 from pointgnn_amd.synthetic import synthetic_cloud
 from oracle import graph_oracle as go
 from oracle import gnn_oracle as gn
-from _refimport import reference_graph_gen
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -65,24 +64,24 @@ def test_multi_level_random_mode_golden(tag, rnd):
 
 
 def test_oracle_against_live_reference():
-    gg = reference_graph_gen()
-    if gg is None:
-        pytest.skip("/root/reference not present (GPU box)")
-    from pointgnn_amd.synthetic import synthetic_cloud
-    xyz, _ = synthetic_cloud(seed=3, preset="tiny")
+    """The reference's graph_gen run on the seeded `tiny` cloud
+    (live_reference.npz, tests/golden/make_golden_reference.py): the oracle's
+    radius graph and multi-level graph equal its output."""
+    g = gold("live_reference.npz")
+    xyz = g["xyz"]
+    assert np.array_equal(xyz, synthetic_cloud(seed=3, preset="tiny")[0])
     kp, _ = go.keypoints_center(xyz, xyz, 0.4)
-    ref = gg.gen_disjointed_rnn_local_graph_v3(xyz, kp, 1.0, -1)
-    assert np.array_equal(go.radius_graph_c(xyz, kp, 1.0),
-                          go.canonical_edges(ref))
+    assert np.array_equal(kp, g["kp"])
+    assert np.array_equal(go.radius_graph_c(xyz, kp, 1.0), g["radius_edges"])
     cfg = configs.car_auto_config(3)
     np.random.seed(5)
     random.seed(5)
-    rv, rk, re = gg.gen_multi_level_local_graph_v3(xyz, **cfg["graph_gen_kwargs"])
-    np.random.seed(5)
-    random.seed(5)
     ov, ok, oe = go.multi_level_graph(xyz, **cfg["graph_gen_kwargs"])
-    for a, b in zip(rk + re, ok + oe):
-        assert np.array_equal(np.asarray(a), np.asarray(b))
+    want = [g["multi_kp%d" % i] for i in range(len(ok))] + \
+        [g["multi_edges%d" % i] for i in range(len(oe))]
+    assert len(want) == sum(1 for k in g if k.startswith("multi_"))
+    for a, b in zip(want, ok + oe):
+        assert np.array_equal(a, np.asarray(b))
 
 
 def test_center_keypoints_properties():
@@ -408,29 +407,6 @@ def test_multi_level_pooling_random_golden(tag, rnd):
         assert np.array_equal(kps[l], g["tiny_%s_kp%d" % (tag, l)])
     assert [len(c) for c in coords] + [len(e) for e in edges] == \
         list(g["tiny_%s_counts" % tag])
-
-
-def test_multi_level_pooling_golden_is_the_reference_live():
-    """With /root/reference present: the fixture equals a fresh run of the
-    reference's function (and so does the oracle, by the tests above)."""
-    gg = reference_graph_gen()
-    if gg is None:
-        pytest.skip("reference tree not present (GPU box)")
-    import sys
-    sys.path.insert(0, GOLD)
-    try:
-        import make_golden_multilevel as mk
-    finally:
-        sys.path.remove(GOLD)
-    mk.install_open3d_stand_in()
-    g = gold("graph_multilevel.npz")
-    xyz = g["tiny_xyz"]
-    vc, ki, el = gg.gen_multi_level_local_graph_v3(
-        xyz, mk.BASE_VOXEL, mk.LEVEL_CONFIGS, add_rnd3d=False,
-        downsample_method='center')
-    for l in range(3):
-        assert np.array_equal(np.asarray(ki[l]), g["tiny_center_kp%d" % l])
-        assert np.array_equal(np.asarray(el[l]), g["tiny_center_edges%d" % l])
 
 
 def test_torch_cpu_port_equals_the_numpy_oracle():

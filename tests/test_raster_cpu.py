@@ -1,9 +1,8 @@
 """oracle/raster_oracle.py (the cv2.fillPoly restatement behind
 nms.overlapped_boxes_3d, nms.py:29-62) against properties cv2.fillPoly has in
-every OpenCV version, against the reference's own nms.overlapped_boxes_3d
-running on the stand-in, and against the committed fixture."""
+every OpenCV version, and against the committed fixture: the reference's own
+nms.overlapped_boxes_3d run on the stand-in (make_golden_aug.py)."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -11,7 +10,6 @@ import pytest
 from oracle import raster_oracle as RO
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF = "/root/reference"
 
 
 def _fill(pts, h, w):
@@ -153,39 +151,3 @@ def test_fixture_reproduces():
                                          fix[tag + "_list"])
         assert np.array_equal(got, fix[tag + "_overlap"], equal_nan=True)
     assert np.sum(fix["a10_overlap"] > 0) > 50
-
-
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "models")),
-                    reason="reference tree only exists in the build container")
-def test_restated_overlap_equals_reference_function_on_the_stand_in():
-    """oracle.overlapped_boxes_3d (restatement of nms.py:29-62) == the
-    reference's nms.overlapped_boxes_3d with `cv2` = the fillPoly stand-in."""
-    import types
-    saved = {k: sys.modules.get(k) for k in ("cv2", "shapely",
-                                             "shapely.geometry", "models",
-                                             "models.nms")}
-    shp, geo = types.ModuleType("shapely"), types.ModuleType("shapely.geometry")
-    geo.Polygon = object
-    shp.geometry = geo
-    sys.modules.update({"cv2": RO.cv2_stub(), "shapely": shp,
-                        "shapely.geometry": geo})
-    sys.modules.pop("models.nms", None)
-    sys.modules.pop("models", None)
-    sys.path.insert(0, REF)
-    try:
-        from models import nms as ref_nms
-        fix = np.load(os.path.join(GOLD, "raster_overlap.npz"))
-        for tag in ("a10", "quad"):
-            with np.errstate(all="ignore"):
-                want = ref_nms.overlapped_boxes_3d(fix[tag + "_single"],
-                                                   fix[tag + "_list"])
-                got = RO.overlapped_boxes_3d(fix[tag + "_single"],
-                                             fix[tag + "_list"])
-            assert np.array_equal(got, want, equal_nan=True)
-    finally:
-        sys.path.remove(REF)
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v

@@ -271,13 +271,13 @@ def _run_bench(argv, env_extra, timeout=240):
 
 def test_bench_self_launches_its_ranks():
     """`python bench.py --gpus 2` with no launcher around it creates its two
-    ranks itself (the driver's plain command line); rank 0 prints exactly one
-    JSON line whose n_gpus is what the process group saw.  PGNN_BENCH_STUB
-    swaps the engine for a sleep and RCCL for gloo -- the launcher, the rank
-    plumbing, the barrier + MAX timing rule and the JSON contract are the
-    real code."""
-    p, lines = _run_bench(["--gpus", "2", "--steps", "6", "--warmup", "2"],
-                          {"PGNN_BENCH_STUB": "1"})
+    ranks itself (the driver's command line, with --full: five timed
+    regions); rank 0 prints exactly one JSON line whose n_gpus is what the
+    process group saw.  PGNN_BENCH_STUB swaps the engine for a sleep and RCCL
+    for gloo -- the launcher, the rank plumbing, the barrier + MAX timing rule
+    and the JSON contract are the real code."""
+    p, lines = _run_bench(["--gpus", "2", "--steps", "6", "--warmup", "2",
+                           "--full"], {"PGNN_BENCH_STUB": "1"})
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(lines) == 1
     r = lines[0]
@@ -297,6 +297,54 @@ def test_bench_self_launches_its_ranks():
     assert rep["min"] <= rep["median"] <= rep["max"]
     assert r["config"]["timed_region_s"] == pytest.approx(
         r["ms_per_step"] * 6e-3)
+
+
+def test_bench_plain_run_times_exactly_steps():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` (stub engine) times
+    one region of exactly N steps: ms_per_step is that region over N, and the
+    line carries the headline keys."""
+    p, lines = _run_bench(["--gpus", "1", "--steps", "5", "--warmup", "1"],
+                          {"PGNN_BENCH_STUB": "1"})
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert len(lines) == 1
+    r = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype",
+                "ms_per_step"):
+        assert key in r, key
+    assert r["steps"] == 5 and r["warmup"] == 1
+    rep = r["config"]["repeat_ms_per_step"]
+    assert rep["n"] == 1 and rep["all"] == [r["ms_per_step"]]
+    assert r["config"]["frames_timed"] == 5 * 8
+    assert r["config"]["timed_region_s"] == pytest.approx(
+        r["ms_per_step"] * 5e-3)
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path):
+    """bench.dump_outputs: float32 .npy per frame and array; past the byte
+    limit every array keeps the same seeded, sorted sample of its rows."""
+    import bench
+    import numpy as np
+    g = torch.Generator().manual_seed(0)
+    step = [(torch.randn(100, 4, generator=g, dtype=torch.float64),
+             torch.randn(100, 4, 7, generator=g)) for _ in range(2)]
+    bench.dump_outputs(str(tmp_path / "all"), step)
+    for j, (lg, bx) in enumerate(step):
+        a = np.load(str(tmp_path / "all" / ("frame%d_logits.npy" % j)))
+        b = np.load(str(tmp_path / "all" / ("frame%d_box_encodings.npy" % j)))
+        assert a.dtype == np.float32 and b.dtype == np.float32
+        assert np.array_equal(a, lg.float().numpy())
+        assert np.array_equal(b, bx.numpy())
+    total = sum(4 * (l.numel() + b.numel()) for l, b in step)
+    limit = total // 4
+    bench.dump_outputs(str(tmp_path / "cut"), step, limit=limit)
+    files = sorted((tmp_path / "cut").glob("*.npy"))
+    assert sum(f.stat().st_size - 128 for f in files) <= limit
+    lg = np.load(str(tmp_path / "cut" / "frame1_logits.npy"))
+    full = step[1][0].float().numpy()
+    rows = [int(np.flatnonzero((full == r).all(1))[0]) for r in lg]
+    assert 0 < len(rows) < 100 and rows == sorted(rows)
+    bx = np.load(str(tmp_path / "cut" / "frame1_box_encodings.npy"))
+    assert np.array_equal(bx, step[1][1].numpy()[rows])
 
 
 def test_bench_rank_binding_splits_cpus_without_numa_info():

@@ -10,9 +10,9 @@ Here:
   * oracle/gnn_oracle.predict must reproduce the graph's logits/boxes;
   * oracle/train_oracle (float64 autograd) must reproduce losses + gradients;
   * oracle/metrics_oracle must reproduce the tf.metrics values;
-  * with /root/reference present the graphs are re-evaluated live.
+  * the graphs' own evaluation by oracle/tf_graph_ref.py (tfgraph_live.npz)
+    matches the fixtures and the oracle.
 No GPU."""
-import glob
 import os
 import struct
 
@@ -248,41 +248,42 @@ def test_sgd_update_of_reference_tf_graph():
 
 
 # ------------------------------------------------------------ live reference
+def segment_max_nodes(ref):
+    """Tower 0's UnsortedSegmentMax nodes of an oracle.tf_graph_ref graph."""
+    return [n for n in ref.g.order
+            if ref.g.nodes[n].op == "UnsortedSegmentMax"
+            and not n.startswith("gradients") and "_1/" not in n
+            and "_2/" not in n and "_3/" not in n]
+
+
 @pytest.mark.parametrize("name", ["car_auto_T0", "car_auto_T1"])
 def test_reference_graph_live(name):
-    """With /root/reference present: re-evaluate the shipped .meta and compare
-    with the committed fixture AND with the oracle, bit for bit (same NumPy
-    kernels in the same order)."""
-    metas = glob.glob("/root/reference/checkpoints/%s/model-*.meta"
-                      % CHECKPOINTS[name])
-    if not metas:
-        pytest.skip("/root/reference not present (GPU box)")
-    from oracle import tf_graph_ref as tg
-    ref = tg.ReferenceGraph(metas[0])
+    """The shipped .meta re-evaluated by oracle/tf_graph_ref.py
+    (tfgraph_live.npz, tests/golden/make_golden_reference.py) against the
+    committed fixture AND the oracle, bit for bit (same NumPy kernels in the
+    same order)."""
+    live = gold("tfgraph_live.npz")
     cfg = configs.get_config(name)
     w, _ = fixture_weights(name, cfg)
     # the graph's variables are exactly the checkpoint's (names and shapes)
-    assert {v: tuple(s) for v, s in ref.variable_shapes().items()} == \
-        {v: tuple(np.shape(w[v])) for v in ref.variable_names}
-    ref.set_weights(w)
+    pre = name + "/shape/"
+    shapes = {k[len(pre):]: tuple(v) for k, v in live.items()
+              if k.startswith(pre)}
+    assert shapes and shapes == {v: tuple(np.shape(w[v])) for v in shapes}
+    lg, bx = live[name + "/logits"], live[name + "/box_encodings"]
     kw = graph_inputs("graph_tiny.npz")
-    lg, bx, pr = ref.predict(**kw)
     t = gold("tfgraph_%s.npz" % name)
     np.testing.assert_allclose(lg, t["logits"], atol=2e-5, rtol=0)
     lo, bo = gn.predict(w, cfg, kw["features"], kw["coords"], kw["keypoints"],
                         kw["edges"], dtype=np.float32)
     assert np.array_equal(lg, lo) and np.array_equal(bx, bo)
-    # per-layer: every UnsortedSegmentMax output of tower 0 equals the oracle's
-    tw = ref.towers[0]
-    seg = [n for n in ref.g.order
-           if ref.g.nodes[n].op == "UnsortedSegmentMax"
-           and not n.startswith("gradients") and "_1/" not in n
-           and "_2/" not in n and "_3/" not in n]
-    assert len(seg) == len(cfg["model_kwargs"]["layer_configs"]) - 1
-    fd = ref.feed(0, is_training=False, **kw)
-    vals = ref.g.run(seg, fd)
+    # per layer: one UnsortedSegmentMax of tower 0 per GNN layer
+    n_seg = int(live[name + "/n_segment_max"])
+    assert n_seg == len(cfg["model_kwargs"]["layer_configs"]) - 1
     _, _, feats = gn.predict(w, cfg, kw["features"], kw["coords"],
                              kw["keypoints"], kw["edges"], dtype=np.float32,
                              return_features=True)
-    assert vals[0].shape == (kw["coords"][1].shape[0], 300)
-    assert tw["logits"] in ref.g.nodes and len(feats) == len(seg) + 1
+    assert tuple(live[name + "/segment_max0_shape"]) == \
+        (kw["coords"][1].shape[0], 300)
+    assert bool(live[name + "/has_logits_node"]) and \
+        len(feats) == n_seg + 1

@@ -22,9 +22,9 @@ tests)
   echo "SMOKE rc=$? $(grep '\[smoke\]' $OUT/smoke.log | tail -1)" >> $S
   ;;
 bench)
-  ( time timeout 900 python bench.py --steps 20 --warmup 5 ) > $OUT/bench.json 2> $OUT/bench.err
+  ( time timeout 900 python bench.py --full --steps 20 --warmup 5 ) > $OUT/bench.json 2> $OUT/bench.err
   echo "BENCH rc=$? $(grep real $OUT/bench.err) $(head -c 1200 $OUT/bench.json)" >> $S
-  timeout 600 python bench.py --config ped_cyl_auto_T3 --no-cpu-baseline --no-live-pmc --steps 24 > $OUT/bench_ped.json 2> $OUT/bench_ped.err
+  timeout 600 python bench.py --full --config ped_cyl_auto_T3 --no-cpu-baseline --no-live-pmc --steps 24 > $OUT/bench_ped.json 2> $OUT/bench_ped.err
   echo "BENCH_PED rc=$? $(head -c 600 $OUT/bench_ped.json)" >> $S
   timeout 600 python bench.py --train --steps 24 --warmup 8 --frames 4 > $OUT/bench_train.json 2> $OUT/bench_train.err
   echo "BENCH_TRAIN rc=$? $(head -c 600 $OUT/bench_train.json)" >> $S
@@ -34,10 +34,10 @@ bench)
 prof)
   for what in bench infer infer_seed0 infer_seed0_f16x2 train; do
     case $what in
-      bench) CMD="python $ROOT/bench.py --no-cpu-baseline --no-secondary --no-live-pmc";;
-      infer) CMD="python $ROOT/bench.py --steps 16 --warmup 2 --no-cpu-baseline --no-secondary --no-live-pmc --no-pipeline";;
-      infer_seed0) CMD="python $ROOT/bench.py --steps 8 --warmup 2 --frames 1 --no-cpu-baseline --no-secondary --no-live-pmc --no-pipeline --no-roofline";;
-      infer_seed0_f16x2) CMD="python $ROOT/bench.py --edge-arith f16x2 --steps 8 --warmup 2 --frames 1 --no-cpu-baseline --no-secondary --no-live-pmc --no-pipeline --no-roofline";;
+      bench) CMD="python $ROOT/bench.py --full --no-cpu-baseline --no-secondary --no-live-pmc";;
+      infer) CMD="python $ROOT/bench.py --full --steps 16 --warmup 2 --no-cpu-baseline --no-secondary --no-live-pmc --no-pipeline";;
+      infer_seed0) CMD="python $ROOT/bench.py --full --steps 8 --warmup 2 --frames 1 --no-cpu-baseline --no-secondary --no-live-pmc --no-pipeline --no-roofline";;
+      infer_seed0_f16x2) CMD="python $ROOT/bench.py --full --edge-arith f16x2 --steps 8 --warmup 2 --frames 1 --no-cpu-baseline --no-secondary --no-live-pmc --no-pipeline --no-roofline";;
       train) CMD="python $ROOT/bench.py --train --steps 8 --warmup 4 --frames 4";;
     esac
     rm -rf $OUT/prof_$what
