@@ -1301,6 +1301,50 @@ int pgnn_kitti_cam_points_in_image(
     void *workspace, size_t workspace_bytes, float *out_xyz, float *out_attr,
     int32_t attr_dim, int64_t capacity, int32_t *out_count, void *stream);
 
+/* ---- voxel-average down-sampling of a frame (dataset/kitti_dataset.py:16-48
+ * downsample_by_average_voxel; the `downsample_by_voxel_size` key of every
+ * config, passed to the frame fetch at run.py:210-211, train.py:80, eval.py:70).
+ * xyz [n,3] float32 and attr [n,attr_dim] float32 (nullable; attr_dim 0..4) on
+ * the device.  kitti_dataset.py:24-28: idx = ((xyz - amin(xyz)) // voxel_size)
+ * .astype(int32) with NumPy's float32 floor_divide (voxel_size, a double here,
+ * is applied as NumPy applies a Python float to a float32 array: in float32);
+ * :29-30 key = ix + iy*dim_x + iz*dim_y*dim_x in WRAPPING int32, rows come out
+ * in ascending signed key; :31-38 each voxel's rows are summed sequentially in
+ * float32 and divided by the int64 count, so the result is float64:
+ * out_xyz [capacity,3], out_attr [capacity,attr_dim], out_lens [capacity]
+ * (nullable: points per voxel).  The reference's argsort is not stable, so for
+ * voxels of three or more points its summation order is the sort
+ * implementation's; here it is DEFINED: ascending original index.
+ * n_dev (nullable, device int32): the point count when only the device knows
+ * it; n_points is then the capacity everything is sized for and
+ * min(*n_dev, n_points) points are read.  *out_count (device) = number of
+ * voxels (also beyond capacity).  Enqueued on `stream`, no host read.
+ * n_points == 0 is PGNN_E_INVALID (the reference raises on np.amax of an
+ * empty array), as are voxel_size <= 0 or not finite and attr_dim > 4. */
+size_t pgnn_voxel_average_workspace_bytes(int64_t n_points, int32_t attr_dim);
+int pgnn_voxel_average_f32(const float *xyz, const float *attr,
+                           int32_t attr_dim, int64_t n_points,
+                           const int32_t *n_dev, double voxel_size,
+                           void *workspace, size_t workspace_bytes,
+                           double *out_xyz, double *out_attr, int32_t *out_lens,
+                           int64_t capacity, int32_t *out_count, void *stream);
+/* get_cam_points_in_image[_with_rgb] with a voxel size (kitti_dataset.py
+ * :612-628 get_cam_points = :998-1006 velo_points_to_cam, then the
+ * down-sampling above on xyz and the reflectance; :666-716 front mask z > 0.1,
+ * :1036-1052 float64 projection, strict image crop, :985-996 colour lookup --
+ * all on the FLOAT64 voxel rows, the voxel count handed on in device memory).
+ * Arguments as pgnn_kitti_cam_points_in_image; out_xyz [capacity,3] and
+ * out_attr [capacity,attr_dim] are float64 (np.hstack([attr, rgb]) of a
+ * float64 and a float32 array is float64); kept rows are in voxel-key order. */
+size_t pgnn_kitti_cam_points_voxel_in_image_workspace_bytes(int64_t n_points);
+int pgnn_kitti_cam_points_voxel_in_image(
+    const float *velo_points, int64_t n_points, const float *velo_to_cam_3x4,
+    const double *cam_to_image_3x3, double image_width, double image_height,
+    const uint8_t *image_bgr, int64_t image_rows, int64_t image_cols,
+    double voxel_size, void *workspace, size_t workspace_bytes,
+    double *out_xyz, double *out_attr, int32_t attr_dim, int64_t capacity,
+    int32_t *out_count, void *stream);
+
 /* ---- diagnostics (not part of the reference-facing surface) -------------- */
 /* Process-wide knobs for benchmarks and tests; see "Conventions".  Keys:
  *   launch shape   scatter_rows_per_wave, scatter_nt, mlp_blocks_per_cu,

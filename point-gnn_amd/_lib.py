@@ -398,6 +398,15 @@ _SIGNATURES = {
                                                c_f64, c_vp, c_i64, c_i64, c_vp,
                                                c_sz, c_vp, c_vp, c_i32, c_i64,
                                                c_vp, c_vp]),
+    # voxel-average down-sampling
+    "pgnn_voxel_average_workspace_bytes": (c_sz, [c_i64, c_i32]),
+    "pgnn_voxel_average_f32": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_vp, c_f64,
+                                       c_vp, c_sz, c_vp, c_vp, c_vp, c_i64,
+                                       c_vp, c_vp]),
+    "pgnn_kitti_cam_points_voxel_in_image_workspace_bytes": (c_sz, [c_i64]),
+    "pgnn_kitti_cam_points_voxel_in_image": (
+        c_i32, [c_vp, c_i64, c_vp, c_vp, c_f64, c_f64, c_vp, c_i64, c_i64,
+                c_f64, c_vp, c_sz, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp]),
     # streaming metrics
     "pgnn_metrics_state_bytes": (c_sz, [c_i32, c_i32]),
     "pgnn_metrics_update": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32,

@@ -6,7 +6,7 @@
 //
 // HBM-bound streaming: 16 B read per scan point, 16-28 B written per kept
 // point; two passes (count per block, scan, write) keep np.nonzero order.
-#include "pgnn_common.h"
+#include "ingest_common.h"
 #include "sort.h"
 
 namespace pgnn {
@@ -14,43 +14,19 @@ namespace {
 
 constexpr int kBlock = 256;
 
-struct IngestArgs {
-  const float *velo;  // [n,4] x y z reflectance
-  int64_t n;
-  float r[9];         // velo_to_cam[:3,:3] as float32, row-major
-  float t[3];         // velo_to_cam[:3,3] as float32
-  double p[9];        // cam_to_image[:, :3] (float64 holding P2's float32)
-  double width, height;
-  const uint8_t *image;  // optional [H,W,3] BGR (cv2.imread layout)
-  int64_t img_h, img_w;
-};
-
 struct Projected {
   float x, y, z;
   double u, v;
   bool keep;
 };
 
-// kitti_dataset.py:1002-1005: float32 matmul + float32 add.  The products are
-// accumulated in k order with fused multiply-adds, which is what the sgemm
-// micro-kernels NumPy dispatches to do; the parity test states the (<= 1 ulp)
-// bound for BLAS builds that associate differently.
 __device__ __forceinline__ Projected project_point(const IngestArgs &a,
                                                    int64_t i) {
   const float4 q = reinterpret_cast<const float4 *>(a.velo)[i];
   Projected o;
-  o.x = __fmaf_rn(q.z, a.r[2], __fmaf_rn(q.y, a.r[1], q.x * a.r[0])) + a.t[0];
-  o.y = __fmaf_rn(q.z, a.r[5], __fmaf_rn(q.y, a.r[4], q.x * a.r[3])) + a.t[1];
-  o.z = __fmaf_rn(q.z, a.r[8], __fmaf_rn(q.y, a.r[7], q.x * a.r[6])) + a.t[2];
-  // :675 front points, :678-684 projection in float64 and the image test
-  const double X = o.x, Y = o.y, Z = o.z;
-  const double iu = (X * a.p[0] + Y * a.p[1]) + Z * a.p[2];
-  const double iv = (X * a.p[3] + Y * a.p[4]) + Z * a.p[5];
-  const double iw = (X * a.p[6] + Y * a.p[7]) + Z * a.p[8];
-  o.u = iu / iw;
-  o.v = iv / iw;
-  o.keep = o.z > 0.1f && o.u > 0.0 && o.u < a.width && o.v > 0.0 &&
-           o.v < a.height;
+  velo_to_cam_f32(a, q, &o.x, &o.y, &o.z);
+  // :675 front points
+  o.keep = project_in_image(a, o.x, o.y, o.z, &o.u, &o.v) && o.z > 0.1f;
   return o;
 }
 
@@ -92,15 +68,8 @@ __global__ __launch_bounds__(kBlock) void ingest_write_kernel(
     float *at = out_attr + slot * attr_dim;
     at[0] = a.velo[4 * i + 3];
     if (attr_dim == 4) {
-      // :994-995 image[int32(v), int32(u), ::-1] / 255 (BGR -> RGB)
-      const int64_t px = (int64_t)(int)o.u, py = (int64_t)(int)o.v;
-      float r = 0.0f, g = 0.0f, b = 0.0f;
-      if (a.image && px >= 0 && px < a.img_w && py >= 0 && py < a.img_h) {
-        const uint8_t *c = a.image + (py * a.img_w + px) * 3;
-        b = (float)c[0] / 255.0f;
-        g = (float)c[1] / 255.0f;
-        r = (float)c[2] / 255.0f;
-      }
+      float r, g, b;
+      sample_rgb(a, o.u, o.v, &r, &g, &b);
       at[1] = r;
       at[2] = g;
       at[3] = b;
@@ -172,13 +141,7 @@ extern "C" int pgnn_kitti_cam_points_in_image(
   IngestArgs a;
   a.velo = velo_points;
   a.n = n_points;
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) {
-      a.r[3 * r + c] = velo_to_cam_3x4[4 * r + c];
-      a.p[3 * r + c] = cam_to_image_3x3[3 * r + c];
-    }
-    a.t[r] = velo_to_cam_3x4[4 * r + 3];
-  }
+  fill_calib(&a, velo_to_cam_3x4, cam_to_image_3x3);
   a.width = image_width;
   a.height = image_height;
   a.image = attr_dim == 4 ? image_bgr : nullptr;

@@ -9,10 +9,15 @@ per-point transform / projection / crop / ordered compaction is
 `pgnn_kitti_cam_points_in_image`.  Results are `Points(xyz, attr)` with CUDA
 tensors, ready for `graph_gen` and the model.
 
-Not implemented here (raise or absent): labels, augmentation, voxel
-down-sampling (`downsample_by_voxel_size` is null in every shipped config),
-PNG decoding -- only the image SIZE is needed for the crop, read from the PNG
-header; for 'irgb' features pass a decoded BGR array.
+With a voxel size (`downsample_by_voxel_size` of the configs) the frame is
+voxel-averaged between the transform and the crop
+(`downsample_by_average_voxel`, kitti_dataset.py:16-48, `pgnn_voxel_average_f32`
+/ `pgnn_kitti_cam_points_voxel_in_image`) and comes out float64, as the
+reference's does.
+
+Not implemented here (raise or absent): PNG decoding -- only the image SIZE
+is needed for the crop, read from the PNG header; for 'irgb' features pass a
+decoded BGR array.
 """
 import os
 import struct
@@ -102,18 +107,65 @@ class PendingPoints(object):
         m = int(self.count_host[0])
         xyz, attr = self.xyz[:m], self.attr[:m]
         if self.pad_rgb:
-            zeros = torch.zeros((m, 3), dtype=torch.float32, device=attr.device)
+            zeros = torch.zeros((m, 3), dtype=attr.dtype, device=attr.device)
             attr = torch.cat([attr, zeros], dim=1)
         return Points(xyz=xyz, attr=attr)
 
 
+def _cuda_device(t):
+    import torch
+    if isinstance(t, torch.Tensor) and t.is_cuda:
+        return t.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def downsample_by_average_voxel(points, voxel_size):
+    """kitti_dataset.py:16-48: the mean of the points (and attributes) of every
+    occupied voxel, rows in ascending voxel key.  `points`: Points of float32
+    NumPy arrays or CUDA tensors, `attr` [n,a] (a <= 4) or None -> Points of
+    float64 CUDA tensors (float32 sums divided by int64 counts are float64 in
+    the reference).  The points of a voxel are added in ascending index (the
+    reference's unstable argsort leaves that order to NumPy's sort)."""
+    import torch
+    lib = _lib.load()
+    dev = _cuda_device(points.xyz)
+    xyz = torch.as_tensor(points.xyz).to(device=dev, dtype=torch.float32)
+    xyz = xyz.reshape(-1, 3).contiguous()
+    n = int(xyz.shape[0])
+    attr, attr_dim = None, 0
+    if points.attr is not None:
+        attr = torch.as_tensor(points.attr).to(device=dev,
+                                               dtype=torch.float32)
+        attr = attr.reshape(n, -1).contiguous()
+        attr_dim = int(attr.shape[1])
+    out_xyz = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    out_attr = torch.empty((n, attr_dim), dtype=torch.float64, device=dev) \
+        if attr is not None else None
+    count = torch.zeros((1,), dtype=torch.int32, device=dev)
+    ws_bytes = int(lib.pgnn_voxel_average_workspace_bytes(n, attr_dim))
+    ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pgnn_voxel_average_f32(
+            _lib.ptr(xyz), _lib.ptr(attr) if attr is not None else None,
+            attr_dim, n, None, float(voxel_size), _lib.ptr(ws), ws_bytes,
+            _lib.ptr(out_xyz),
+            _lib.ptr(out_attr) if out_attr is not None else None, None, n,
+            _lib.ptr(count), _lib.stream_ptr()), "pgnn_voxel_average_f32")
+        m = int(count.item())
+    return Points(xyz=out_xyz[:m],
+                  attr=out_attr[:m] if out_attr is not None else None)
+
+
 def cam_points_in_image(velo_data, calib, image_shape, image=None,
-                        with_rgb=False, deferred=False):
+                        with_rgb=False, deferred=False,
+                        downsample_voxel_size=None):
     """velo_data [n,4] float32 (x,y,z,reflectance; NumPy or CUDA tensor) ->
     Points(xyz [m,3], attr [m,1] or [m,4]) as CUDA tensors:
     kitti_dataset.py:666-689 (`get_cam_points_in_image`) / :691-716 (`..._with_
     rgb`) after the file reads.  image_shape = (height, width); image = decoded
-    BGR uint8 [H,W,3] (cv2.imread layout) when with_rgb."""
+    BGR uint8 [H,W,3] (cv2.imread layout) when with_rgb.
+    downsample_voxel_size: the cloud is voxel-averaged between the transform
+    and the crop (:612-628) and the result is float64, rows in voxel order."""
     import torch
     lib = _lib.load()
     dev = velo_data.device if isinstance(velo_data, torch.Tensor) and \
@@ -139,20 +191,33 @@ def cam_points_in_image(velo_data, calib, image_shape, image=None,
         img_t = img_t.contiguous()
         if img_t.dim() != 3 or img_t.shape[2] != 3:
             raise ValueError("image must be [H, W, 3] uint8 (BGR)")
-    out_xyz = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    out_attr = torch.empty((n, attr_dim), dtype=torch.float32, device=dev)
+    voxel = downsample_voxel_size is not None
+    out_dtype = torch.float64 if voxel else torch.float32
+    out_xyz = torch.empty((n, 3), dtype=out_dtype, device=dev)
+    out_attr = torch.empty((n, attr_dim), dtype=out_dtype, device=dev)
     count = torch.zeros((1,), dtype=torch.int32, device=dev)
-    ws_bytes = int(lib.pgnn_kitti_ingest_workspace_bytes(n))
+    ws_bytes = int(
+        lib.pgnn_kitti_cam_points_voxel_in_image_workspace_bytes(n) if voxel
+        else lib.pgnn_kitti_ingest_workspace_bytes(n))
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    img_args = (_lib.ptr(img_t) if img_t is not None else None,
+                int(img_t.shape[0]) if img_t is not None else 0,
+                int(img_t.shape[1]) if img_t is not None else 0)
     with torch.cuda.device(dev):
-        _lib.check(lib.pgnn_kitti_cam_points_in_image(
-            _lib.ptr(v), n, rt.ctypes.data, p.ctypes.data, float(width),
-            float(height), _lib.ptr(img_t) if img_t is not None else None,
-            int(img_t.shape[0]) if img_t is not None else 0,
-            int(img_t.shape[1]) if img_t is not None else 0,
-            _lib.ptr(ws), ws_bytes, _lib.ptr(out_xyz), _lib.ptr(out_attr),
-            attr_dim, n, _lib.ptr(count), _lib.stream_ptr()),
-            "pgnn_kitti_cam_points_in_image")
+        if voxel:
+            _lib.check(lib.pgnn_kitti_cam_points_voxel_in_image(
+                _lib.ptr(v), n, rt.ctypes.data, p.ctypes.data, float(width),
+                float(height), *img_args, float(downsample_voxel_size),
+                _lib.ptr(ws), ws_bytes, _lib.ptr(out_xyz), _lib.ptr(out_attr),
+                attr_dim, n, _lib.ptr(count), _lib.stream_ptr()),
+                "pgnn_kitti_cam_points_voxel_in_image")
+        else:
+            _lib.check(lib.pgnn_kitti_cam_points_in_image(
+                _lib.ptr(v), n, rt.ctypes.data, p.ctypes.data, float(width),
+                float(height), *img_args,
+                _lib.ptr(ws), ws_bytes, _lib.ptr(out_xyz), _lib.ptr(out_attr),
+                attr_dim, n, _lib.ptr(count), _lib.stream_ptr()),
+                "pgnn_kitti_cam_points_in_image")
         if deferred:
             count_host = torch.empty(1, dtype=torch.int32, pin_memory=True)
             count_host.copy_(count, non_blocking=True)
@@ -216,16 +281,36 @@ class KittiDataset(object):
         return png_size(os.path.join(
             self._image_dir, self._file_list[frame_idx]) + '.png')
 
+    def get_cam_points(self, frame_idx, downsample_voxel_size=None,
+                       calib=None, xyz_range=None):
+        """kitti_dataset.py:612-628: the whole scan in camera coordinates (no
+        crop), voxel-averaged when a size is given.  The float32 transform is
+        the reference's expression on the host (:998-1006); Points of CUDA
+        tensors, float32 without a voxel size and float64 with one."""
+        import torch
+        if calib is None:
+            calib = self.get_calib(frame_idx)
+        pts = self.get_velo_points(frame_idx, xyz_range=xyz_range)
+        m = np.transpose(calib['velo_to_cam'])
+        cam_xyz = np.matmul(pts.xyz, m[:3, :3].astype(np.float32))
+        cam_xyz += m[[3], :3].astype(np.float32)
+        dev = _cuda_device(None)
+        cam = Points(xyz=torch.from_numpy(cam_xyz).to(dev),
+                     attr=torch.from_numpy(np.ascontiguousarray(pts.attr)
+                                           ).to(dev))
+        if downsample_voxel_size is not None:
+            cam = downsample_by_average_voxel(cam, downsample_voxel_size)
+        return cam
+
     def get_cam_points_in_image(self, frame_idx, downsample_voxel_size=None,
                                 calib=None, xyz_range=None):
-        if downsample_voxel_size is not None:
-            raise NotImplementedError(
-                "downsample_by_voxel_size is null in every shipped config")
         if calib is None:
             calib = self.get_calib(frame_idx)
         pts = self.get_velo_points(frame_idx, xyz_range=xyz_range)
         velo = np.concatenate([pts.xyz, pts.attr], axis=1)
-        return cam_points_in_image(velo, calib, self._image_shape(frame_idx))
+        return cam_points_in_image(
+            velo, calib, self._image_shape(frame_idx),
+            downsample_voxel_size=downsample_voxel_size)
 
     def get_cam_points_in_image_with_rgb(self, frame_idx,
                                          downsample_voxel_size=None,
@@ -236,9 +321,6 @@ class KittiDataset(object):
         package) the colour channels are zero -- enough for the 'i' / 'i000' /
         '0' input features of the shipped configs (run.py:226-241).
         deferred (extension): enqueue only and return a PendingPoints."""
-        if downsample_voxel_size is not None:
-            raise NotImplementedError(
-                "downsample_by_voxel_size is null in every shipped config")
         if calib is None:
             calib = self.get_calib(frame_idx)
         if xyz_range is None:
@@ -253,15 +335,18 @@ class KittiDataset(object):
             else self._image_shape(frame_idx)
         if image is None:
             import torch
-            p = cam_points_in_image(velo, calib, shape, deferred=deferred)
+            p = cam_points_in_image(
+                velo, calib, shape, deferred=deferred,
+                downsample_voxel_size=downsample_voxel_size)
             if deferred:
                 p.pad_rgb = True
                 return p
-            zeros = torch.zeros((p.attr.shape[0], 3), dtype=torch.float32,
+            zeros = torch.zeros((p.attr.shape[0], 3), dtype=p.attr.dtype,
                                 device=p.attr.device)
             return Points(xyz=p.xyz, attr=torch.cat([p.attr, zeros], dim=1))
-        return cam_points_in_image(velo, calib, shape, image=image,
-                                   with_rgb=True, deferred=deferred)
+        return cam_points_in_image(
+            velo, calib, shape, image=image, with_rgb=True, deferred=deferred,
+            downsample_voxel_size=downsample_voxel_size)
 
     # ---- labels and training targets (kitti_dataset.py:703-751, 1132-1284)
     def get_label(self, frame_idx, no_orientation=False):

@@ -15,7 +15,7 @@ from functools import partial
 import numpy as np
 import torch
 
-from . import gnn
+from . import _lib, gnn
 from .weights import init_params
 
 __all__ = ["MultiLayerFastLocalGraphModelV2", "get_model", "cls_loss_kind",
@@ -214,6 +214,17 @@ class MultiLayerFastLocalGraphModelV2(object):
                 None if k is None else up(k, np.int32)
                 for k in t_keypoint_indices_list]
             t_edges_list = [up(e, np.int32) for e in t_edges_list]
+        else:
+            # float64 inputs (the cloud of a voxel-averaged frame, a graph
+            # built on it) are narrowed the way the reference's feed_dict
+            # narrows them into its float32 placeholders (run.py:248-260);
+            # a capacity-form tensor keeps its count
+            def narrow(t):
+                if t.dtype == torch.float32:
+                    return t
+                return _lib.tag_count(t.to(torch.float32), _lib.count_of(t))
+            t_initial_vertex_features = narrow(t_initial_vertex_features)
+            t_vertex_coord_list = [narrow(c) for c in t_vertex_coord_list]
         # set `model.keep_features = True` to keep every layer's output
         # (models.py:113-147's `tfeatures` after each layer) in
         # `model.feature_list` -- per-layer parity checks

@@ -103,7 +103,10 @@ def detect_frame(dataset, frame_idx, model, config, use_box_merge=True,
         box_encoding_method=config['box_encoding_method'],
         use_box_merge=use_box_merge, use_box_score=use_box_score)
     cand_idx, _ = nms.select_candidates(probs)
-    cand_xyz = coords[-1][(cand_idx // config['num_classes']).long()]
+    # (float32 like the decode above: a no-op unless the frame was
+    # voxel-averaged, whose float64 vertices both loops narrow alike)
+    cand_xyz = coords[-1].to(torch.float32)[
+        (cand_idx // config['num_classes']).long()]
     t = lap('decode box + nms', t)
     rows = kitti_output.detections_to_kitti_labels(
         labels, boxes, scores, calib, config['label_method'],
