@@ -1454,14 +1454,17 @@ int segfc_bwd_impl(const float *Y, int64_t ld_y, const int32_t *seg_ids,
   PGNN_REQUIRE(n_rows >= 0 && n_cols > 0 && n_cols <= 512 && num_segments >= 0 &&
                    k_in > 0 && k_in <= 512,
                PGNN_E_INVALID, "segmax_fc_bwd: bad sizes");
-  bool pair_pending = false;  // dP / dQ zeroed together with the counts below
+  // dP | dQ back to back (the trainer's layout) and a whole number of 16-byte
+  // words from a 16-byte boundary, like the counts in the workspace: zeroed
+  // together with the counts below, in one launch of 16-byte stores
+  bool pair_pending = false;
   if (edges && num_segments > 0) {
     PGNN_REQUIRE(dP && dQ && ld_pq >= k_in, PGNN_E_INVALID,
                  "edge_segmax_fc_bwd: bad dP / dQ");
-    if (n_rows == 0 || dQ != dP + (size_t)num_segments * ld_pq)
-      PGNN_HIP(zero_pair(dP, dQ, (size_t)num_segments * ld_pq, stream));
-    else
-      pair_pending = true;
+    const size_t n_pq = (size_t)num_segments * ld_pq;
+    pair_pending = n_rows > 0 && dQ == dP + n_pq && n_pq % 2 == 0 &&
+                   (uintptr_t)dP % 16 == 0 && (uintptr_t)workspace % 16 == 0;
+    if (!pair_pending) PGNN_HIP(zero_pair(dP, dQ, n_pq, stream));
   }
   if (n_rows == 0 || num_segments == 0) return 0;
   PGNN_REQUIRE(Y && seg_ids && out && grad_out && WT && dW &&
@@ -1490,9 +1493,6 @@ int segfc_bwd_impl(const float *Y, int64_t ld_y, const int32_t *seg_ids,
     // and the step is a chain of them
     const int64_t w0 = ((int64_t)num_segments * w.ldc * 4 + 16) / 16;
     const int64_t w1 = (int64_t)num_segments * ld_pq * 2 * 4 / 16;
-    PGNN_REQUIRE(((uintptr_t)w.cnt % 16 == 0) && ((uintptr_t)dP % 16 == 0) &&
-                     ((int64_t)num_segments * ld_pq * 8 % 16 == 0),
-                 PGNN_E_INVALID, "edge_segmax_fc_bwd: dP must be 16-byte aligned");
     hipLaunchKernelGGL(zero2_kernel, dim3(grid_for(w0 + w1, 2048)), dim3(256), 0,
                        stream, (uint4 *)w.cnt, w0, (uint4 *)dP, w1);
   } else {

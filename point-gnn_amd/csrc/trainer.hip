@@ -101,12 +101,14 @@ __global__ void dpred_slice_kernel(const float *__restrict__ dpred, int64_t rows
 // The vertex side of a GNN stage's edge input in one pass (gnn.py:337-352):
 // hx = [h[:, :c] | x | 0 ...] and, with x' = x + delta, x' itself and
 // Q = x' Wx -- pgnn_offset_apply's expression, so Q has the same bits.
+// xyz_copy: x once more, [rows, 3] (stacked on top of x' for the backward).
 __global__ void pre_edge_prep_kernel(const float *__restrict__ h, int64_t ldh,
                                      int c, const float *__restrict__ xyz,
                                      const float *__restrict__ delta,
                                      int64_t ld_delta, int64_t rows,
                                      const float *__restrict__ wx,
                                      float *__restrict__ hx, int ldhx,
+                                     float *__restrict__ xyz_copy,
                                      float *__restrict__ xyz_out,
                                      float *__restrict__ Q, int ld_q,
                                      float *__restrict__ fill,
@@ -136,7 +138,10 @@ __global__ void pre_edge_prep_kernel(const float *__restrict__ h, int64_t ldh,
         x1 = x1 + delta[r * ld_delta + 1];
         x2 = x2 + delta[r * ld_delta + 2];
       }
-      if (k < 3) xyz_out[3 * r + k] = k == 0 ? x0 : (k == 1 ? x1 : x2);
+      if (k < 3) {
+        xyz_out[3 * r + k] = k == 0 ? x0 : (k == 1 ? x1 : x2);
+        xyz_copy[3 * r + k] = k == 0 ? p0 : (k == 1 ? p1 : p2);
+      }
       Q[r * ld_q + k] = (x0 * wx[k] + x1 * wx[ld_q + k]) + x2 * wx[2 * ld_q + k];
     }
   }
@@ -377,7 +382,7 @@ struct PoolSaved {
 struct GnnSaved {
   const float *h_in;           // [K, ld_h]
   float *off_act[PGNN_TRAIN_MAX_FC];  // outputs of the offset MLP layers
-  float *xo, *q, *hx, *p;
+  float *xx, *xo, *q, *hx, *p;  // xx = [x; x'] [2K, 3], xo = x' its 2nd half
   float *eact[PGNN_TRAIN_MAX_FC];  // eact[0] = H1, eact[i] = output of a[i]
   int32_t *dst;
   float *agg;
@@ -719,8 +724,8 @@ size_t scratch_need(const Trainer &t, const pgnn_train_batch &b) {
                                                           (int32_t)K, last.ref.k_in);
       if (n > need) need = n;
     }
-    if (s.kind == 1) {  // the Wx rows: k_in = 3
-      const size_t n = pgnn_weight_grad_workspace_bytes(3, s.a[0].ref.n_out, K);
+    if (s.kind == 1) {  // the coordinate rows: k_in = 3, rows [x; x']
+      const size_t n = pgnn_weight_grad_workspace_bytes(3, s.a[0].ref.n_out, 2 * K);
       if (n > need) need = n;
     } else {  // the fused backward of the narrow pooling layers
       const size_t n = pgnn_pool_narrow_bwd_workspace_bytes(E);
@@ -851,7 +856,8 @@ int forward_impl(Ctx &c, Saved &sv) {
       const int wq = pad16(w1.ref.n_out);
       g.h_in = h;
       for (size_t i = 0; i < s.c.size(); ++i) g.off_act[i] = c.ws.f(K, pad16(s.c[i].ref.n_out));
-      g.xo = c.ws.f(K, 3);
+      g.xx = c.ws.f(2 * K, 3);
+      g.xo = g.xx + 3 * K;
       g.q = c.ws.f(K, wq);
       g.hx = c.ws.f(K, pad16(cc + 3));
       g.p = c.ws.f(K, wq);
@@ -889,7 +895,7 @@ int forward_impl(Ctx &c, Saved &sv) {
                              dim3(blocks_for(K * (ldhx > wq ? ldhx : wq), 8192)),
                              dim3(256), 0, c.stream, h, (int64_t)ld_h, cc,
                              b.coords[lvl], delta, ld_delta, K, s.wx, g.hx, ldhx,
-                             g.xo, g.q, wq, g.agg, (int64_t)K * wa);
+                             g.xx, g.xo, g.q, wq, g.agg, (int64_t)K * wa);
         }
         rc = fc_fwd(c, w1, g.hx, pad16(cc + 3), K, false, nullptr, 0, g.p);
         if (rc) return rc;
@@ -1286,14 +1292,38 @@ int backward_impl(Ctx &c, Saved &sv, const float *dlogits, const float *dpred) {
                                     c.stream);
           if (rc) return rc;
         }
-        // P = [h, x] W1 + b1
-        rc = fc_bwd(c, sv, w1, g.hx, pad16(cc + 3), nullptr, dp, Ks, false, dhx,
-                    true, true);
-        if (rc) return rc;
-        // Q = x' Wx, Wx = rows cc..cc+2 of W1 (the minus sign is in dq)
-        // (it adds into rows of the same dW as the deferred job of w1 above,
-        // and jobs of one batch must not share outputs: the second batch)
-        {
+        // P = [h, x] W1 + b1 and Q = x' Wx, Wx = rows cc..cc+2 of W1 (the
+        // minus sign is in dq).  Those three rows of dW are
+        //   sum_v x_v dP_v + sum_v x'_v dQ_v = sum_e (x_src - x'_dst) dH1_e:
+        // two sums of coordinate-sized terms (tens of metres) that cancel
+        // down to offset-sized ones.  They are ONE job over the stacked rows
+        // [x; x'] (g.xx) and [dP; dQ] (back to back) in the second batch,
+        // whose few narrow jobs get short row slices: as a part of w1's job
+        // in the first batch (long slices) their float32 rounding reached
+        // 1e-5 of the gradient's scale at the benchmarked batch size.
+        if (w1.ref.n_out <= 320) {  // (fc_wgrad defers exactly these)
+          defer_wgrad(c, g.hx, pad16(cc + 3), cc, dp, wq, w1.ref.n_out, Ks,
+                      w1.gw, w1.gb, true);
+          rc = fc_dx(c, w1, dp, wq, Ks, dhx);
+          if (rc) return rc;
+          pgnn_wgrad_job j = {};
+          j.X = g.xx;
+          j.ld_x = 3;
+          j.dZ = dp;
+          j.ld_dz = wq;
+          j.n_rows = 2 * Ks;
+          j.dW = w1.gw + (int64_t)cc * w1.ref.n_out;
+          j.db = nullptr;
+          j.k_in = 3;
+          j.n_out = w1.ref.n_out;
+          j.accumulate = 1;
+          c.wjobs2.push_back(j);
+        } else {
+          rc = fc_bwd(c, sv, w1, g.hx, pad16(cc + 3), nullptr, dp, Ks, false,
+                      dhx, true, true);
+          if (rc) return rc;
+          // (it adds into rows of the same dW as w1's job above, and jobs of
+          // one batch must not share outputs: the second batch)
           pgnn_wgrad_job j = {};
           j.X = g.xo;
           j.ld_x = 3;

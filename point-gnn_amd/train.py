@@ -41,6 +41,31 @@ def learning_rate(train_config, step):
     return train_config['initial_lr'] * train_config['decay_factor'] ** p
 
 
+def adam_step_from_checkpoint(ck, opt_kwargs, global_step):
+    """Adam's step count (optimizer steps taken with its slots) recovered from
+    a checkpoint dict: TF keeps beta1_power = beta1^(t+1) and beta2_power =
+    beta2^(t+1) as float32 variables (Trainer.optimizer_state_dict writes them
+    so).  beta1_power alone stops being exact once it leaves the normal float32
+    range (0.9^(t+1) is subnormal from t = 959 and zero from t ~ 985), so:
+      beta1_power while it is a normal float32 above 1e-30, else
+      beta2_power while it is a normal float32 (0.999^(t+1): up to ~87k steps),
+      else, when the checkpoint holds Adam's slots, `global_step`;
+    0 when it holds no Adam slots (another optimizer's checkpoint: fresh slots,
+    fresh bias-correction clock)."""
+    tiny = float(np.finfo(np.float32).tiny)
+    for key, beta, floor in (('beta1_power', 'beta1', 1e-30),
+                             ('beta2_power', 'beta2', tiny)):
+        if key not in ck:
+            continue
+        p = float(np.asarray(ck[key], np.float32).reshape(-1)[0])
+        b = float(opt_kwargs[beta])
+        if p >= max(floor, tiny) and p < 1.0 and 0.0 < b < 1.0:
+            return max(0, int(round(np.log(p) / np.log(b))) - 1)
+    if any(k.endswith('/Adam') or k.endswith('/Adam_1') for k in ck):
+        return int(global_step)
+    return 0
+
+
 def batch_data(batch_list):
     """train.py:135-171: merge frames into one disjoint graph by offsetting
     point / centre indices.  Accepts NumPy arrays or torch tensors (same kind
@@ -821,13 +846,10 @@ class Trainer(object):
         if 'Variable' in ck:
             self.global_step = int(ck['Variable'])
         self.opt_step = 0
-        if self.optimizer == 'adam' and 'beta1_power' in ck:
-            # beta1_power = beta1 ^ (steps taken + 1)
-            b1 = float(self.opt_kwargs['beta1'])
-            p = float(np.asarray(ck['beta1_power']).reshape(-1)[0])
-            if 0.0 < p < 1.0 and 0.0 < b1 < 1.0:
-                self.opt_step = max(0, int(round(np.log(p) / np.log(b1))) - 1)
-        elif self.optimizer != 'adam' and any(
+        if self.optimizer == 'adam':
+            self.opt_step = adam_step_from_checkpoint(ck, self.opt_kwargs,
+                                                      self.global_step)
+        elif any(
                 (name + '/' + slot) in ck for name, _ in self.specs[:1]
                 for slot in _OPTIMIZERS[self.optimizer][2]):
             self.opt_step = self.global_step

@@ -8,6 +8,7 @@ import pytest
 import pointgnn_amd  # noqa: F401
 from pointgnn_amd import configs, weights
 from oracle import train_oracle as to
+from _train_decisions import device_decisions as _device_decisions
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -541,46 +542,6 @@ def test_full_gradient_matches_oracle(dev, name):
         worst_max, worst_fro))
 
 
-def _device_decisions(tr, cfg):
-    """The non-smooth choices the DEVICE's forward took (ReLU masks, segment-
-    max winners), read from the activations the Python-driven step keeps for
-    its backward (`Trainer._saved`), in oracle/train_oracle.Decisions order."""
-    out = []
-    fc = tr.fc
-
-    def relu_masks(names, acts, skip_last):
-        n = len(names) - (1 if skip_last else 0)
-        for i in range(n):
-            w = fc[names[i]].n_out
-            out.append((acts[i + 1][:, :w] > 0).cpu().numpy())
-
-    def winners(rows, dst, agg, width):
-        idx = dst.long()
-        out.append((rows[:, :width] == agg[idx][:, :width]).cpu().numpy())
-
-    for item in tr._saved:
-        if item[0] == 'pool':
-            _, names, acts, dst, agg, onames, oacts = item[:7]
-            relu_masks(names, acts, False)
-            winners(acts[-1], dst, agg, fc[names[-1]].n_out)
-            relu_masks(onames, oacts, False)
-        elif item[0] == 'gnn':
-            (_, enames, hx, xo, e, eacts, dst, agg, unames, uacts, off_names,
-             off_acts, c) = item
-            if off_names is not None:
-                relu_masks(off_names, off_acts, True)
-            for i, n in enumerate(enames):      # eacts[0] = ReLU(P - Q)
-                out.append((eacts[i][:, :fc[n].n_out] > 0).cpu().numpy())
-            winners(eacts[-1], dst, agg, fc[enames[-1]].n_out)
-            relu_masks(unames, uacts, True)
-        else:
-            _, cls_names, cacts, loc = item
-            relu_masks(cls_names, cacts, True)
-            for names, a in loc:
-                relu_masks(names, a, True)
-    return out
-
-
 @pytest.mark.parametrize("name", ["car_auto_T1", "car_auto_T3", "car_fixed_T3",
                                   "ped_cyl_auto_T3"])
 def test_full_gradient_matches_mask_matched_oracle(dev, name):
@@ -750,6 +711,44 @@ def test_other_optimizers_follow_tf_update_rules(dev, opt, kwargs, tmp_path):
         train.Trainer(cfg, train_config=dict(
             tcfg, optimizer='momentum',
             optimizer_kwargs={'use_nesterov': True}), device=dev)
+
+
+def test_adam_resume_after_a_long_run_keeps_its_clock(dev, tmp_path):
+    """A checkpoint written at opt_step = global_step = 2000 -- where the
+    float32 beta1_power = 0.9^2001 has underflowed to zero -- resumes with
+    Adam's step count 2000 (from beta2_power), and the next step of the
+    resumed trainer equals the next step of the original (a clock restarted
+    at t = 1 would scale the update by sqrt(1 - 0.999) / (1 - 0.9) ~ 0.32).
+    Both steps apply the SAME gradient: two runs of the backward differ in
+    the last bits (float atomics), and at t = 2001 Adam's normalised update
+    (~4 lr per entry after one step of slots) carries that noise above the
+    resume test's tolerance."""
+    import torch
+    from pointgnn_amd import train
+    cfg = configs.car_auto_config(1)
+    params = weights.init_params(cfg, seed=6, bias_scale=0.05)
+    batch = _tiny_batch(seed=4)
+    tcfg = {'initial_lr': 0.01, 'decay_step': 1000000, 'decay_factor': 0.5,
+            'optimizer': 'adam', 'optimizer_kwargs': {}, 'unify_copies': True}
+    tr = train.Trainer(cfg, train_config=tcfg, params=params, device=dev)
+    tr.train_step(batch)                       # non-zero slots
+    tr.opt_step = tr.global_step = 2000
+    tr.save_checkpoint(str(tmp_path))
+    b = train.Trainer(cfg, train_config=tcfg, seed=99, device=dev)
+    b.load_checkpoint(str(tmp_path))
+    assert b.global_step == 2000 and b.opt_step == 2000
+    assert torch.equal(tr.flat, b.flat)
+    for sa, sb in zip(tr.slots, b.slots):
+        assert torch.equal(sa, sb)
+    tr.train_step(batch, apply=False)
+    g = tr.grad.clone()
+    lr = train.learning_rate(tcfg, 2000)
+    w0 = tr.flat.clone()
+    for t in (tr, b):
+        t.grad.copy_(g)
+        t._apply_gradients(lr)          # what train_step(apply=True) runs
+    assert not torch.equal(tr.flat, w0)
+    assert torch.allclose(tr.flat, b.flat, rtol=1e-5, atol=1e-7)
 
 
 def test_pseudo_batch_accumulates_like_the_reference(dev):
@@ -954,11 +953,214 @@ def test_segmax_fc_bwd_matches_dense_adjoint(dev, rows, k_in, n_cols, nseg,
     np.testing.assert_allclose(db.cpu().numpy(), ref_db, atol=5e-5, rtol=2e-4)
 
 
+K_TIE_CAP = 65536       # csrc/train.hip kTieCap: entries of the tie list
+
+
+def _edge_segmax_case(seed, nseg, n_cols=256, k_in=256, per_seg=3,
+                      extra_tie=False, spare=16, ld_pq=None):
+    """Inputs of the edge stage's last layer + segment max with a KNOWN number
+    of positive ties.  H1 = ReLU(P[src] - Q[dst]) >= 0 and W > 0, so with the
+    bias at -0.1 every Y = ReLU(H1 W + b) is positive; each of the `nseg`
+    segments holds `per_seg` distinct edges, every one of them twice (the same
+    (src, dst) pair: identical H1 and Y rows), which gives exactly one further
+    row tied with each (segment, column) maximum: nseg * n_cols ties.
+    `extra_tie`: one more segment of two identical ZERO H1 rows (P of its
+    source is 0, Q of its vertex 1), whose Y = ReLU(b) is positive in the
+    single column with a positive bias -- one tie more.  Returns a dict of
+    float32 arrays plus the float64 reference of the adjoint."""
+    rng = np.random.default_rng(seed)
+    from pointgnn_amd.gnn import padded_width
+    kp, cp = padded_width(k_in), padded_width(n_cols)
+    ld_pq = ld_pq or kp
+    n_seg = nseg + (1 if extra_tie else 0)
+    nv = n_seg + spare                 # vertices (= segments of the edge form)
+    vstar = nv - 1                     # the extra segment's source
+    p = np.zeros((nv, ld_pq), np.float32)
+    q = np.zeros((nv, ld_pq), np.float32)
+    p[:, :k_in] = rng.uniform(0.0, 1.2, (nv, k_in))
+    q[:, :k_in] = rng.uniform(-0.3, 0.3, (nv, k_in))
+    edges = []
+    for s in range(nseg):
+        src = rng.choice(nv - 1, per_seg, replace=False)
+        src = rng.permutation(np.concatenate([src, src]))
+        edges += [(int(a), s) for a in src]
+    if extra_tie:
+        p[vstar] = 0.0
+        q[nseg, :k_in] = 1.0
+        edges += [(vstar, nseg), (vstar, nseg)]
+    edges = np.asarray(edges, np.int32)
+    src, dst = edges[:, 0].astype(np.int64), edges[:, 1].astype(np.int64)
+    h1 = np.zeros((len(edges), kp), np.float32)
+    h1[:, :k_in] = np.maximum(p[src, :k_in] - q[dst, :k_in], 0)
+    w = (rng.uniform(0.5, 1.5, (k_in, n_cols)) / k_in).astype(np.float32)
+    b = np.full(n_cols, -0.1, np.float32)
+    b[7] = 0.3
+    y = np.zeros((len(edges), cp), np.float32)
+    y[:, :n_cols] = np.maximum(h1[:, :k_in] @ w + b, 0)
+    out = np.zeros((nv, cp), np.float32)            # exact segment maxima
+    np.maximum.at(out, dst, y)
+    gout = np.zeros((nv, cp), np.float32)
+    gout[:, :n_cols] = rng.standard_normal((nv, n_cols))
+    wt = np.zeros((n_cols, kp), np.float32)
+    wt[:, :k_in] = w.T
+    # float64 reference: TF's equal split among tied positive maxima
+    y64 = y[:, :n_cols].astype(np.float64)
+    sel = (y64 == out[dst, :n_cols]) & (y64 > 0)
+    cnt = np.zeros((nv, n_cols))
+    np.add.at(cnt, dst, sel)
+    dz = np.where(sel, gout[dst, :n_cols] / np.maximum(cnt[dst], 1), 0.0)
+    x64 = h1[:, :k_in].astype(np.float64)
+    dh1 = (dz @ w.astype(np.float64).T) * (x64 > 0)
+    ref_dp = np.zeros((nv, k_in))
+    ref_dq = np.zeros((nv, k_in))
+    np.add.at(ref_dp, src, dh1)
+    np.add.at(ref_dq, dst, -dh1)
+    return dict(k_in=k_in, n_cols=n_cols, kp=kp, cp=cp, ld_pq=ld_pq, nv=nv,
+                p=p, q=q, edges=edges, h1=h1, y=y, out=out, gout=gout, wt=wt,
+                ties=int(np.maximum(cnt - 1, 0).sum()), ref_dx=dh1,
+                ref_dp=ref_dp, ref_dq=ref_dq, ref_dw=x64.T @ dz,
+                ref_db=dz.sum(0))
+
+
+def _run_edge_segmax(dev, c, form, with_db=True, pq_offset=0, contiguous=True):
+    """One call of pgnn_edge_segmax_fc_bwd_f32 (form 'h1': H1 rows given,
+    'pq': recomputed from P and Q) or pgnn_segmax_fc_bwd_f32 (form 'x': H1 as
+    the materialised X, dX written) on case `c`, dW / db accumulating into
+    prefilled buffers, dP / dQ (or dX) prefilled with garbage.  dP | dQ sit
+    back to back in one buffer (`contiguous`, the trainer's layout) starting
+    `pq_offset` floats into it, or in two buffers.  Returns the outputs and
+    whether the guard floats around dP | dQ kept their value."""
+    import torch
+    from pointgnn_amd import _lib
+    lib = _lib.load()
+    k_in, n_cols, kp, cp = c['k_in'], c['n_cols'], c['kp'], c['cp']
+    nv, ld_pq, n_e = c['nv'], c['ld_pq'], len(c['edges'])
+    yd, od, gd, wtd, hd = (T(c[k], dev) for k in ('y', 'out', 'gout', 'wt', 'h1'))
+    ed = T(c['edges'], dev)
+    dd = ed[:, 1].contiguous()
+    pd, qd = T(c['p'], dev), T(c['q'], dev)
+    dw = torch.full((k_in, n_cols), 0.25, dtype=torch.float32, device=dev)
+    db = torch.full((n_cols,), -0.5, dtype=torch.float32, device=dev) \
+        if with_db else None
+    ws = torch.empty(lib.pgnn_segmax_fc_bwd_workspace_bytes(n_e, n_cols, nv,
+                                                            k_in),
+                     dtype=torch.uint8, device=dev)
+    res = {}
+    n_pq = nv * ld_pq
+    guard_ok = True
+    if form == "x":
+        dx = torch.full((n_e, kp), 7.0, dtype=torch.float32, device=dev)
+        rc = lib.pgnn_segmax_fc_bwd_f32(
+            _lib.ptr(yd), cp, _lib.ptr(dd), n_e, n_cols, nv, _lib.ptr(od), cp,
+            _lib.ptr(gd), cp, _lib.ptr(hd), kp, k_in, _lib.ptr(wtd), kp,
+            _lib.ptr(dx), kp, kp, 1, _lib.ptr(dw),
+            _lib.ptr(db) if with_db else None, _lib.ptr(ws), ws.numel(),
+            _lib.stream_ptr())
+        torch.cuda.synchronize()
+        res['dx'] = dx.cpu().numpy()
+    else:
+        if contiguous:
+            buf = torch.full((pq_offset + 2 * n_pq + 8,), 7.0,
+                             dtype=torch.float32, device=dev)
+            dp = buf[pq_offset:pq_offset + n_pq]
+            dq = buf[pq_offset + n_pq:pq_offset + 2 * n_pq]
+        else:
+            dp = torch.full((n_pq,), 7.0, dtype=torch.float32, device=dev)
+            dq = torch.full((n_pq,), 7.0, dtype=torch.float32, device=dev)
+        rc = lib.pgnn_edge_segmax_fc_bwd_f32(
+            _lib.ptr(yd), cp, _lib.ptr(ed), _lib.ptr(dd), n_e, n_cols, nv,
+            _lib.ptr(od), cp, _lib.ptr(gd), cp,
+            _lib.ptr(hd) if form == "h1" else None, kp, _lib.ptr(pd),
+            _lib.ptr(qd), k_in, _lib.ptr(wtd), kp, dp.data_ptr(),
+            dq.data_ptr(), ld_pq, _lib.ptr(dw),
+            _lib.ptr(db) if with_db else None, _lib.ptr(ws), ws.numel(),
+            _lib.stream_ptr())
+        torch.cuda.synchronize()
+        res['dp'] = dp.cpu().numpy().reshape(nv, ld_pq)
+        res['dq'] = dq.cpu().numpy().reshape(nv, ld_pq)
+        if contiguous:
+            g = buf.cpu().numpy()
+            guard_ok = bool((g[:pq_offset] == 7.0).all() and
+                            (g[pq_offset + 2 * n_pq:] == 7.0).all())
+    res['dw'] = dw.cpu().numpy()
+    res['db'] = db.cpu().numpy() if with_db else None
+    return rc, res, guard_ok
+
+
+def _check_edge_segmax(c, form, res, with_db=True):
+    """The bars of test_segmax_fc_bwd_matches_dense_adjoint: dX / dP / dQ to
+    atol 2e-5, rtol 1e-4; dW / db to atol 5e-5, rtol 2e-4."""
+    k_in = c['k_in']
+    if form == "x":
+        np.testing.assert_allclose(res['dx'][:, :k_in], c['ref_dx'], atol=2e-5,
+                                   rtol=1e-4, err_msg="dX")
+        assert np.all(res['dx'][:, k_in:] == 0)
+    else:
+        for key in ('dp', 'dq'):
+            np.testing.assert_allclose(res[key][:, :k_in], c['ref_' + key],
+                                       atol=2e-5, rtol=1e-4, err_msg=key)
+            assert np.all(res[key][:, k_in:] == 0), key + " padding not zeroed"
+    np.testing.assert_allclose(res['dw'], c['ref_dw'] + 0.25, atol=5e-5,
+                               rtol=2e-4, err_msg="dW")
+    if with_db:
+        np.testing.assert_allclose(res['db'], c['ref_db'] - 0.5, atol=5e-5,
+                                   rtol=2e-4, err_msg="db")
+
+
+@pytest.mark.parametrize("form", ["h1", "pq", "x"])
+@pytest.mark.parametrize("ties,with_db", [
+    ("cap", True), ("cap+1", True), ("cap+1", False), ("4cap", False)])
+def test_segmax_fc_bwd_at_the_tie_list_capacity(dev, form, ties, with_db):
+    """The further rows of tied positive maxima reach the weight gradient
+    through a list of kTieCap = 65536 (row, column) entries; past it
+    segmax_wgrad_ties_kernel scans every row instead.  Exactly kTieCap ties
+    (the list, full), kTieCap + 1 (the scan) and 4 kTieCap, against the
+    float64 adjoint: pgnn_edge_segmax_fc_bwd_f32 with the H1 rows given
+    ('h1') and recomputed from P and Q ('pq'), pgnn_segmax_fc_bwd_f32 on the
+    materialised rows ('x'); dW / db accumulate into prefilled buffers, db
+    may be NULL, garbage in dP / dQ / dX is overwritten."""
+    nseg = {"cap": 256, "cap+1": 256, "4cap": 1024}[ties]
+    c = _edge_segmax_case(nseg, nseg, extra_tie=(ties == "cap+1"))
+    if ties == "4cap":
+        assert c['ties'] >= 4 * K_TIE_CAP, c['ties']
+    else:
+        want = K_TIE_CAP + (1 if ties == "cap+1" else 0)
+        assert c['ties'] == want, (c['ties'], want)
+    rc, res, guard_ok = _run_edge_segmax(dev, c, form, with_db=with_db)
+    assert rc == 0
+    assert guard_ok
+    _check_edge_segmax(c, form, res, with_db=with_db)
+
+
+@pytest.mark.parametrize("layout", ["offset4", "odd", "separate"])
+def test_edge_segmax_fc_bwd_unaligned_contiguous_pq(dev, layout):
+    """dQ == dP + num_vertices * ld_pq (one buffer, as the trainer lays them
+    out) is zeroed in the same launch as the counts -- as 16-byte words.  The
+    header asks for no alignment, so a dP 4 bytes into its buffer, or an odd
+    num_vertices * ld_pq, must work too (and as with two separate buffers),
+    within the bars of the float64 adjoint."""
+    if layout == "odd":
+        c = _edge_segmax_case(5, 37, n_cols=200, k_in=100, spare=16, ld_pq=103)
+        assert (c['nv'] * c['ld_pq']) % 2 == 1
+    else:
+        c = _edge_segmax_case(5, 37, n_cols=200, k_in=100, spare=17)
+    for form in ("h1", "pq"):
+        rc, res, guard_ok = _run_edge_segmax(
+            dev, c, form, pq_offset=1 if layout == "offset4" else 0,
+            contiguous=layout != "separate")
+        assert rc == 0, (layout, form, rc)
+        assert guard_ok, "outside dP | dQ written"
+        _check_edge_segmax(c, form, res)
+
+
 @pytest.mark.parametrize("name,fixture", [
     ("car_auto_T1", "graph_tiny.npz"), ("car_auto_T3", "graph_tiny.npz"),
     ("ped_cyl_auto_T3", "graph_tiny.npz"), ("car_auto_T0", "graph_tiny.npz"),
     # 194k level-1 edges: the native forward takes the fused rows-emitting
-    # edge kernel (>= ~65k edges), the backward recomputes H1 from P and Q
+    # edge kernel (>= ~65k edges), which with the default tunable
+    # train_h1 = 1 also writes H1 for the backward to read (the train_h1 = 0
+    # backward, which recomputes H1 from P and Q, is held to the float64
+    # oracle in tests/test_gpu_train_fullsize.py)
     ("car_auto_T3", "graph_small.npz"), ("ped_cyl_auto_T3", "graph_small.npz")])
 def test_native_sparse_and_dense_steps_give_the_same_gradient(dev, name,
                                                               fixture):

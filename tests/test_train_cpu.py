@@ -49,6 +49,43 @@ def test_learning_rate_schedule():
     assert abs(learning_rate(tc, 1399999) - 0.125e-3) < 1e-12
 
 
+def test_adam_step_survives_a_long_run():
+    """train.adam_step_from_checkpoint: Adam's step count from a checkpoint
+    whose beta powers are float32, written exactly as
+    Trainer.optimizer_state_dict writes them (beta^(t+1)).  beta1_power alone
+    is subnormal from t = 959 and zero from t ~ 985 (0.9^(t+1)); beta2_power
+    carries the count to ~87k steps; past that the count falls back to
+    global_step -- but only when the checkpoint holds Adam's slots."""
+    from pointgnn_amd.train import adam_step_from_checkpoint
+    slots = {'layer1/extract_vertex_features/fully_connected/weights/Adam':
+             np.zeros((4, 32), np.float32),
+             'layer1/extract_vertex_features/fully_connected/weights/Adam_1':
+             np.zeros((4, 32), np.float32)}
+    sweep = [1, 3, 500] + list(range(958, 1001)) + [2000, 50000, 90000]
+    for kw in ({'beta1': 0.9, 'beta2': 0.999, 'epsilon': 1e-8},
+               {'beta1': 0.8, 'beta2': 0.999, 'epsilon': 1e-6}):
+        for t in sweep:
+            ck = dict(slots, Variable=np.int32(t + 7),
+                      beta1_power=np.float32(kw['beta1'] ** (t + 1)),
+                      beta2_power=np.float32(kw['beta2'] ** (t + 1)))
+            got = adam_step_from_checkpoint(ck, kw, t)
+            assert got == t, (kw, t, got)
+            # which source answered: a different global_step shows it
+            fallback = not np.float32(kw['beta2'] ** (t + 1)) >= \
+                np.finfo(np.float32).tiny
+            got = adam_step_from_checkpoint(ck, kw, t + 7)
+            assert got == (t + 7 if fallback else t), (kw, t, got)
+            assert fallback == (t == 90000), t
+    # no Adam slots (another optimizer's checkpoint): a fresh clock
+    kw = {'beta1': 0.9, 'beta2': 0.999, 'epsilon': 1e-8}
+    assert adam_step_from_checkpoint({'Variable': np.int32(5000)}, kw, 5000) == 0
+    other = {'layer1/extract_vertex_features/fully_connected/weights/Momentum':
+             np.zeros((4, 32), np.float32)}
+    assert adam_step_from_checkpoint(other, kw, 5000) == 0
+    # Adam's slots without beta powers: global_step
+    assert adam_step_from_checkpoint(dict(slots), kw, 5000) == 5000
+
+
 def test_mask_matched_oracle_replays_its_own_decisions():
     """oracle/train_oracle.Decisions: replaying the decisions a forward
     recorded reproduces its loss and gradients exactly; replaying a float32
