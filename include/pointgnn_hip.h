@@ -526,7 +526,7 @@ int pgnn_edge_mlp_scatter_max_fwd_dyn(const float *P, const float *Q,
                                       void *stream);
 
 /* SECONDARY arithmetic for the same stage with ONE remaining edge layer of
- * 300x300 or 256x256 (csrc/edge_ws_bf16.h): the layer's product runs on the
+ * 300x300 or 256x256 (csrc/edge_ws_split.h, Bf16x3): the layer's product runs on the
  * bf16 matrix pipe with BOTH operands split exactly into three bf16 parts
  * (8 + 8 + 8 significand bits) and the six products of combined order <= 2
  * accumulated in fp32 -- the dropped terms are below 2^-24 of a product, one
@@ -555,7 +555,7 @@ int pgnn_edge_mlp_scatter_max_bf16x3_fwd(
     const pgnn_dyn_count *num_vertices, void *stream);
 
 /* SECONDARY arithmetic 'f16x2' for the same stage and shapes
- * (csrc/edge_ws_f16.h): both operands of the layer's product are represented
+ * (csrc/edge_ws_split.h, F16x2): both operands of the layer's product are represented
  * by TWO fp16 values (x ~ x0 + x1' / 2^11, round to nearest, 22 significand
  * bits), three fp16 MFMAs per block accumulate in fp32 -- half the matrix
  * instructions of the bf16x3 entry, three column groups instead of four.  Not

@@ -346,7 +346,7 @@ extern "C" size_t pgnn_packed_fc_floats(int32_t k_in, int32_t n_out) {
   return kq * nt * 256 + nt * 16;
 }
 
-// ---- split-bf16 weight image (edge_ws_bf16.h) ----------------------------------
+// ---- split-precision weight images (edge_ws_split.h, pool_ws_f16.h) ------------
 namespace {
 inline uint16_t bf16_rne(float x) {
   uint32_t u;
@@ -359,65 +359,46 @@ inline float bf16_as_float(uint16_t h) {
   memcpy(&f, &u, 4);
   return f;
 }
-}  // namespace
 
-extern "C" size_t pgnn_packed_fc_bf16x3_bytes(int32_t k_in, int32_t n_out) {
+// x = x0 + x1 + x2 exactly: both residuals are exact in fp32
+struct SplitBf16x3 {
+  static constexpr int kParts = 3;
+  static void split(float x, uint16_t (&p)[kParts]) {
+    p[0] = bf16_rne(x);
+    const float r1 = x - bf16_as_float(p[0]);
+    p[1] = bf16_rne(r1);
+    p[2] = bf16_rne(r1 - bf16_as_float(p[1]));
+  }
+};
+// x ~ w0 + w1' / 2^11: the residual is exact in fp32, the scaling (a power of
+// two) keeps it out of fp16's subnormals
+struct SplitF16x2 {
+  static constexpr int kParts = 2;
+  static void split(float x, uint16_t (&p)[kParts]) {
+    const _Float16 w0 = (_Float16)x;
+    const _Float16 w1 = (_Float16)((x - (float)w0) * 2048.0f);
+    memcpy(&p[0], &w0, 2);
+    memcpy(&p[1], &w1, 2);
+  }
+};
+
+template <class S>
+size_t packed_split_bytes(int32_t k_in, int32_t n_out) {
   if (k_in <= 0 || n_out <= 0) return 0;
   const size_t kb = (k_in + 31) / 32, nt = (n_out + 15) / 16;
-  return kb * nt * 3 * 1024 + nt * 16 * sizeof(float);
+  return kb * nt * S::kParts * 1024 + nt * 16 * sizeof(float);
 }
 
-extern "C" int pgnn_pack_fc_bf16x3(const float *w, const float *b, int32_t k_in,
-                                   int32_t n_out, void *image) {
-  PGNN_GUARD_BEGIN
-  PGNN_REQUIRE(w && image && k_in > 0 && n_out > 0, PGNN_E_INVALID,
-               "pack_fc_bf16x3: bad argument");
+// image [kb][t][part][lane][8] of 16-bit parts, the bias (fp32, 16 nt values)
+// behind it.  Slot (g, j) of lane (g, n) in block kb holds row 32 kb + 8 g + j
+// of the weights, or (acc_order) row 32 kb + 4 g + j (j < 4) / 32 kb + 16 + 4 g
+// + j - 4: the order in which a lane of the fp32 MFMA accumulators of the
+// layer below holds a row's features (pool_ws_f16.h)
+template <class S>
+void pack_fc_split(const float *w, const float *b, int32_t k_in, int32_t n_out,
+                   void *image, bool acc_order) {
   const int kb_n = (k_in + 31) / 32, nt = (n_out + 15) / 16;
   uint16_t *img = reinterpret_cast<uint16_t *>(image);
-  for (int kb = 0; kb < kb_n; ++kb)
-    for (int t = 0; t < nt; ++t)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 8; ++j) {
-          const int k = 32 * kb + 8 * (lane >> 4) + j;
-          const int n = 16 * t + (lane & 15);
-          const float x = (k < k_in && n < n_out) ? w[(size_t)k * n_out + n] : 0.0f;
-          // x = x0 + x1 + x2 exactly: both residuals are exact in fp32
-          const uint16_t p0 = bf16_rne(x);
-          const float r1 = x - bf16_as_float(p0);
-          const uint16_t p1 = bf16_rne(r1);
-          const float r2 = r1 - bf16_as_float(p1);
-          const uint16_t p2 = bf16_rne(r2);
-          const size_t frag = ((size_t)kb * nt + t) * 3;
-          img[((frag + 0) * 64 + lane) * 8 + j] = p0;
-          img[((frag + 1) * 64 + lane) * 8 + j] = p1;
-          img[((frag + 2) * 64 + lane) * 8 + j] = p2;
-        }
-  float *bias = reinterpret_cast<float *>(reinterpret_cast<char *>(image) +
-                                          (size_t)kb_n * nt * 3 * 1024);
-  for (int n = 0; n < nt * 16; ++n) bias[n] = (b && n < n_out) ? b[n] : 0.0f;
-  return 0;
-  PGNN_GUARD_END
-}
-
-extern "C" size_t pgnn_packed_fc_f16x2_bytes(int32_t k_in, int32_t n_out) {
-  if (k_in <= 0 || n_out <= 0) return 0;
-  const size_t kb = (k_in + 31) / 32, nt = (n_out + 15) / 16;
-  return kb * nt * 2 * 1024 + nt * 16 * sizeof(float);
-}
-
-namespace {
-// acc_order: slot (g, j) of block kb holds feature 32 kb + 4 g + j (j < 4) or
-// 32 kb + 16 + 4 g + j - 4 -- the order in which a lane of the fp32 MFMA
-// accumulators of the layer below holds a row's features (pool_ws_f16.h)
-int pack_fc_f16x2(const float *w, const float *b, int32_t k_in, int32_t n_out,
-                  void *image, bool acc_order) {
-  PGNN_REQUIRE(w && image && k_in > 0 && n_out > 0, PGNN_E_INVALID,
-               "pack_fc_f16x2: bad argument");
-  const int kb_n = (k_in + 31) / 32, nt = (n_out + 15) / 16;
-  for (size_t i = 0; i < (size_t)k_in * n_out; ++i)
-    PGNN_REQUIRE(std::fabs(w[i]) < 32768.0f, PGNN_E_UNSUPPORTED,
-                 "pack_fc_f16x2: a weight outside fp16's range");
-  _Float16 *img = reinterpret_cast<_Float16 *>(image);
   for (int kb = 0; kb < kb_n; ++kb)
     for (int t = 0; t < nt; ++t)
       for (int lane = 0; lane < 64; ++lane)
@@ -428,20 +409,46 @@ int pack_fc_f16x2(const float *w, const float *b, int32_t k_in, int32_t n_out,
                                               : 16 + 4 * g + (j - 4));
           const int n = 16 * t + (lane & 15);
           const float x = (k < k_in && n < n_out) ? w[(size_t)k * n_out + n] : 0.0f;
-          // x ~ w0 + w1' / 2^11: the residual is exact in fp32, the scaling
-          // (a power of two) keeps it out of fp16's subnormals
-          const _Float16 w0 = (_Float16)x;
-          const _Float16 w1 = (_Float16)((x - (float)w0) * 2048.0f);
-          const size_t frag = ((size_t)kb * nt + t) * 2;
-          img[((frag + 0) * 64 + lane) * 8 + j] = w0;
-          img[((frag + 1) * 64 + lane) * 8 + j] = w1;
+          uint16_t p[S::kParts];
+          S::split(x, p);
+          const size_t frag = ((size_t)kb * nt + t) * S::kParts;
+          for (int i = 0; i < S::kParts; ++i)
+            img[((frag + i) * 64 + lane) * 8 + j] = p[i];
         }
   float *bias = reinterpret_cast<float *>(reinterpret_cast<char *>(image) +
-                                          (size_t)kb_n * nt * 2 * 1024);
+                                          (size_t)kb_n * nt * S::kParts * 1024);
   for (int n = 0; n < nt * 16; ++n) bias[n] = (b && n < n_out) ? b[n] : 0.0f;
+}
+
+int pack_fc_f16x2(const float *w, const float *b, int32_t k_in, int32_t n_out,
+                  void *image, bool acc_order) {
+  PGNN_REQUIRE(w && image && k_in > 0 && n_out > 0, PGNN_E_INVALID,
+               "pack_fc_f16x2: bad argument");
+  for (size_t i = 0; i < (size_t)k_in * n_out; ++i)
+    PGNN_REQUIRE(std::fabs(w[i]) < 32768.0f, PGNN_E_UNSUPPORTED,
+                 "pack_fc_f16x2: a weight outside fp16's range");
+  pack_fc_split<SplitF16x2>(w, b, k_in, n_out, image, acc_order);
   return 0;
 }
 }  // namespace
+
+extern "C" size_t pgnn_packed_fc_bf16x3_bytes(int32_t k_in, int32_t n_out) {
+  return packed_split_bytes<SplitBf16x3>(k_in, n_out);
+}
+
+extern "C" size_t pgnn_packed_fc_f16x2_bytes(int32_t k_in, int32_t n_out) {
+  return packed_split_bytes<SplitF16x2>(k_in, n_out);
+}
+
+extern "C" int pgnn_pack_fc_bf16x3(const float *w, const float *b, int32_t k_in,
+                                   int32_t n_out, void *image) {
+  PGNN_GUARD_BEGIN
+  PGNN_REQUIRE(w && image && k_in > 0 && n_out > 0, PGNN_E_INVALID,
+               "pack_fc_bf16x3: bad argument");
+  pack_fc_split<SplitBf16x3>(w, b, k_in, n_out, image, false);
+  return 0;
+  PGNN_GUARD_END
+}
 
 extern "C" int pgnn_pack_fc_f16x2(const float *w, const float *b, int32_t k_in,
                                   int32_t n_out, void *image) {

@@ -104,7 +104,7 @@ struct EdgeWsArgs {
   // [n_edges, 4 * ldv4] (written by the workgroups of column group 0 only:
   // every group gathers the same rows)
   float *h1_out;
-  // edge_ws_f16.h only: the vertex count of a capacity-form call (nullable;
+  // edge_ws_split.h, F16x2 only: the vertex count of a capacity-form call (nullable;
   // min(*nv_dev, num_segments) rows of P / Q exist) for the range guard
   const int32_t *nv_dev;
 };
@@ -566,6 +566,128 @@ __device__ __forceinline__ WsWho ws_who_balanced(const EdgeWsArgs &a, int slice,
   return w;
 }
 
+// ---- the frame the weights-stationary kernels share ---------------------------
+// (edge_ws_kernel, edge_ws_split.h, pool_ws.h, pool_ws_f16.h).  A helper is
+// adopted where the kernel's instruction stream stays what it was; the places
+// where it does not keep their copy and say so.
+
+// Fragments 0 .. n_frag-1 of a workgroup (1 KiB each: one V per lane; fragment f
+// is fragment src_frag(f) of the packed image a.wp) -> LDS `wl`, wave w taking
+// fragments w, w + 8, ...; then the bias values of its column tiles t0 ..
+// t0+ntg-1, which sit in the image behind `bias_at` floats.
+// Every wave requests ALL its fragments (PER dwordx4 per lane) before the first
+// LDS write: as a plain copy loop hipcc emits load -> s_waitcnt vmcnt(0) ->
+// ds_write per fragment, 17 dependent round trips to L2 / HBM with 2048 waves
+// asking at once -- ~25 us of a 985 us kernel in which no SIMD had anything to
+// do (tools/ws_timeline.py: the last wave ends 40 us before the kernel does).
+// Unconditional clamped requests, the validity test at the write.
+// (No __restrict__ on a helper's parameters: unlike the qualifier on a local
+// pointer it survives inlining as alias scopes and changes the schedule.)
+template <int PER, class V, class ARGS, class MAP>
+__device__ __forceinline__ void ws_stage(const ARGS &a, V *wl, int n_frag,
+                                         MAP src_frag, size_t bias_at, int t0,
+                                         int ntg, float *bias_lds, int wave,
+                                         int lane) {
+  const V *src = reinterpret_cast<const V *>(a.wp);
+  V tmp[PER];
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const int f = wave + i * kWsWaves;
+    tmp[i] = src[src_frag(f < n_frag ? f : 0) * 64 + lane];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const int f = wave + i * kWsWaves;
+    if (f < n_frag) wl[(size_t)f * 64 + lane] = tmp[i];
+  }
+  if ((int)threadIdx.x < 16 * ntg)
+    bias_lds[threadIdx.x] = a.wp[bias_at + 16 * t0 + threadIdx.x];
+}
+
+// capacity form: min(*n_dev, cap) rows are processed
+__device__ __forceinline__ int64_t ws_edge_count(int64_t cap,
+                                                 const int32_t *n_dev) {
+  if (n_dev) {
+    const int64_t nd = *n_dev;
+    cap = nd < cap ? nd : cap;
+  }
+  return cap;
+}
+
+// the column group of this workgroup
+__device__ __forceinline__ int ws_group(const EdgeWsArgs &a, int slice,
+                                        int local, int wave) {
+  if (a.balanced) return ws_who_balanced(a, slice, local, wave).grp;
+  int grp = 0;
+  while (grp + 1 < a.groups && local >= a.wg0[grp + 1]) ++grp;
+  return grp;
+}
+
+// Row tiles [first, last) are shared by the nw waves of a column group, this
+// wave being number wi: the slice's tiles over the slice's workgroups of the
+// group, or (balanced form) all tiles over all the group's workgroups
+struct WsShare {
+  int64_t first, last, nw, wi;
+};
+__device__ __forceinline__ WsShare ws_share(const EdgeWsArgs &a, int grp,
+                                            int slice, int local, int wave,
+                                            int64_t n_wt) {
+  WsShare s;
+  s.first = n_wt * slice / a.xcds;
+  s.last = n_wt * (slice + 1) / a.xcds;
+  s.nw = (int64_t)(a.wg0[grp + 1] - a.wg0[grp]) * kWsWaves;
+  s.wi = (int64_t)(local - a.wg0[grp]) * kWsWaves + wave;
+  if (a.balanced) {  // (no pool)
+    const WsWho w = ws_who_balanced(a, slice, local, wave);
+    s.first = 0;
+    s.last = n_wt;
+    s.nw = w.nw;
+    s.wi = w.wi;
+  }
+  return s;
+}
+
+// Tile pool: the last pool_pct % of `span` tiles are handed out dynamically,
+// unless that leaves the static ranges less than `least` tiles
+__device__ __forceinline__ int64_t ws_pool_size(int64_t span, const int32_t *sched,
+                                                int pool_pct, int least,
+                                                int64_t nw) {
+  int64_t pool = sched ? span * pool_pct / 100 : 0;
+  if (span - pool < least * nw) pool = 0;  // too little work to bother
+  return pool;
+}
+
+// ... `chunk` tiles at a time from `counter`: the offset in the pool of the
+// chunk this wave gets (at or behind the pool's size: the pool is empty)
+__device__ __forceinline__ int ws_pool_claim(int32_t *counter, int chunk,
+                                             int lane) {
+  int c = 0;
+  if (lane == 0)
+    c = __hip_atomic_fetch_add(counter, chunk, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+  return __builtin_amdgcn_readfirstlane(c);
+}
+
+// ... and the last wave to get here re-arms the n_counters counters behind
+// sched[2]: every claim of this launch was made before its wave counted itself
+// done (sched[1])
+__device__ __forceinline__ void ws_pool_rearm(int32_t *sched, int n_counters,
+                                              int lane) {
+  if (sched && lane == 0) {
+    const int total = (int)gridDim.x * kWsWaves;
+    const int done = __hip_atomic_fetch_add(&sched[1], 1, __ATOMIC_ACQ_REL,
+                                            __HIP_MEMORY_SCOPE_AGENT);
+    if (done == total - 1) {
+      for (int i = 0; i < n_counters; ++i)
+        __hip_atomic_store(&sched[2 + i], 0, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&sched[1], 0, __ATOMIC_RELEASE,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 template <int KQ, int NTMAX, bool EMIT = false, bool ROWS = false>
 __global__ __launch_bounds__(64 * kWsWaves) void edge_ws_kernel(EdgeWsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -578,24 +700,14 @@ __global__ __launch_bounds__(64 * kWsWaves) void edge_ws_kernel(EdgeWsArgs a) {
   // profiling builds only: when this wave entered the kernel (constant
   // 100 MHz clock), i.e. before the weights go to LDS
   const long long rt_entry = a.ts ? (long long)__builtin_amdgcn_s_memrealtime() : 0;
-  int grp = 0;
-  if (a.balanced) {
-    grp = ws_who_balanced(a, slice, local, wave).grp;
-  } else {
-    while (grp + 1 < a.groups && local >= a.wg0[grp + 1]) ++grp;
-  }
+  const int grp = ws_group(a, slice, local, wave);
   const int t0 = a.tile0[grp];
   const int ntg = a.tile0[grp + 1] - t0;
   // this group's weight fragments -> LDS, [q][t][lane] float4 (1 KiB each),
-  // and its bias values
+  // and its bias values: ws_stage with the map (q, t) -> (q, t0 + t), written
+  // out (through the helper hipcc orders this kernel's address arithmetic
+  // differently; its instruction stream is kept as it was)
   {
-    // Every wave requests ALL its fragments (<= 17 dwordx4 per lane) before
-    // the first LDS write: as a plain copy loop hipcc emits load ->
-    // s_waitcnt vmcnt(0) -> ds_write per fragment, 17 dependent round trips
-    // to L2 / HBM with 2048 waves asking at once -- ~25 us of a 985 us kernel
-    // in which no SIMD had anything to do (tools/ws_timeline.py: the last wave
-    // ends 40 us before the kernel does).  Unconditional clamped requests,
-    // the validity test at the write.
     const v4f *__restrict__ src = reinterpret_cast<const v4f *>(a.wp);
     constexpr int PER = (KQ * NTMAX + kWsWaves - 1) / kWsWaves;
     const int n_frag = KQ * ntg;
@@ -624,30 +736,14 @@ __global__ __launch_bounds__(64 * kWsWaves) void edge_ws_kernel(EdgeWsArgs a) {
   // waves take `chunk` tiles at a time when their own range is done -- slack
   // for waves that hit more segment boundaries, slower CUs, or a late start
   // behind another stream's kernels.  A pool chunk is a range of its own.
-  int64_t n_edges = a.n_edges;
-  if (a.n_dev) {
-    const int64_t nd = *a.n_dev;
-    n_edges = nd < n_edges ? nd : n_edges;
-  }
-  const int64_t n_wt = (n_edges + 15) / 16;
-  int64_t s_first = n_wt * slice / a.xcds;
-  int64_t s_last = n_wt * (slice + 1) / a.xcds;
-  int64_t nw = (int64_t)(a.wg0[grp + 1] - a.wg0[grp]) * kWsWaves;
-  int64_t wi = (int64_t)(local - a.wg0[grp]) * kWsWaves + wave;
-  if (a.balanced) {  // all row tiles over all the group's waves (no pool)
-    const WsWho w = ws_who_balanced(a, slice, local, wave);
-    s_first = 0;
-    s_last = n_wt;
-    nw = w.nw;
-    wi = w.wi;
-  }
-  int64_t span = s_last - s_first;
-  int64_t pool = a.sched ? span * a.pool_pct / 100 : 0;
-  if (span - pool < 4 * nw) pool = 0;  // too little work to bother
+  const int64_t n_edges = ws_edge_count(a.n_edges, a.n_dev);
+  const WsShare s = ws_share(a, grp, slice, local, wave, (n_edges + 15) / 16);
+  int64_t span = s.last - s.first;
+  const int64_t pool = ws_pool_size(span, a.sched, a.pool_pct, 4, s.nw);
   span -= pool;
-  const int64_t pool_first = s_first + span;
-  int64_t tile_first = s_first + span * wi / nw;
-  int64_t tile_last = s_first + span * (wi + 1) / nw;
+  const int64_t pool_first = s.first + span;
+  int64_t tile_first = s.first + span * s.wi / s.nw;
+  int64_t tile_last = s.first + span * (s.wi + 1) / s.nw;
   long long *tsw = nullptr;
   if (a.ts) {
     tsw = a.ts + ((int64_t)blockIdx.x * kWsWaves + wave) * kWsStampStride;
@@ -660,6 +756,7 @@ __global__ __launch_bounds__(64 * kWsWaves) void edge_ws_kernel(EdgeWsArgs a) {
     }
   }
   int stamped = 0;
+  // one pool counter per (row slice, column group)
   int32_t *counter = a.sched ? a.sched + 2 + slice * kWsMaxGroups + grp : nullptr;
   for (;;) {
     if (ntg == NTMAX)
@@ -671,14 +768,10 @@ __global__ __launch_bounds__(64 * kWsWaves) void edge_ws_kernel(EdgeWsArgs a) {
                                               tile_last, lane, tsw, stamped,
                                               n_edges);
     if (pool == 0) break;
-    int c = 0;
-    if (lane == 0)
-      c = __hip_atomic_fetch_add(counter, a.chunk, __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
-    c = __builtin_amdgcn_readfirstlane(c);
+    const int c = ws_pool_claim(counter, a.chunk, lane);
     if (c >= pool) break;
-    tile_first = pool_first + c;
-    tile_last = tile_first + a.chunk < s_last ? tile_first + a.chunk : s_last;
+    tile_first = pool_first + c;  // a pool chunk is a range of its own
+    tile_last = tile_first + a.chunk < s.last ? tile_first + a.chunk : s.last;
   }
   if (tsw && lane == 0) {
     tsw[1] = __builtin_readcyclecounter();
@@ -686,8 +779,9 @@ __global__ __launch_bounds__(64 * kWsWaves) void edge_ws_kernel(EdgeWsArgs a) {
     tsw[7] = stamped;
   }
   if (a.sched && lane == 0) {
-    // the last wave to get here re-arms the counters: every claim of this
-    // launch was made before its wave counted itself done
+    // ws_pool_rearm for a.xcds * kWsMaxGroups counters, written out: through
+    // the helper the (cold) loop compiles to one instruction less, and this
+    // kernel's instruction stream is kept as it was
     const int total = (int)gridDim.x * kWsWaves;
     const int done = __hip_atomic_fetch_add(&a.sched[1], 1, __ATOMIC_ACQ_REL,
                                             __HIP_MEMORY_SCOPE_AGENT);

@@ -14,8 +14,7 @@
 // The E x C activations never reach HBM.
 #include "mlp_engine.h"
 #include "edge_ws.h"
-#include "edge_ws_bf16.h"
-#include "edge_ws_f16.h"
+#include "edge_ws_split.h"
 #include "pool_ws.h"
 #include "pool_split.h"
 #include "pool_ws_f16.h"
@@ -1711,49 +1710,81 @@ int ws_partition(EdgeWsArgs &a, int nt, int ntmax, int cus) {
   return 0;
 }
 
-template <int KB, int NTMAX>
-int launch_edge_ws3(EdgeWsArgs &a, int nt, int cus, hipStream_t stream) {
+// Host side of an arithmetic of edge_ws_split.h: its name in messages, the
+// largest column group per K depth (KB = 10: 19 tiles in 5/5/5/4 resp. 7/6/6;
+// KB = 8: 16 in 4 x 4 resp. 6/5/5), the relative cost of a row tile per group
+// -- mfma cycles of a column tile (60 resp. 30 MFMAs of 16 cycles at KB = 10) +
+// the part of the gather / split / segmented max that does not hide behind
+// them (bf16x3: round 4's 2.4k cycles, when nothing did; the interleaved body
+// leaves about a third) --, and whether the waves raise their priority
+// outside the MFMA loop (g_ws_prio)
+template <class Arith>
+struct SplitHost;
+template <>
+struct SplitHost<Bf16x3> {
+  static constexpr const char *kName = "edge_bf16x3";
+  static constexpr int kNtMax10 = 5, kNtMax8 = 5;
+  static constexpr double kTileCost = 960.0, kRowCost = 2400.0;
+  static int prio() { return g_ws_prio; }
+};
+template <>
+struct SplitHost<F16x2> {
+  static constexpr const char *kName = "edge_f16x2";
+  static constexpr int kNtMax10 = 7, kNtMax8 = 6;
+  static constexpr double kTileCost = 480.0, kRowCost = 1600.0;
+  static int prio() { return 0; }
+};
+
+template <class Arith>
+std::string split_msg(const char *what) {
+  return std::string(SplitHost<Arith>::kName) + ": " + what;
+}
+
+template <class Arith, int KB, int NTMAX>
+int launch_edge_ws_split(EdgeWsArgs &a, int nt, int cus, int32_t *status,
+                         hipStream_t stream) {
+  using H = SplitHost<Arith>;
   const int rc = ws_partition(a, nt, NTMAX, cus);
   if (rc) return rc;
   {
-    // relative cost of a row tile: 60 MFMAs of 16 cycles per column tile + the
-    // part of the gather / split / segmented max that does not hide behind them
-    // (round 4's 2.4k cycles, when nothing did; the interleaved body leaves
-    // about a third: tools/sessions/r05_s9.sh)
     double cost[kWsMaxGroups];
     for (int g = 0; g < a.groups; ++g)
-      cost[g] = 960.0 * KB / 10 * (a.tile0[g + 1] - a.tile0[g]) + 2400.0;
+      cost[g] = H::kTileCost * KB / 10 * (a.tile0[g + 1] - a.tile0[g]) + H::kRowCost;
     if (g_ws_balance) ws_balance(a, cus, cost);
   }
-  const size_t lds = (size_t)KB * NTMAX * 3 * 1024 + 16 * NTMAX * sizeof(float);
+  const size_t lds =
+      (size_t)KB * NTMAX * Arith::kParts * 1024 + 16 * NTMAX * sizeof(float);
   PGNN_REQUIRE(lds <= device_max_lds(), PGNN_E_UNSUPPORTED,
-               "edge_bf16x3: column group does not fit the LDS");
-  auto kern = edge_ws_bf16x3_kernel<KB, NTMAX>;
+               split_msg<Arith>("column group does not fit the LDS").c_str());
+  auto kern = edge_ws_split_kernel<Arith, KB, NTMAX>;
   const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
   if (lrc) return lrc;
   hipLaunchKernelGGL(kern, dim3((unsigned)(cus / a.xcds * a.xcds)),
-                     dim3(64 * kWsWaves), lds, stream, a);
+                     dim3(64 * kWsWaves), lds, stream, a, status);
   PGNN_HIP(hipGetLastError());
   return 0;
 }
-}  // namespace
 
-extern "C" int pgnn_edge_mlp_scatter_max_bf16x3_fwd(
-    const float *P, const float *Q, int64_t ld_pq, int32_t width,
-    const int32_t *edges, int64_t edges_cap, int32_t vertices_cap,
-    const void *image, int32_t n_out, int32_t relu_from, int32_t edges_sorted,
-    float *out, int64_t ld_out, const pgnn_dyn_count *n_edges,
-    const pgnn_dyn_count *num_vertices, void *stream_) {
-  PGNN_GUARD_BEGIN
-  hipStream_t stream = (hipStream_t)stream_;
+// the two split-precision edge entries; status: F16x2's range flag (null for
+// Bf16x3, whose kernel has no guard)
+template <class Arith>
+int edge_split_fwd_impl(const float *P, const float *Q, int64_t ld_pq,
+                        int32_t width, const int32_t *edges, int64_t edges_cap,
+                        int32_t vertices_cap, const void *image, int32_t n_out,
+                        int32_t relu_from, int32_t edges_sorted, float *out,
+                        int64_t ld_out, int32_t *status,
+                        const pgnn_dyn_count *n_edges,
+                        const pgnn_dyn_count *num_vertices, hipStream_t stream) {
+  using H = SplitHost<Arith>;
   PGNN_REQUIRE(edges_cap >= 0 && vertices_cap >= 0 && width > 0 && n_out > 0 &&
                    image,
-               PGNN_E_INVALID, "edge_bf16x3: bad argument");
+               PGNN_E_INVALID, split_msg<Arith>("bad argument").c_str());
   const Dyn de = dyn_of(n_edges), dk = dyn_of(num_vertices);
   const int kq = (width + 15) / 16, nt = (n_out + 15) / 16;
   const int kb = (width + 31) / 32;
   PGNN_REQUIRE(ld_pq == 16 * kq && ld_out >= 16 * nt, PGNN_E_INVALID,
-               "edge_bf16x3: ld_pq / ld_out do not match the padded widths");
+               split_msg<Arith>("ld_pq / ld_out do not match the padded widths")
+                   .c_str());
   int cus = stream_cu_count(stream);
   if (g_ws_reserve > 0 && cus - g_ws_reserve >= 64) cus -= g_ws_reserve;
   // the shapes the kernel is instantiated for, and enough rows to amortise
@@ -1766,16 +1797,19 @@ extern "C" int pgnn_edge_mlp_scatter_max_bf16x3_fwd(
       (int64_t)vertices_cap * ld_pq * 4 >= ((int64_t)1 << 32))
     return PGNN_E_UNSUPPORTED;  // (no message: an expected answer)
   if (vertices_cap == 0) return 0;
-  PGNN_REQUIRE(out != nullptr, PGNN_E_INVALID, "edge_bf16x3: null output");
+  PGNN_REQUIRE(out != nullptr, PGNN_E_INVALID,
+               split_msg<Arith>("null output").c_str());
   if (!(edges_sorted & 2)) {
     const int rc = fill_lowest_rows(out, ld_out, vertices_cap, dk, stream);
     if (rc) return rc;
   }
   if (edges_cap == 0) return 0;
-  PGNN_REQUIRE(P && Q && edges, PGNN_E_INVALID, "edge_bf16x3: null input");
+  PGNN_REQUIRE(P && Q && edges, PGNN_E_INVALID,
+               split_msg<Arith>("null input").c_str());
   PGNN_REQUIRE(((uintptr_t)P % 16 == 0) && ((uintptr_t)Q % 16 == 0) &&
                    ((uintptr_t)image % 16 == 0),
-               PGNN_E_INVALID, "edge_bf16x3: P / Q / image must be 16-byte aligned");
+               PGNN_E_INVALID,
+               split_msg<Arith>("P / Q / image must be 16-byte aligned").c_str());
   EdgeWsArgs a = {};
   a.P = P;
   a.Q = Q;
@@ -1791,38 +1825,27 @@ extern "C" int pgnn_edge_mlp_scatter_max_bf16x3_fwd(
   a.num_segments = vertices_cap;
   a.sorted = edges_sorted & 1;
   a.xcds = (g_ws_xcds >= 1 && cus % g_ws_xcds == 0) ? g_ws_xcds : 8;
-  a.prio = g_ws_prio;
-  if (kb == 10) return launch_edge_ws3<10, 5>(a, nt, cus, stream);
-  return launch_edge_ws3<8, 5>(a, nt, cus, stream);
-  PGNN_GUARD_END
-}
-
-namespace {
-template <int KB, int NTMAX>
-int launch_edge_ws2(EdgeWsArgs &a, int nt, int cus, int32_t *status,
-                    hipStream_t stream) {
-  const int rc = ws_partition(a, nt, NTMAX, cus);
-  if (rc) return rc;
-  {
-    // relative cost of a row tile: 30 MFMAs of 16 cycles per column tile + the
-    // part of the gather / split / segmented max that does not hide behind them
-    double cost[kWsMaxGroups];
-    for (int g = 0; g < a.groups; ++g)
-      cost[g] = 480.0 * KB / 10 * (a.tile0[g + 1] - a.tile0[g]) + 1600.0;
-    if (g_ws_balance) ws_balance(a, cus, cost);
-  }
-  const size_t lds = (size_t)KB * NTMAX * 2 * 1024 + 16 * NTMAX * sizeof(float);
-  PGNN_REQUIRE(lds <= device_max_lds(), PGNN_E_UNSUPPORTED,
-               "edge_f16x2: column group does not fit the LDS");
-  auto kern = edge_ws_f16x2_kernel<KB, NTMAX>;
-  const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
-  if (lrc) return lrc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(cus / a.xcds * a.xcds)),
-                     dim3(64 * kWsWaves), lds, stream, a, status);
-  PGNN_HIP(hipGetLastError());
-  return 0;
+  a.prio = H::prio();
+  if (Arith::kRangeGuard) a.nv_dev = dk.dev;
+  if (kb == 10)
+    return launch_edge_ws_split<Arith, 10, H::kNtMax10>(a, nt, cus, status, stream);
+  return launch_edge_ws_split<Arith, 8, H::kNtMax8>(a, nt, cus, status, stream);
 }
 }  // namespace
+
+extern "C" int pgnn_edge_mlp_scatter_max_bf16x3_fwd(
+    const float *P, const float *Q, int64_t ld_pq, int32_t width,
+    const int32_t *edges, int64_t edges_cap, int32_t vertices_cap,
+    const void *image, int32_t n_out, int32_t relu_from, int32_t edges_sorted,
+    float *out, int64_t ld_out, const pgnn_dyn_count *n_edges,
+    const pgnn_dyn_count *num_vertices, void *stream_) {
+  PGNN_GUARD_BEGIN
+  return edge_split_fwd_impl<Bf16x3>(P, Q, ld_pq, width, edges, edges_cap,
+                                     vertices_cap, image, n_out, relu_from,
+                                     edges_sorted, out, ld_out, nullptr, n_edges,
+                                     num_vertices, (hipStream_t)stream_);
+  PGNN_GUARD_END
+}
 
 extern "C" int pgnn_edge_mlp_scatter_max_f16x2_fwd(
     const float *P, const float *Q, int64_t ld_pq, int32_t width,
@@ -1831,53 +1854,10 @@ extern "C" int pgnn_edge_mlp_scatter_max_f16x2_fwd(
     float *out, int64_t ld_out, int32_t *status, const pgnn_dyn_count *n_edges,
     const pgnn_dyn_count *num_vertices, void *stream_) {
   PGNN_GUARD_BEGIN
-  hipStream_t stream = (hipStream_t)stream_;
-  PGNN_REQUIRE(edges_cap >= 0 && vertices_cap >= 0 && width > 0 && n_out > 0 &&
-                   image,
-               PGNN_E_INVALID, "edge_f16x2: bad argument");
-  const Dyn de = dyn_of(n_edges), dk = dyn_of(num_vertices);
-  const int kq = (width + 15) / 16, nt = (n_out + 15) / 16;
-  const int kb = (width + 31) / 32;
-  PGNN_REQUIRE(ld_pq == 16 * kq && ld_out >= 16 * nt, PGNN_E_INVALID,
-               "edge_f16x2: ld_pq / ld_out do not match the padded widths");
-  int cus = stream_cu_count(stream);
-  if (g_ws_reserve > 0 && cus - g_ws_reserve >= 64) cus -= g_ws_reserve;
-  if (!((kb == 10 && nt == 19) || (kb == 8 && nt == 16)) || cus < 64 ||
-      cus % 8 != 0 ||
-      (!g_b16_force &&
-       expected(de, edges_cap) < (int64_t)16 * 2 * kWsWaves * cus) ||
-      (int64_t)vertices_cap * ld_pq * 4 >= ((int64_t)1 << 32))
-    return PGNN_E_UNSUPPORTED;  // (no message: an expected answer)
-  if (vertices_cap == 0) return 0;
-  PGNN_REQUIRE(out != nullptr, PGNN_E_INVALID, "edge_f16x2: null output");
-  if (!(edges_sorted & 2)) {
-    const int rc = fill_lowest_rows(out, ld_out, vertices_cap, dk, stream);
-    if (rc) return rc;
-  }
-  if (edges_cap == 0) return 0;
-  PGNN_REQUIRE(P && Q && edges, PGNN_E_INVALID, "edge_f16x2: null input");
-  PGNN_REQUIRE(((uintptr_t)P % 16 == 0) && ((uintptr_t)Q % 16 == 0) &&
-                   ((uintptr_t)image % 16 == 0),
-               PGNN_E_INVALID, "edge_f16x2: P / Q / image must be 16-byte aligned");
-  EdgeWsArgs a = {};
-  a.P = P;
-  a.Q = Q;
-  a.ldv4 = (int)(ld_pq >> 2);
-  a.edges = edges;
-  a.n_edges = edges_cap;
-  a.n_dev = de.dev;
-  a.wp = reinterpret_cast<const float *>(image);
-  a.nt = nt;
-  a.relu_from = relu_from;
-  a.out = out;
-  a.ldo = ld_out;
-  a.num_segments = vertices_cap;
-  a.sorted = edges_sorted & 1;
-  a.xcds = (g_ws_xcds >= 1 && cus % g_ws_xcds == 0) ? g_ws_xcds : 8;
-  a.prio = 0;
-  a.nv_dev = dk.dev;
-  if (kb == 10) return launch_edge_ws2<10, 7>(a, nt, cus, status, stream);
-  return launch_edge_ws2<8, 6>(a, nt, cus, status, stream);
+  return edge_split_fwd_impl<F16x2>(P, Q, ld_pq, width, edges, edges_cap,
+                                    vertices_cap, image, n_out, relu_from,
+                                    edges_sorted, out, ld_out, status, n_edges,
+                                    num_vertices, (hipStream_t)stream_);
   PGNN_GUARD_END
 }
 

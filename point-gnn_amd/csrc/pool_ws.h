@@ -54,6 +54,13 @@ struct PoolWsArgs {
   const void *l2_f16;
 };
 
+// second level of the index chain: the point index of the keypoint of edge
+// `e` (clamped: rows past the end / foreign ids read keypoint 0)
+__device__ __forceinline__ int pool_kp_of(const PoolWsArgs &a, bool ok, int2 e) {
+  const int d = ok ? e.y : 0;
+  return a.kp[((unsigned)d < (unsigned)a.num_segments) ? d : 0];
+}
+
 // acc[t] = sum_q W[q][tb + t]^T h[q]  for the NTB column tiles from tb on
 template <int KQ, int NT, int NTB>
 __device__ __forceinline__ void pool_ws_block(const v4f *const (&wfrag)[3],
@@ -137,11 +144,7 @@ __device__ __forceinline__ void pool_ws_body(const PoolWsArgs &a,
   // unconditional clamped requests, validity selects at the use (edge_ws.h)
   bool nxt_ok = e_first + n < E;
   int2 nxt = e2[nxt_ok ? e_first + n : 0];
-  int nxt_k;
-  {
-    const int d0 = nxt_ok ? nxt.y : 0;
-    nxt_k = a.kp[((unsigned)d0 < (unsigned)a.num_segments) ? d0 : 0];
-  }
+  int nxt_k = pool_kp_of(a, nxt_ok, nxt);
   for (int64_t tile = tile_first;; ++tile) {
     const bool fin = tile >= tile_last;
     const int64_t e0 = tile * 16;
@@ -176,6 +179,8 @@ __device__ __forceinline__ void pool_ws_body(const PoolWsArgs &a,
       nxt = e2[nxt_ok ? e0 + 16 + n : 0];
       // lane (g, n) holds input features 4g .. 4g+3 of row n: the B operand
       // of the first layer (K group 0); [f(src), xyz(src) - xyz(kp(dst))]
+      // (pool_ws2_body has its copy of this gather: as a shared function hipcc
+      // compiles it with one compare more in a different place, in both kernels)
       v4f x[1];
       x[0] = (v4f){0.f, 0.f, 0.f, 0.f};
       if (ok) {
@@ -231,10 +236,7 @@ __device__ __forceinline__ void pool_ws_body(const PoolWsArgs &a,
       }
       __builtin_amdgcn_sched_barrier(0);
       // second level of the next tile's index chain (its pair has landed)
-      {
-        const int dn = nxt_ok ? nxt.y : 0;
-        nxt_k = a.kp[((unsigned)dn < (unsigned)a.num_segments) ? dn : 0];
-      }
+      nxt_k = pool_kp_of(a, nxt_ok, nxt);
       const int up = __shfl_up(my_d, 1);
       const int prev = n == 0 ? run.cur_d : up;
       starts = (unsigned)(__ballot(my_d != prev) & 0xFFFFull);
@@ -302,44 +304,19 @@ __global__ __launch_bounds__(64 * kWsWaves) void pool_ws_kernel(PoolWsArgs a) {
   float *bias_lds = reinterpret_cast<float *>(wl + KQ * NT * 64);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  {
-    const v4f *__restrict__ src = reinterpret_cast<const v4f *>(a.wp);
-    // all 19 fragment requests of a wave in flight before the first LDS
-    // write (see edge_ws_kernel: the plain copy loop is 19 dependent round
-    // trips)
-    constexpr int PER = (KQ * NT + kWsWaves - 1) / kWsWaves;
-    v4f tmp[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int f = wave + i * kWsWaves;
-      tmp[i] = src[(size_t)(f < KQ * NT ? f : 0) * 64 + lane];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int f = wave + i * kWsWaves;
-      if (f < KQ * NT) wl[(size_t)f * 64 + lane] = tmp[i];
-    }
-    if ((int)threadIdx.x < 16 * NT)
-      bias_lds[threadIdx.x] = a.wp[(size_t)KQ * NT * 256 + threadIdx.x];
-  }
+  ws_stage<(KQ * NT + kWsWaves - 1) / kWsWaves>(
+      a, wl, KQ * NT, [](int f) { return (size_t)f; }, (size_t)KQ * NT * 256,
+      0, NT, bias_lds, wave, lane);
   __syncthreads();
   // static ranges for (100 - pool_pct) % of the 16-row tiles, the rest in
   // chunks from a pool (edge_ws.h); ~10 tiles per wave at E0 = 350k, so the
   // pool works in single tiles
-  int64_t n_edges = a.n_edges;
-  if (a.n_dev) {
-    const int64_t nd = *a.n_dev;
-    n_edges = nd < n_edges ? nd : n_edges;
-  }
+  const int64_t n_edges = ws_edge_count(a.n_edges, a.n_dev);
   const int64_t n_wt = (n_edges + 15) / 16;
   const int64_t nw = (int64_t)gridDim.x * kWsWaves;
   const int64_t wi = (int64_t)blockIdx.x * kWsWaves + wave;
-  int64_t span = n_wt;
-  int64_t pool = a.sched ? span * a.pool_pct / 100 : 0;
-  if (span - pool < 2 * nw) pool = 0;
-  span -= pool;
-  const int64_t pool_first = span;
+  const int64_t pool = ws_pool_size(n_wt, a.sched, a.pool_pct, 2, nw);
+  const int64_t span = n_wt - pool;  // the pool begins behind the static part
   int64_t tile_first = span * wi / nw;
   int64_t tile_last = span * (wi + 1) / nw;
   long long *tsw = nullptr;
@@ -358,13 +335,9 @@ __global__ __launch_bounds__(64 * kWsWaves) void pool_ws_kernel(PoolWsArgs a) {
     pool_ws_body<EMIT>(a, wl, bias_lds, tile_first, tile_last, lane, tsw,
                        stamped, n_edges);
     if (pool == 0) break;
-    int c = 0;
-    if (lane == 0)
-      c = __hip_atomic_fetch_add(&a.sched[2], a.chunk, __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
-    c = __builtin_amdgcn_readfirstlane(c);
+    const int c = ws_pool_claim(&a.sched[2], a.chunk, lane);
     if (c >= pool) break;
-    tile_first = pool_first + c;
+    tile_first = span + c;
     tile_last = tile_first + a.chunk < n_wt ? tile_first + a.chunk : n_wt;
   }
   if (tsw && lane == 0) {
@@ -372,17 +345,7 @@ __global__ __launch_bounds__(64 * kWsWaves) void pool_ws_kernel(PoolWsArgs a) {
     tsw[3] = __builtin_amdgcn_s_memrealtime();
     tsw[7] = stamped;
   }
-  if (a.sched && lane == 0) {
-    const int total = (int)gridDim.x * kWsWaves;
-    const int done = __hip_atomic_fetch_add(&a.sched[1], 1, __ATOMIC_ACQ_REL,
-                                            __HIP_MEMORY_SCOPE_AGENT);
-    if (done == total - 1) {
-      __hip_atomic_store(&a.sched[2], 0, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&a.sched[1], 0, __ATOMIC_RELEASE,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  ws_pool_rearm(a.sched, 1, lane);
 }
 
 }  // namespace pgnn

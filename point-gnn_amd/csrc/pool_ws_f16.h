@@ -2,7 +2,7 @@
 // car point MLP 4 -> 32 -> 64 -> 128 -> 300 of PointSetPooling (gnn.py:256-277),
 //     out[d] = max over edges (s -> d) of MLP([f(s), xyz(s) - xyz(kp(d))]),
 // with the LAST layer (128 -> 300: 79 % of the fp32 kernel's matrix time) in
-// the arithmetic of edge_ws_f16.h -- both operands as x0 + x1' / 2^11 in fp16,
+// the arithmetic F16x2 of edge_ws_split.h -- both operands as x0 + x1' / 2^11 in fp16,
 // three fp16 MFMAs per 32-wide block, two fp32 accumulators; optionally the
 // 64 -> 128 layer below it as well (reg_layer_f16: 76 % of what is left); the
 // two narrowest layers stay fp32 MFMA in registers (reg_layer).  It belongs to
@@ -24,7 +24,7 @@
 // Range: the hidden activations are clamped at 65504 and flagged from 32768 on
 // like the edge kernel's (`status` bit 0).
 #pragma once
-#include "edge_ws_f16.h"
+#include "edge_ws_split.h"
 #include "pool_ws.h"
 
 namespace pgnn {
@@ -130,7 +130,7 @@ __device__ __forceinline__ void pool_ws2_block(const v4u *const (&wfrag)[3],
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int kb = 0; kb < 4; ++kb) {
-    // term-major as in edge_ws2_body: w1' of this block is requested under
+    // term-major as in F16x2::mma_block: w1' of this block is requested under
     // the first term, w0 of the next block under the last
 #pragma unroll
     for (int t = 0; t < NTB; ++t) w1[t] = frag(kb, t, 1);
@@ -192,11 +192,7 @@ __device__ __forceinline__ void pool_ws2_body(const PoolWsArgs &a,
   // index chain one tile ahead (pool_ws_body)
   bool nxt_ok = e_first + n < E;
   int2 nxt = e2[nxt_ok ? e_first + n : 0];
-  int nxt_k;
-  {
-    const int d0 = nxt_ok ? nxt.y : 0;
-    nxt_k = a.kp[((unsigned)d0 < (unsigned)a.num_segments) ? d0 : 0];
-  }
+  int nxt_k = pool_kp_of(a, nxt_ok, nxt);
   for (int64_t tile = tile_first;; ++tile) {
     const bool fin = tile >= tile_last;
     const int64_t e0 = tile * 16;
@@ -220,7 +216,7 @@ __device__ __forceinline__ void pool_ws2_body(const PoolWsArgs &a,
       const int my_k = nxt_k;
       nxt_ok = tile + 1 < tile_last && e0 + 16 + n < E;
       nxt = e2[nxt_ok ? e0 + 16 + n : 0];
-      v4f x[1];
+      v4f x[1];  // the gather of pool_ws_body
       x[0] = (v4f){0.f, 0.f, 0.f, 0.f};
       if (ok) {
 #pragma unroll
@@ -246,10 +242,7 @@ __device__ __forceinline__ void pool_ws2_body(const PoolWsArgs &a,
         reg_layer<4, 8>(a.l2, lane, h2, h3);
       __builtin_amdgcn_sched_barrier(0);
       pool_split_f16<4>(h3, X0, X1, gmax);
-      {
-        const int dn = nxt_ok ? nxt.y : 0;
-        nxt_k = a.kp[((unsigned)dn < (unsigned)a.num_segments) ? dn : 0];
-      }
+      nxt_k = pool_kp_of(a, nxt_ok, nxt);
       const int prev = __builtin_amdgcn_update_dpp(run.cur_d, my_d,
                                                    0x111 /*row_shr:1*/, 0xF, 0xF,
                                                    false);
@@ -288,38 +281,16 @@ __global__ __launch_bounds__(64 * kWsWaves) void pool_ws_f16x2_kernel(
   float *bias_lds = reinterpret_cast<float *>(wl + KB * NT * 2 * 64);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  {
-    const v4u *__restrict__ src = reinterpret_cast<const v4u *>(a.wp);
-    constexpr int PER = (KB * NT * 2 + kWsWaves - 1) / kWsWaves;
-    v4u tmp[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int f = wave + i * kWsWaves;
-      tmp[i] = src[(size_t)(f < KB * NT * 2 ? f : 0) * 64 + lane];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int f = wave + i * kWsWaves;
-      if (f < KB * NT * 2) wl[(size_t)f * 64 + lane] = tmp[i];
-    }
-    if ((int)threadIdx.x < 16 * NT)
-      bias_lds[threadIdx.x] = a.wp[(size_t)KB * NT * 2 * 256 + threadIdx.x];
-  }
+  ws_stage<(KB * NT * 2 + kWsWaves - 1) / kWsWaves>(
+      a, wl, KB * NT * 2, [](int f) { return (size_t)f; },
+      (size_t)KB * NT * 2 * 256, 0, NT, bias_lds, wave, lane);
   __syncthreads();
-  int64_t n_edges = a.n_edges;
-  if (a.n_dev) {
-    const int64_t nd = *a.n_dev;
-    n_edges = nd < n_edges ? nd : n_edges;
-  }
+  const int64_t n_edges = ws_edge_count(a.n_edges, a.n_dev);
   const int64_t n_wt = (n_edges + 15) / 16;
   const int64_t nw = (int64_t)gridDim.x * kWsWaves;
   const int64_t wi = (int64_t)blockIdx.x * kWsWaves + wave;
-  int64_t span = n_wt;
-  int64_t pool = a.sched ? span * a.pool_pct / 100 : 0;
-  if (span - pool < 2 * nw) pool = 0;
-  span -= pool;
-  const int64_t pool_first = span;
+  const int64_t pool = ws_pool_size(n_wt, a.sched, a.pool_pct, 2, nw);
+  const int64_t span = n_wt - pool;  // the pool begins behind the static part
   int64_t tile_first = span * wi / nw;
   int64_t tile_last = span * (wi + 1) / nw;
   u32 gmax = 0;
@@ -327,28 +298,14 @@ __global__ __launch_bounds__(64 * kWsWaves) void pool_ws_f16x2_kernel(
     pool_ws2_body<L2F16>(a, wl, bias_lds, tile_first, tile_last, lane, n_edges,
                          gmax);
     if (pool == 0) break;
-    int c = 0;
-    if (lane == 0)
-      c = __hip_atomic_fetch_add(&a.sched[2], a.chunk, __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
-    c = __builtin_amdgcn_readfirstlane(c);
+    const int c = ws_pool_claim(&a.sched[2], a.chunk, lane);
     if (c >= pool) break;
-    tile_first = pool_first + c;
+    tile_first = span + c;
     tile_last = tile_first + a.chunk < n_wt ? tile_first + a.chunk : n_wt;
   }
   if (status && ((gmax & 0xffffu) >= 0x7800u || (gmax >> 16) >= 0x7800u))
     atomicOr(status, 1);
-  if (a.sched && lane == 0) {
-    const int total = (int)gridDim.x * kWsWaves;
-    const int done = __hip_atomic_fetch_add(&a.sched[1], 1, __ATOMIC_ACQ_REL,
-                                            __HIP_MEMORY_SCOPE_AGENT);
-    if (done == total - 1) {
-      __hip_atomic_store(&a.sched[2], 0, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&a.sched[1], 0, __ATOMIC_RELEASE,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  ws_pool_rearm(a.sched, 1, lane);
 }
 
 }  // namespace pgnn

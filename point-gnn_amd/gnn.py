@@ -664,13 +664,13 @@ EDGE_INPUT_TAP = None
 #               its kernel variants);
 #   'bf16x3' -- SECONDARY: both operands split exactly into three bf16 parts,
 #               six bf16 MFMAs per block accumulated in fp32
-#               (csrc/edge_ws_bf16.h, pgnn_edge_mlp_scatter_max_bf16x3_fwd):
+#               (csrc/edge_ws_split.h, pgnn_edge_mlp_scatter_max_bf16x3_fwd):
 #               agrees with 'f32' to fp32 rounding noise, ~1.7x faster.  Falls
 #               back to 'f32' where the kernel does not apply (few edges,
 #               other layer shapes).
 #   'f16x2'  -- SECONDARY: both operands as TWO fp16 values (22 significand
 #               bits, round to nearest), three fp16 MFMAs per block
-#               (csrc/edge_ws_f16.h, pgnn_edge_mlp_scatter_max_f16x2_fwd):
+#               (csrc/edge_ws_split.h, pgnn_edge_mlp_scatter_max_f16x2_fwd):
 #               not exact -- the stage's distance to float64 grows by a few per
 #               cent -- ~3x faster than 'f32'.  Activations are clamped at
 #               65504; the kernel flags frames in which one could reach 32768 and

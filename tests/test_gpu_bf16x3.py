@@ -1,7 +1,7 @@
 """The SECONDARY arithmetics of the per-edge layer on the matrix pipe's 16-bit
-formats: 'bf16x3' (csrc/edge_ws_bf16.h: both operands of the 300x300 / 256x256
+formats: 'bf16x3' (csrc/edge_ws_split.h: both operands of the 300x300 / 256x256
 product split exactly into three bf16 parts, the six products of combined order
-<= 2 accumulated in fp32) and 'f16x2' (csrc/edge_ws_f16.h: both operands as two
+<= 2 accumulated in fp32) and 'f16x2' (csrc/edge_ws_split.h: both operands as two
 fp16 values, 22 significand bits, three products; with it the wide last layer
 of PointSetPooling's point MLP runs in the same representation,
 csrc/pool_ws_f16.h).

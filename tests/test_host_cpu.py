@@ -474,7 +474,7 @@ def test_variable_scope_is_thread_local():
 
 
 def test_bf16x3_weight_image_is_an_exact_split():
-    """pgnn_pack_fc_bf16x3 (host side of csrc/edge_ws_bf16.h): the three bf16
+    """pgnn_pack_fc_bf16x3 (host side of csrc/edge_ws_split.h): the three bf16
     parts of every weight sum to the fp32 weight EXACTLY, sit where the
     kernel's A-operand layout expects them ([kb][t][part][lane][8]), pad with
     zeros, and the bias follows in fp32."""
@@ -512,7 +512,7 @@ def test_bf16x3_weight_image_is_an_exact_split():
 
 
 def test_f16x2_weight_images_natural_and_accumulator_order():
-    """pgnn_pack_fc_f16x2 / _acc (host side of csrc/edge_ws_f16.h and
+    """pgnn_pack_fc_f16x2 / _acc (host side of csrc/edge_ws_split.h and
     pool_ws_f16.h): w0 = fp16(w), w1' = fp16((w - w0) 2^11) at
     [kb][t][part][lane][8]; the two entries differ only in WHICH row of W slot
     (g, j) of a block holds -- 8 g + j, or the order in which a lane of the

@@ -2,7 +2,7 @@
 // Loop body: one v_mfma (5 independent accumulators in rotation) followed by K
 // filler instructions of one kind on independent registers; 1 or 2 waves per
 // SIMD; cycles per loop trip from s_memtime (shader clock).  K = 0 is the bare
-// MFMA rate.  The edge kernel of csrc/edge_ws_bf16.h wants ~2.4 VALU passes,
+// MFMA rate.  The Bf16x3 edge kernel of csrc/edge_ws_split.h wants ~2.4 VALU passes,
 // 0.5 ds_read_b128 and 0.13 global loads hidden behind every 16x16x32 MFMA;
 // this table says which of them are.
 //   hipcc -O3 --offload-arch=gfx950 tools/micro/mfma_mix.hip -o /tmp/mfma_mix && /tmp/mfma_mix

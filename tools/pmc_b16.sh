@@ -23,7 +23,7 @@ for set in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_M
   python - "$db" >> $RES <<'EOF2'
 import sqlite3, sys
 db = sqlite3.connect(sys.argv[1])
-for pat, tag in (("edge_ws_bf16x3_kernel", "b16x3"), ("edge_ws_f16x2_kernel", "f16x2"),
+for pat, tag in (("edge_ws_split_kernel<pgnn::Bf16x3", "b16x3"), ("edge_ws_split_kernel<pgnn::F16x2", "f16x2"),
                  ("edge_ws_kernel", "f32")):
     rows = db.execute("select counter_name, count(*), avg(value) from counters_collection "
                       "where kernel_name like ? group by counter_name", ("%" + pat + "%",))
