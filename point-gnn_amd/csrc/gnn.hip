@@ -1052,6 +1052,32 @@ int launch_rows8(const Plan &p, int64_t n_rows, const RowsArgs &ra,
 
 void ws_balance(EdgeWsArgs &a, int cus, const double *cost);  // below
 
+// Row slices of a weights-stationary launch on `cus` CUs: `ws_xcds` when it
+// divides them, else one per XCD.
+inline int ws_slices(int cus) {
+  return (g_ws_xcds >= 1 && cus % g_ws_xcds == 0) ? g_ws_xcds : 8;
+}
+
+// Can launch_edge_ws / ws_partition split `nt` column tiles into groups of at
+// most `ntmax` on `cus` CUs?  Every `*_applies` predicate asks this with the
+// slices the launch will use, so that "applies" and "launches" are ONE
+// decision: a geometry the partition cannot serve (e.g. 64 CUs in 32 slices
+// for three column groups) takes the LDS-tile kernel or is declined like any
+// other unsupported shape, and nothing is enqueued before the answer is known.
+bool ws_feasible(int nt, int ntmax, int cus) {
+  const int groups = (nt + ntmax - 1) / ntmax;
+  const int per_slice = cus / ws_slices(cus);
+  if (groups > kWsMaxGroups || per_slice < groups) return false;
+  const int base = nt / groups, extra = nt % groups;
+  if (base < ntmax - 1 || base + (extra ? 1 : 0) > ntmax) return false;
+  int used = 0;
+  for (int g = 0; g < groups; ++g) {
+    const int cnt = per_slice * (base + (g < extra ? 1 : 0)) / nt;
+    used += cnt < 1 ? 1 : cnt;
+  }
+  return used <= per_slice;
+}
+
 // Weights-stationary edge kernel (edge_ws.h): one workgroup per CU, the column
 // tiles in groups that fit the LDS, the 16-row tiles in one slice per XCD.
 // ROWS: `ea.P` holds one ready input row per edge (pool_split.h).
@@ -1078,7 +1104,7 @@ int launch_edge_ws(const LayerDev &L, const EdgeArgs &ea, int64_t n_edges,
   a.ldo = sa.ldo;
   a.num_segments = sa.num_segments;
   a.sorted = sa.sorted;
-  a.xcds = (g_ws_xcds >= 1 && cus % g_ws_xcds == 0) ? g_ws_xcds : 8;
+  a.xcds = ws_slices(cus);
   a.prio = g_ws_prio;
   a.ts = (long long *)g_mlp_ts;
   a.sched = (g_ws_pool_pct > 0 && a.xcds <= kWsMaxSlices) ? sched : nullptr;
@@ -1156,6 +1182,7 @@ bool edge_ws_applies(const Plan &p, int64_t n_edges, int cus) {
   const LayerDev &L = p.chain.l[0];
   if (p.chain.n != 1 || L.kq != L.nt || (L.nt != 19 && L.nt != 16)) return false;
   if (cus < 64 || cus % 8 != 0) return false;
+  if (!ws_feasible(L.nt, L.nt == 19 ? 7 : 8, cus)) return false;
   // one column group of the layer's fragments + bias must fit a workgroup's
   // LDS (133 KiB / 128 KiB on gfx950's 160 KiB); a device with less takes the
   // LDS-tile kernel
@@ -1254,6 +1281,7 @@ bool pool_split_applies(const Plan &p, int64_t n_edges, int cus) {
       c.l[4].nt != 32)
     return false;
   if (cus < 64 || cus % 8 != 0) return false;
+  if (!ws_feasible(c.l[4].nt, 8, cus)) return false;
   if ((size_t)16 * 8 * 1024 + 16 * 16 * sizeof(float) > device_max_lds())
     return false;
   if (g_mlp_debug & 16384) return true;
@@ -1283,6 +1311,9 @@ int launch_pool_split(const Plan &p, const PoolArgs &pa, int64_t n_edges,
   a.a4_out = hidden;
   a.ld4 = kPoolSplitHidden;
   a.slices = 8;
+  // (pool_split_applies has asked already; nothing is enqueued before this)
+  PGNN_REQUIRE(ws_feasible(p.chain.l[4].nt, 8, cus), PGNN_E_UNSUPPORTED,
+               "pool_split: too few CUs for the column groups");
   const size_t lds = (size_t)8 * 16 * 1024 + 16 * 16 * sizeof(float);
   auto kern = pool_hidden_kernel;
   {
@@ -1791,6 +1822,7 @@ int edge_split_fwd_impl(const float *P, const float *Q, int64_t ld_pq,
   // 150 KiB of weights per workgroup: otherwise the caller runs the fp32 entry
   if (!((kb == 10 && nt == 19) || (kb == 8 && nt == 16)) || cus < 64 ||
       cus % 8 != 0 ||
+      !ws_feasible(nt, kb == 10 ? H::kNtMax10 : H::kNtMax8, cus) ||
       (!g_b16_force &&
        expected(de, edges_cap) < (int64_t)16 * 2 * kWsWaves * cus) ||
       // (the kernel addresses P / Q rows with 32-bit byte offsets)
@@ -1824,7 +1856,7 @@ int edge_split_fwd_impl(const float *P, const float *Q, int64_t ld_pq,
   a.ldo = ld_out;
   a.num_segments = vertices_cap;
   a.sorted = edges_sorted & 1;
-  a.xcds = (g_ws_xcds >= 1 && cus % g_ws_xcds == 0) ? g_ws_xcds : 8;
+  a.xcds = ws_slices(cus);
   a.prio = H::prio();
   if (Arith::kRangeGuard) a.nv_dev = dk.dev;
   if (kb == 10)

@@ -130,6 +130,11 @@ def _worst(got, ref):
     return w
 
 
+# (batch, params, float64 gradients, oracle losses) per config: the oracle run
+# is the expensive part and the geometry cases below hold to the same one
+_ORACLE = {}
+
+
 @pytest.mark.parametrize("name", list(CASES))
 def test_full_size_gradient_matches_mask_matched_oracle(name):
     """The gradient of every variable at the benchmarked batch size, with the
@@ -225,3 +230,96 @@ def test_full_size_gradient_matches_mask_matched_oracle(name):
         for n, e in errs.items():
             assert e <= BAR, "%s %s: max-entry rel err %.3g" % (mode, n, e)
     assert len(set(losses.values())) == 1, losses
+    _ORACLE[name] = (batch, params, g64, loss)
+
+
+def _oracle(name, dev):
+    """The cached oracle of the test above, or -- this test run alone -- the
+    same computation: the Python forward's decisions replayed in float64."""
+    import torch
+    from pointgnn_amd import train
+    if name not in _ORACLE:
+        cfg = configs.get_config(name)
+        preset, n_frames, hi = CASES[name]
+        batch = _batch(cfg, preset, n_frames, hi, dev)
+        params = weights.init_params(cfg, seed=5, bias_scale=0.1)
+        tr = train.Trainer(cfg, params=params, device=dev)
+        tr.native = False
+        tr.forward(*batch[:4])
+        masks = device_decisions(tr, cfg)
+        del tr
+        torch.cuda.empty_cache()
+        dec = to.Decisions(masks)
+        loss, g64, _ = to.step_gradients(params, cfg, [batch], decisions=[dec])
+        assert dec.pos == len(masks)
+        _ORACLE[name] = (batch, params, g64, loss)
+    return _ORACLE[name]
+
+
+def _native_step(cfg, params, batch, dev):
+    """One native car step on the current stream -> (the workspace as the
+    forward left it, gradients, losses).  The workspace holds everything the
+    forward saves for the backward -- the per-edge rows (`rows_out`), the
+    gathered hidden rows (`h1_out`), the pooling activations -- and is zeroed
+    first, so that two forwards can be compared byte for byte."""
+    from pointgnn_amd import train
+    t2 = train.Trainer(cfg, params=params, device=dev)
+    t2.native, t2.sparse_adjoint = True, True
+    t2.forward(*batch[:4])            # sizes the workspace
+    assert t2._native is not None
+    t2._native_ws.zero_()
+    t2.forward(*batch[:4])
+    saved = t2._native_ws.clone()
+    out = t2.train_step(batch, apply=False)
+    got = t2.grad_dict()
+    del t2
+    return saved, got, (out['cls_loss'], out['loc_loss'])
+
+
+def test_native_step_at_other_ws_geometries():
+    """The training forward forms of the weights-stationary kernels
+    (edge_ws_kernel<.., EMIT> with rows_out / h1_out, pool_ws_kernel<true>) at
+    two more grid geometries: `ws_reserve` = 64 (192 workgroups) and 4 row
+    slices on a 240-CU stream.  The bar of the test above, unchanged -- every
+    variable within 1e-5 of max|g64| of the mask-matched float64 oracle --,
+    and what the forward saves is bit-equal to the default geometry's: rows,
+    hidden rows and activations are per-row quantities with no cross-wave
+    sums."""
+    import torch
+    from pointgnn_amd import _lib
+    import _ws_cases as wc
+    dev = torch.device("cuda")
+    _lib.load()
+    name = "car_auto_T3"
+    cfg = configs.get_config(name)
+    batch, params, g64, loss = _oracle(name, dev)
+    base, _, base_losses = _native_step(cfg, params, batch, dev)
+    again, _, _ = _native_step(cfg, params, batch, dev)
+    assert again.numel() == base.numel() and torch.equal(again, base), \
+        "the forward's workspace is not reproducible at ONE geometry"
+    del again
+    for geo in (wc.DEFAULT._replace(reserve=64),
+                wc.DEFAULT._replace(stream=240, xcds=4)):
+        with wc.masked_stream(geo.stream) as stream, wc.tunables(geo), \
+                torch.cuda.stream(stream):
+            assert _fused_forwards_accept(dev, batch, 300) == (0, 0), \
+                "the fused rows-writing forwards decline at %s" % wc.geo_id(geo)
+            saved, got, losses = _native_step(cfg, params, batch, dev)
+            stream.synchronize()
+            same = saved.numel() == base.numel() and torch.equal(saved, base)
+            del saved
+        errs = {n: float(np.abs(got[n] - r).max() / (np.abs(r).max() + 1e-12))
+                for n, r in g64.items()}
+        wn = max(errs, key=errs.get)
+        print("[fullsize] %s native step at %s: worst entry error %.3g (%s); "
+              "losses %r; saved activations %s" % (
+                  name, wc.geo_id(geo), errs[wn], wn, losses,
+                  "bit-equal" if same else "DIFFER"), flush=True)
+        assert same, "saved activations differ at %s" % wc.geo_id(geo)
+        for i, key in enumerate(('cls_loss', 'loc_loss')):
+            assert abs(losses[i] - loss[key]) <= 1e-5 * abs(loss[key]), (
+                wc.geo_id(geo), key, losses[i], loss[key])
+        assert losses == base_losses, (wc.geo_id(geo), losses, base_losses)
+        for n, e in errs.items():
+            assert e <= BAR, "%s %s: max-entry rel err %.3g" % (
+                wc.geo_id(geo), n, e)
