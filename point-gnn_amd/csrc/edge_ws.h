@@ -41,6 +41,7 @@
 // counts: the gathers of one slice (all column groups) meet in one L2.
 #pragma once
 #include "mlp_engine.h"
+#include "ws_partition.h"  // kWsMaxGroups, kWsMaxSlices, the geometry arithmetic
 
 namespace pgnn {
 
@@ -52,9 +53,7 @@ namespace pgnn {
 #define PGNN_WS_SCHED 2
 #endif
 
-constexpr int kWsMaxGroups = 4;
 constexpr int kWsWaves = 8;
-constexpr int kWsMaxSlices = 8;
 // sched_ws layout: [0], [1] as in the LDS-tile kernels (claims, done count),
 // then one pool counter per (row slice, column group)
 constexpr int kWsSchedInts = 2 + kWsMaxSlices * kWsMaxGroups;

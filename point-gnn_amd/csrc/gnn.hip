@@ -240,6 +240,19 @@ __device__ __forceinline__ void consume_rows(const float *__restrict__ stage,
   }
 }
 
+// An opaque per-tile copy of the lane id for the tile loops of the 8-wave
+// K-row kernels: the per-lane weight addresses of every layer are loop
+// invariant, and hoisted out of the tile loop they cost ~100 VGPRs -- spills
+// in the capacity-form kernels.
+__device__ __forceinline__ int opaque_lane(int lane_id) {
+  int lane;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(lane_id));
+  return lane;
+}
+
+// (The rest of that frame -- the n_dev clamp, rows_valid --, the lowest() fill
+// of agg and the "stage + residual -> y, refill the tile" block stay copies in
+// each kernel: as helpers they change the vertex_* kernels' instruction streams.)
 // ---- 16-row tiles of the 8-wave K-row kernels (512 threads) -------------------
 // Thread (r = tid >> 5, c0 = tid & 31) owns columns c0, c0 + 32, ... of tile row
 // r: ten steps cover the 320 columns a layer pass can produce.  Every phase
@@ -849,6 +862,20 @@ __global__ void offset_apply_kernel(const float *__restrict__ xyz,
 }
 
 // ---- host side -----------------------------------------------------------------
+// One launch: the kernel's dynamic-LDS limit raised to `lds` where it uses any,
+// the launch, its error.
+template <class... Params, class... Args>
+int launch_lds(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds,
+               hipStream_t stream, const Args &...args) {
+  if (lds) {
+    const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+}
+
 struct Plan {
   ChainDev chain;
   int tile_floats_per_row;  // max ld over in-place activations
@@ -913,10 +940,6 @@ int launch_fused(const Plan &p, int64_t n_rows, const RowsArgs &ra,
   PGNN_REQUIRE(lds <= 160 * 1024, PGNN_E_UNSUPPORTED,
                "mlp: layer too wide for the LDS tile");
   auto kern = fused_mlp_kernel<MSUB, PRO>;
-  {
-    const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
-    if (lrc) return lrc;
-  }
   const int64_t n_tiles = (n_rows + ROWS - 1) / ROWS;
   int per_cu = (int)((160 * 1024) / lds);
   if (per_cu > g_mlp_blocks_per_cu) per_cu = g_mlp_blocks_per_cu;
@@ -938,12 +961,10 @@ int launch_fused(const Plan &p, int64_t n_rows, const RowsArgs &ra,
     fprintf(stderr, "[pgnn] fused<%d,%d> lds=%zu per_cu=%d occupancy_api=%d (%d) grid=%lld tiles=%lld\n",
             MSUB, PRO, lds, per_cu, nb, (int)e, (long long)grid, (long long)n_tiles);
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, p.chain,
-                     n_rows, ra, pa, ea, sa, stage_off, g_mlp_debug,
-                     (long long *)g_mlp_ts, sched, n_static, n_dev,
-                     g_mlp_pool_pct);
-  PGNN_HIP(hipGetLastError());
-  return 0;
+  return launch_lds(kern, dim3((unsigned)grid), dim3(256), lds, stream, p.chain,
+                    n_rows, ra, pa, ea, sa, stage_off, g_mlp_debug,
+                    (long long *)g_mlp_ts, sched, n_static, n_dev,
+                    g_mlp_pool_pct);
 }
 
 // Plain row MLP (PRO_ROWS) for SMALL row counts: 16-row tiles and EIGHT waves
@@ -971,11 +992,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void rows_mlp_kernel(
   const int64_t n_tiles = (n_rows + ROWS - 1) / ROWS;
   const int ld0 = lds_ld(16 * chain.l[0].kq);
   for (int64_t tile_id = blockIdx.x; tile_id < n_tiles; tile_id += gridDim.x) {
-    // (an opaque per-tile copy of the lane id: the per-lane weight addresses
-    // of every layer are loop invariant, and hoisted out of the tile loop they
-    // cost ~100 VGPRs -- spills in the capacity-form kernels)
-    int lane;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(lane_id));
+    const int lane = opaque_lane(lane_id);
     const int64_t row0 = tile_id * ROWS;
     const int rows_valid =
         (int)((n_rows - row0 < ROWS) ? (n_rows - row0) : ROWS);
@@ -1036,296 +1053,12 @@ int launch_rows8(const Plan &p, int64_t n_rows, const RowsArgs &ra,
   const size_t lds = plan_lds_bytes(p, 16);
   PGNN_REQUIRE(lds <= 160 * 1024, PGNN_E_UNSUPPORTED,
                "mlp: layer too wide for the LDS tile");
-  auto kern = rows_mlp_kernel<TAPS>;
-  {
-    const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
-    if (lrc) return lrc;
-  }
   const int64_t n_tiles = (n_rows + 15) / 16;
   const int stage_off = p.stage_cols ? 16 * p.tile_floats_per_row : -1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(grid_tiles > 0 ? grid_tiles : n_tiles)),
-                     dim3(64 * kRowsWaves), lds,
-                     stream, p.chain, n_rows, ra, stage_off, n_dev);
-  PGNN_HIP(hipGetLastError());
-  return 0;
-}
-
-void ws_balance(EdgeWsArgs &a, int cus, const double *cost);  // below
-
-// Row slices of a weights-stationary launch on `cus` CUs: `ws_xcds` when it
-// divides them, else one per XCD.
-inline int ws_slices(int cus) {
-  return (g_ws_xcds >= 1 && cus % g_ws_xcds == 0) ? g_ws_xcds : 8;
-}
-
-// Can launch_edge_ws / ws_partition split `nt` column tiles into groups of at
-// most `ntmax` on `cus` CUs?  Every `*_applies` predicate asks this with the
-// slices the launch will use, so that "applies" and "launches" are ONE
-// decision: a geometry the partition cannot serve (e.g. 64 CUs in 32 slices
-// for three column groups) takes the LDS-tile kernel or is declined like any
-// other unsupported shape, and nothing is enqueued before the answer is known.
-bool ws_feasible(int nt, int ntmax, int cus) {
-  const int groups = (nt + ntmax - 1) / ntmax;
-  const int per_slice = cus / ws_slices(cus);
-  if (groups > kWsMaxGroups || per_slice < groups) return false;
-  const int base = nt / groups, extra = nt % groups;
-  if (base < ntmax - 1 || base + (extra ? 1 : 0) > ntmax) return false;
-  int used = 0;
-  for (int g = 0; g < groups; ++g) {
-    const int cnt = per_slice * (base + (g < extra ? 1 : 0)) / nt;
-    used += cnt < 1 ? 1 : cnt;
-  }
-  return used <= per_slice;
-}
-
-// Weights-stationary edge kernel (edge_ws.h): one workgroup per CU, the column
-// tiles in groups that fit the LDS, the 16-row tiles in one slice per XCD.
-// ROWS: `ea.P` holds one ready input row per edge (pool_split.h).
-template <int KQ, int NTMAX, bool ROWS = false>
-int launch_edge_ws(const LayerDev &L, const EdgeArgs &ea, int64_t n_edges,
-                   const SegArgs &sa, int cus, int32_t *sched,
-                   hipStream_t stream, float *rows_out = nullptr,
-                   int64_t ld_rows = 0, float *h1_out = nullptr,
-                   const int32_t *n_dev = nullptr) {
-  EdgeWsArgs a = {};
-  a.n_dev = n_dev;
-  a.rows_out = rows_out;
-  a.ld_rows = ld_rows;
-  a.h1_out = h1_out;
-  a.P = ea.P;
-  a.Q = ea.Q;
-  a.ldv4 = (int)(ea.ldpq >> 2);
-  a.edges = ea.edges;
-  a.n_edges = n_edges;
-  a.wp = L.wp;
-  a.nt = L.nt;
-  a.relu_from = L.relu_from;
-  a.out = sa.out;
-  a.ldo = sa.ldo;
-  a.num_segments = sa.num_segments;
-  a.sorted = sa.sorted;
-  a.xcds = ws_slices(cus);
-  a.prio = g_ws_prio;
-  a.ts = (long long *)g_mlp_ts;
-  a.sched = (g_ws_pool_pct > 0 && a.xcds <= kWsMaxSlices) ? sched : nullptr;
-  PGNN_HIP((hipError_t)arm_sched(a.sched, stream));
-  a.pool_pct = g_ws_pool_pct;
-  a.chunk = g_ws_chunk;
-  a.groups = (L.nt + NTMAX - 1) / NTMAX;
-  const int per_slice = cus / a.xcds;
-  PGNN_REQUIRE(a.groups <= kWsMaxGroups && per_slice >= a.groups,
-               PGNN_E_UNSUPPORTED, "edge_ws: too few CUs for the column groups");
-  // column tiles as evenly as possible (C = 300: 7/6/6, C = 256: 8/8) and the
-  // slice's workgroups in proportion (largest remainder)
-  const int base = L.nt / a.groups, extra = L.nt % a.groups;
-  int size[kWsMaxGroups], cnt[kWsMaxGroups], frac[kWsMaxGroups], used = 0;
-  a.tile0[0] = 0;
-  for (int g = 0; g < a.groups; ++g) {
-    size[g] = base + (g < extra ? 1 : 0);
-    a.tile0[g + 1] = a.tile0[g] + size[g];
-    cnt[g] = per_slice * size[g] / L.nt;
-    if (cnt[g] < 1) cnt[g] = 1;
-    frac[g] = per_slice * size[g] % L.nt;
-    used += cnt[g];
-  }
-  PGNN_REQUIRE(base >= NTMAX - 1 && base + (extra ? 1 : 0) <= NTMAX &&
-                   used <= per_slice,
-               PGNN_E_UNSUPPORTED, "edge_ws: column tiles do not group");
-  while (used < per_slice) {
-    int best = 0;
-    for (int g = 1; g < a.groups; ++g)
-      if (frac[g] > frac[best]) best = g;
-    ++cnt[best];
-    frac[best] = -1;
-    ++used;
-  }
-  a.wg0[0] = 0;
-  for (int g = 0; g < a.groups; ++g) a.wg0[g + 1] = a.wg0[g] + cnt[g];
-  {
-    // relative cost of a row tile: 4 KQ MFMAs of 32 cycles per column tile +
-    // ~1.9k cycles of gather VALU / running max per tile (tools/ws_timeline.py)
-    double cost[kWsMaxGroups];
-    for (int g = 0; g < a.groups; ++g) cost[g] = 128.0 * KQ * size[g] + 1900.0;
-    // (measured on the fp32 kernel: 977 vs 971 us, no gain -- its 12/10/10
-    // imbalance is smaller than the noise between its XCDs; the split-bf16
-    // kernel, 9/8/8/7 for 5/5/5/4 tiles, gains 1.7 %.  ws_balance = 2 turns it
-    // on here too.)
-    if (g_ws_balance >= 2) ws_balance(a, cus, cost);
-  }
-  const size_t lds = (size_t)KQ * NTMAX * 1024 + 16 * NTMAX * sizeof(float);
-  if constexpr (!ROWS) {
-    if (rows_out) {  // training forward: the rows are written as well
-      auto kern = edge_ws_kernel<KQ, NTMAX, true>;
-      const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
-      if (lrc) return lrc;
-      hipLaunchKernelGGL(kern, dim3((unsigned)(per_slice * a.xcds)),
-                         dim3(64 * kWsWaves), lds, stream, a);
-      PGNN_HIP(hipGetLastError());
-      return 0;
-    }
-  }
-  auto kern = edge_ws_kernel<KQ, NTMAX, false, ROWS>;
-  {
-    const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
-    if (lrc) return lrc;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(per_slice * a.xcds)),
-                     dim3(64 * kWsWaves), lds, stream, a);
-  PGNN_HIP(hipGetLastError());
-  return 0;
-}
-
-// the shapes edge_ws.h is instantiated for: one square layer of 19 (C = 300)
-// or 16 (C = 256) column tiles, a CU count that splits into 8 slices
-bool edge_ws_applies(const Plan &p, int64_t n_edges, int cus) {
-  if (g_mlp_debug & 2048) return false;
-  const LayerDev &L = p.chain.l[0];
-  if (p.chain.n != 1 || L.kq != L.nt || (L.nt != 19 && L.nt != 16)) return false;
-  if (cus < 64 || cus % 8 != 0) return false;
-  if (!ws_feasible(L.nt, L.nt == 19 ? 7 : 8, cus)) return false;
-  // one column group of the layer's fragments + bias must fit a workgroup's
-  // LDS (133 KiB / 128 KiB on gfx950's 160 KiB); a device with less takes the
-  // LDS-tile kernel
-  if ((size_t)L.kq * (L.nt == 19 ? 7 : 8) * 1024 + 16 * 8 * sizeof(float) >
-      device_max_lds())
-    return false;
-  if (g_mlp_debug & 4096) return true;
-  // below ~2 tiles per wave the fixed cost (133 KiB of weights per workgroup
-  // into LDS) is not amortised
-  return n_edges >= (int64_t)16 * 2 * kWsWaves * cus;
-}
-
-// Weights-stationary pooling kernel (pool_ws.h): car's 4-32-64-128-300 chain.
-bool pool_ws_applies(const Plan &p, int64_t n_edges, int cus) {
-  if (g_mlp_debug & (8192 | 1024)) return false;
-  const ChainDev &c = p.chain;
-  if (c.n != 4 || c.l[0].kq != 1 || c.l[0].nt != 2 || c.l[1].nt != 4 ||
-      c.l[2].nt != 8 || c.l[3].kq != 8 || c.l[3].nt != 19)
-    return false;
-  if (cus < 8) return false;
-  if ((size_t)8 * 19 * 1024 + 16 * 19 * sizeof(float) > device_max_lds())
-    return false;
-  if (g_mlp_debug & 16384) return true;
-  return n_edges >= (int64_t)16 * 2 * kWsWaves * cus;
-}
-
-int launch_pool_ws(const Plan &p, const PoolArgs &pa, int64_t n_edges,
-                   const SegArgs &sa, int cus, int32_t *sched,
-                   hipStream_t stream, float *const *acts = nullptr,
-                   int64_t ld4 = 0, const int32_t *n_dev = nullptr) {
-  PoolWsArgs a = {};
-  a.n_dev = n_dev;
-  if (acts) {
-    a.a1_out = acts[0];
-    a.a2_out = acts[1];
-    a.a3_out = acts[2];
-    a.a4_out = acts[3];
-    a.ld4 = ld4;
-  }
-  a.feat = pa.feat;
-  a.nfeat = pa.nfeat;
-  a.xyz = pa.xyz;
-  a.kp = pa.kp;
-  a.edges = pa.edges;
-  a.n_edges = n_edges;
-  a.l0 = p.chain.l[0];
-  a.l1 = p.chain.l[1];
-  a.l2 = p.chain.l[2];
-  a.wp = p.chain.l[3].wp;
-  a.kq = p.chain.l[3].kq;
-  a.nt = p.chain.l[3].nt;
-  a.relu_from = p.chain.l[3].relu_from;
-  a.out = sa.out;
-  a.ldo = sa.ldo;
-  a.num_segments = sa.num_segments;
-  a.sorted = sa.sorted;
-  a.prio = g_ws_prio;
-  a.ts = (long long *)g_mlp_ts;
-  a.sched = g_ws_pool_pct > 0 ? sched : nullptr;
-  PGNN_HIP((hipError_t)arm_sched(a.sched, stream));
-  a.pool_pct = g_ws_pool_pct;
-  a.chunk = 1;
-  const size_t lds = (size_t)8 * 19 * 1024 + 16 * 19 * sizeof(float);
-  if (acts) {  // training forward: the layers' activations are written too
-    auto kern = pool_ws_kernel<true>;
-    const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
-    if (lrc) return lrc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)cus), dim3(64 * kWsWaves), lds,
-                       stream, a);
-    PGNN_HIP(hipGetLastError());
-    return 0;
-  }
-  auto kern = pool_ws_kernel<false>;
-  {
-    const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
-    if (lrc) return lrc;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)cus), dim3(64 * kWsWaves), lds, stream,
-                     a);
-  PGNN_HIP(hipGetLastError());
-  return 0;
-}
-
-// Split pooling stage (pool_split.h): ped_cyl's 4-32-64-128-256-512 chain, the
-// hidden rows [n_edges, 256] through a caller-provided workspace.  (car's
-// 4-32-64-128-300 chain on the same form -- 64 -> 128 in LDS, rows [n_edges,
-// 128], 128 -> 300 as edge_ws_kernel<8, 7, ROWS> -- measured 310 us against
-// pool_ws.h's 296: its last layer is only 8 K groups deep, so a row tile
-// carries half the MFMA work over the same per-tile cost; not kept.)
-constexpr int kPoolSplitHidden = 256;
-bool pool_split_applies(const Plan &p, int64_t n_edges, int cus) {
-  if (g_mlp_debug & (8192 | 1024)) return false;
-  const ChainDev &c = p.chain;
-  if (c.n != 5 || c.l[0].kq != 1 || c.l[0].nt != 2 || c.l[1].nt != 4 ||
-      c.l[2].nt != 8 || c.l[3].kq != 8 || c.l[3].nt != 16 || c.l[4].kq != 16 ||
-      c.l[4].nt != 32)
-    return false;
-  if (cus < 64 || cus % 8 != 0) return false;
-  if (!ws_feasible(c.l[4].nt, 8, cus)) return false;
-  if ((size_t)16 * 8 * 1024 + 16 * 16 * sizeof(float) > device_max_lds())
-    return false;
-  if (g_mlp_debug & 16384) return true;
-  return n_edges >= (int64_t)16 * 2 * kWsWaves * cus;
-}
-
-int launch_pool_split(const Plan &p, const PoolArgs &pa, int64_t n_edges,
-                      const SegArgs &sa, int cus, int32_t *sched,
-                      hipStream_t stream, const int32_t *n_dev, float *hidden) {
-  PoolWsArgs a = {};
-  a.n_dev = n_dev;
-  a.feat = pa.feat;
-  a.nfeat = pa.nfeat;
-  a.xyz = pa.xyz;
-  a.kp = pa.kp;
-  a.edges = pa.edges;
-  a.n_edges = n_edges;
-  a.l0 = p.chain.l[0];
-  a.l1 = p.chain.l[1];
-  a.l2 = p.chain.l[2];
-  a.wp = p.chain.l[3].wp;
-  a.kq = p.chain.l[3].kq;
-  a.nt = p.chain.l[3].nt;
-  a.relu_from = p.chain.l[3].relu_from;
-  a.num_segments = sa.num_segments;
-  a.prio = g_ws_prio;
-  a.a4_out = hidden;
-  a.ld4 = kPoolSplitHidden;
-  a.slices = 8;
-  // (pool_split_applies has asked already; nothing is enqueued before this)
-  PGNN_REQUIRE(ws_feasible(p.chain.l[4].nt, 8, cus), PGNN_E_UNSUPPORTED,
-               "pool_split: too few CUs for the column groups");
-  const size_t lds = (size_t)8 * 16 * 1024 + 16 * 16 * sizeof(float);
-  auto kern = pool_hidden_kernel;
-  {
-    const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
-    if (lrc) return lrc;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)cus), dim3(64 * kPoolHWaves), lds,
-                     stream, a);
-  PGNN_HIP(hipGetLastError());
-  const EdgeArgs ea = {hidden, nullptr, kPoolSplitHidden, pa.edges};
-  return launch_edge_ws<16, 8, true>(p.chain.l[4], ea, n_edges, sa, cus, sched,
-                                     stream, nullptr, 0, nullptr, n_dev);
+  return launch_lds(rows_mlp_kernel<TAPS>,
+                    dim3((unsigned)(grid_tiles > 0 ? grid_tiles : n_tiles)),
+                    dim3(64 * kRowsWaves), lds, stream, p.chain, n_rows, ra,
+                    stage_off, n_dev);
 }
 
 int fill_lowest(float *out, int64_t count, hipStream_t stream) {
@@ -1370,13 +1103,13 @@ int fill_lowest_rows(float *out, int64_t ld, int64_t rows, const Dyn &d,
   int64_t blocks = (expected(d, rows) * ld + 1023) / 1024;
   if (blocks < 1) blocks = 1;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(fill_rows_dyn_kernel, dim3((unsigned)blocks), dim3(256), 0,
-                     stream, out, ld, rows, d.dev);
-  PGNN_HIP(hipGetLastError());
-  return 0;
+  return launch_lds(fill_rows_dyn_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                    stream, out, ld, rows, d.dev);
 }
 
 }  // namespace
+
+#include "ws_launch.h"  // the weights-stationary kernels' host side
 
 namespace {
 // workgroups for a capacity-form launch of a 16-row-tile kernel that strides
@@ -1551,8 +1284,7 @@ int pooling_fwd_impl(const float *point_features, int32_t n_feat,
       pa.reg_hidden = 1;
   }
   {
-    int cus = stream_cu_count(stream);
-    if (g_ws_reserve > 0 && cus - g_ws_reserve >= 64) cus -= g_ws_reserve;
+    const int cus = ws_cus(stream);
     // (capacity form: chosen on the expected count; the two kernels give
     // bit-identical maxima, tests/test_gpu_parity.py)
     if (pool_ws_applies(p, expected(de, n_edges), cus))
@@ -1610,8 +1342,7 @@ int edge_fwd_impl(const float *P, const float *Q, int64_t ld_pq, int32_t width,
   EdgeArgs ea = {P, Q, ld_pq, edges};
   SegArgs sa = {out, ld_out, num_vertices, edges_sorted & 1};
   {
-    int cus = stream_cu_count(stream);
-    if (g_ws_reserve > 0 && cus - g_ws_reserve >= 64) cus -= g_ws_reserve;
+    const int cus = ws_cus(stream);
     if (edge_ws_applies(p, expected(de, n_edges), cus)) {
       if (p.chain.l[0].nt == 19)
         return launch_edge_ws<19, 7>(p.chain.l[0], ea, n_edges, sa, cus,
@@ -1630,238 +1361,6 @@ int edge_fwd_impl(const float *P, const float *Q, int64_t ld_pq, int32_t width,
                                      sched_ws, de.dev);
   return launch_fused<2, PRO_EDGE>(p, n_edges, ra, pa, ea, sa, stream, sched_ws,
                                    de.dev);
-}
-}  // namespace
-
-namespace {
-// Balanced workgroup counts over the whole chip for the column groups whose
-// tile counts are a.tile0 (see EdgeWsArgs::balanced).  cost[g] = relative time
-// of one row tile in group g (its MFMA issue + the per-tile fixed part).
-void ws_balance(EdgeWsArgs &a, int cus, const double *cost) {
-  const int per_slice = cus / a.xcds, total = per_slice * a.xcds;
-  a.balanced = 0;
-  if (a.xcds > kWsMaxSlices || a.groups < 2 || a.sched) return;
-  double sum = 0;
-  for (int g = 0; g < a.groups; ++g) sum += cost[g];
-  // largest-remainder share of `total` workgroups
-  int n[kWsMaxGroups], used = 0;
-  double frac[kWsMaxGroups];
-  for (int g = 0; g < a.groups; ++g) {
-    const double x = total * cost[g] / sum;
-    n[g] = (int)x;
-    if (n[g] < a.xcds) n[g] = a.xcds;  // at least one per slice
-    frac[g] = x - n[g];
-    used += n[g];
-  }
-  while (used < total) {
-    int best = 0;
-    for (int g = 1; g < a.groups; ++g)
-      if (frac[g] > frac[best]) best = g;
-    ++n[best];
-    frac[best] -= 1.0;
-    ++used;
-  }
-  if (used != total) return;  // (cannot happen for the shipped shapes)
-  // per slice: cumulative rounding, then repair each slice's sum to per_slice
-  int prev[kWsMaxGroups] = {0, 0, 0, 0};
-  for (int s = 0; s < a.xcds; ++s) {
-    int c[kWsMaxGroups], tot = 0;
-    for (int g = 0; g < a.groups; ++g) {
-      const int cum = (int)((int64_t)n[g] * (s + 1) / a.xcds);
-      c[g] = cum - prev[g];
-      tot += c[g];
-    }
-    // (the last slice closes every group exactly; earlier slices borrow from /
-    // lend to the group that is furthest ahead / behind its share)
-    for (int guard = 0; tot != per_slice && guard < 64; ++guard) {
-      int pick = -1;
-      double worst = 0;
-      for (int g = 0; g < a.groups; ++g) {
-        const double ideal = (double)n[g] * (s + 1) / a.xcds;
-        const double ahead = prev[g] + c[g] - ideal;
-        if (tot > per_slice ? (c[g] > 1 && (pick < 0 || ahead > worst))
-                            : (prev[g] + c[g] < n[g] &&
-                               (pick < 0 || -ahead > worst))) {
-          pick = g;
-          worst = tot > per_slice ? ahead : -ahead;
-        }
-      }
-      if (pick < 0) return;
-      c[pick] += tot > per_slice ? -1 : 1;
-      tot += tot > per_slice ? -1 : 1;
-    }
-    if (tot != per_slice) return;
-    a.swg0[s][0] = 0;
-    for (int g = 0; g < a.groups; ++g) {
-      a.sbase[s][g] = (short)prev[g];
-      a.swg0[s][g + 1] = (short)(a.swg0[s][g] + c[g]);
-      prev[g] += c[g];
-    }
-  }
-  for (int g = 0; g < a.groups; ++g) {
-    if (prev[g] != n[g]) return;
-    a.n_wg[g] = n[g];
-  }
-  a.balanced = 1;
-}
-}  // namespace
-
-namespace {
-// column groups of a weights-stationary launch: tiles as evenly as possible,
-// the slice's workgroups in proportion (largest remainder) -- launch_edge_ws
-int ws_partition(EdgeWsArgs &a, int nt, int ntmax, int cus) {
-  a.groups = (nt + ntmax - 1) / ntmax;
-  const int per_slice = cus / a.xcds;
-  PGNN_REQUIRE(a.groups <= kWsMaxGroups && per_slice >= a.groups,
-               PGNN_E_UNSUPPORTED, "edge_ws: too few CUs for the column groups");
-  const int base = nt / a.groups, extra = nt % a.groups;
-  int size[kWsMaxGroups], cnt[kWsMaxGroups], frac[kWsMaxGroups], used = 0;
-  a.tile0[0] = 0;
-  for (int g = 0; g < a.groups; ++g) {
-    size[g] = base + (g < extra ? 1 : 0);
-    a.tile0[g + 1] = a.tile0[g] + size[g];
-    cnt[g] = per_slice * size[g] / nt;
-    if (cnt[g] < 1) cnt[g] = 1;
-    frac[g] = per_slice * size[g] % nt;
-    used += cnt[g];
-  }
-  PGNN_REQUIRE(base >= ntmax - 1 && base + (extra ? 1 : 0) <= ntmax &&
-                   used <= per_slice,
-               PGNN_E_UNSUPPORTED, "edge_ws: column tiles do not group");
-  while (used < per_slice) {
-    int best = 0;
-    for (int g = 1; g < a.groups; ++g)
-      if (frac[g] > frac[best]) best = g;
-    ++cnt[best];
-    frac[best] = -1;
-    ++used;
-  }
-  a.wg0[0] = 0;
-  for (int g = 0; g < a.groups; ++g) a.wg0[g + 1] = a.wg0[g] + cnt[g];
-  return 0;
-}
-
-// Host side of an arithmetic of edge_ws_split.h: its name in messages, the
-// largest column group per K depth (KB = 10: 19 tiles in 5/5/5/4 resp. 7/6/6;
-// KB = 8: 16 in 4 x 4 resp. 6/5/5), the relative cost of a row tile per group
-// -- mfma cycles of a column tile (60 resp. 30 MFMAs of 16 cycles at KB = 10) +
-// the part of the gather / split / segmented max that does not hide behind
-// them (bf16x3: round 4's 2.4k cycles, when nothing did; the interleaved body
-// leaves about a third) --, and whether the waves raise their priority
-// outside the MFMA loop (g_ws_prio)
-template <class Arith>
-struct SplitHost;
-template <>
-struct SplitHost<Bf16x3> {
-  static constexpr const char *kName = "edge_bf16x3";
-  static constexpr int kNtMax10 = 5, kNtMax8 = 5;
-  static constexpr double kTileCost = 960.0, kRowCost = 2400.0;
-  static int prio() { return g_ws_prio; }
-};
-template <>
-struct SplitHost<F16x2> {
-  static constexpr const char *kName = "edge_f16x2";
-  static constexpr int kNtMax10 = 7, kNtMax8 = 6;
-  static constexpr double kTileCost = 480.0, kRowCost = 1600.0;
-  static int prio() { return 0; }
-};
-
-template <class Arith>
-std::string split_msg(const char *what) {
-  return std::string(SplitHost<Arith>::kName) + ": " + what;
-}
-
-template <class Arith, int KB, int NTMAX>
-int launch_edge_ws_split(EdgeWsArgs &a, int nt, int cus, int32_t *status,
-                         hipStream_t stream) {
-  using H = SplitHost<Arith>;
-  const int rc = ws_partition(a, nt, NTMAX, cus);
-  if (rc) return rc;
-  {
-    double cost[kWsMaxGroups];
-    for (int g = 0; g < a.groups; ++g)
-      cost[g] = H::kTileCost * KB / 10 * (a.tile0[g + 1] - a.tile0[g]) + H::kRowCost;
-    if (g_ws_balance) ws_balance(a, cus, cost);
-  }
-  const size_t lds =
-      (size_t)KB * NTMAX * Arith::kParts * 1024 + 16 * NTMAX * sizeof(float);
-  PGNN_REQUIRE(lds <= device_max_lds(), PGNN_E_UNSUPPORTED,
-               split_msg<Arith>("column group does not fit the LDS").c_str());
-  auto kern = edge_ws_split_kernel<Arith, KB, NTMAX>;
-  const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
-  if (lrc) return lrc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(cus / a.xcds * a.xcds)),
-                     dim3(64 * kWsWaves), lds, stream, a, status);
-  PGNN_HIP(hipGetLastError());
-  return 0;
-}
-
-// the two split-precision edge entries; status: F16x2's range flag (null for
-// Bf16x3, whose kernel has no guard)
-template <class Arith>
-int edge_split_fwd_impl(const float *P, const float *Q, int64_t ld_pq,
-                        int32_t width, const int32_t *edges, int64_t edges_cap,
-                        int32_t vertices_cap, const void *image, int32_t n_out,
-                        int32_t relu_from, int32_t edges_sorted, float *out,
-                        int64_t ld_out, int32_t *status,
-                        const pgnn_dyn_count *n_edges,
-                        const pgnn_dyn_count *num_vertices, hipStream_t stream) {
-  using H = SplitHost<Arith>;
-  PGNN_REQUIRE(edges_cap >= 0 && vertices_cap >= 0 && width > 0 && n_out > 0 &&
-                   image,
-               PGNN_E_INVALID, split_msg<Arith>("bad argument").c_str());
-  const Dyn de = dyn_of(n_edges), dk = dyn_of(num_vertices);
-  const int kq = (width + 15) / 16, nt = (n_out + 15) / 16;
-  const int kb = (width + 31) / 32;
-  PGNN_REQUIRE(ld_pq == 16 * kq && ld_out >= 16 * nt, PGNN_E_INVALID,
-               split_msg<Arith>("ld_pq / ld_out do not match the padded widths")
-                   .c_str());
-  int cus = stream_cu_count(stream);
-  if (g_ws_reserve > 0 && cus - g_ws_reserve >= 64) cus -= g_ws_reserve;
-  // the shapes the kernel is instantiated for, and enough rows to amortise
-  // 150 KiB of weights per workgroup: otherwise the caller runs the fp32 entry
-  if (!((kb == 10 && nt == 19) || (kb == 8 && nt == 16)) || cus < 64 ||
-      cus % 8 != 0 ||
-      !ws_feasible(nt, kb == 10 ? H::kNtMax10 : H::kNtMax8, cus) ||
-      (!g_b16_force &&
-       expected(de, edges_cap) < (int64_t)16 * 2 * kWsWaves * cus) ||
-      // (the kernel addresses P / Q rows with 32-bit byte offsets)
-      (int64_t)vertices_cap * ld_pq * 4 >= ((int64_t)1 << 32))
-    return PGNN_E_UNSUPPORTED;  // (no message: an expected answer)
-  if (vertices_cap == 0) return 0;
-  PGNN_REQUIRE(out != nullptr, PGNN_E_INVALID,
-               split_msg<Arith>("null output").c_str());
-  if (!(edges_sorted & 2)) {
-    const int rc = fill_lowest_rows(out, ld_out, vertices_cap, dk, stream);
-    if (rc) return rc;
-  }
-  if (edges_cap == 0) return 0;
-  PGNN_REQUIRE(P && Q && edges, PGNN_E_INVALID,
-               split_msg<Arith>("null input").c_str());
-  PGNN_REQUIRE(((uintptr_t)P % 16 == 0) && ((uintptr_t)Q % 16 == 0) &&
-                   ((uintptr_t)image % 16 == 0),
-               PGNN_E_INVALID,
-               split_msg<Arith>("P / Q / image must be 16-byte aligned").c_str());
-  EdgeWsArgs a = {};
-  a.P = P;
-  a.Q = Q;
-  a.ldv4 = (int)(ld_pq >> 2);
-  a.edges = edges;
-  a.n_edges = edges_cap;
-  a.n_dev = de.dev;
-  a.wp = reinterpret_cast<const float *>(image);
-  a.nt = nt;
-  a.relu_from = relu_from;
-  a.out = out;
-  a.ldo = ld_out;
-  a.num_segments = vertices_cap;
-  a.sorted = edges_sorted & 1;
-  a.xcds = ws_slices(cus);
-  a.prio = H::prio();
-  if (Arith::kRangeGuard) a.nv_dev = dk.dev;
-  if (kb == 10)
-    return launch_edge_ws_split<Arith, 10, H::kNtMax10>(a, nt, cus, status, stream);
-  return launch_edge_ws_split<Arith, 8, H::kNtMax8>(a, nt, cus, status, stream);
 }
 }  // namespace
 
@@ -1910,8 +1409,7 @@ extern "C" int pgnn_point_set_pooling_f16x2_fwd(
   Plan p;
   int rc = make_plan(layers, n_layers, n_feat + 3, p);
   if (rc) return rc;
-  int cus = stream_cu_count(stream);
-  if (g_ws_reserve > 0 && cus - g_ws_reserve >= 64) cus -= g_ws_reserve;
+  const int cus = ws_cus(stream);
   // the shapes and sizes of pool_ws_kernel (car's 4-32-64-128-300 chain)
   if (!g_f16_pool ||
       !pool_ws_applies(p, g_b16_force ? ((int64_t)1 << 40)
@@ -1931,38 +1429,19 @@ extern "C" int pgnn_point_set_pooling_f16x2_fwd(
                    (uintptr_t)hidden_image % 16 == 0,
                PGNN_E_INVALID,
                "pooling_f16x2: the images must be 16-byte aligned");
-  PoolWsArgs a = {};
-  a.n_dev = de.dev;
-  a.feat = point_features;
-  a.nfeat = n_feat;
-  a.xyz = point_xyz;
-  a.kp = keypoint_indices;
-  a.edges = edges;
-  a.n_edges = edges_cap;
-  a.l0 = p.chain.l[0];
-  a.l1 = p.chain.l[1];
-  a.l2 = p.chain.l[2];
+  const PoolArgs pa = {point_features, n_feat, point_xyz, keypoint_indices, edges};
+  const SegArgs sa = {out, ld_out, keypoints_cap, edges_sorted & 1};
+  // (pool_ws_applies: the last layer is 8 K groups by 19 column tiles)
+  PoolWsArgs a = pool_ws_args(p, pa, edges_cap, de.dev, keypoints_cap);
   a.wp = reinterpret_cast<const float *>(last_image);
-  a.kq = 8;
-  a.nt = 19;
-  a.relu_from = p.chain.l[3].relu_from;
-  a.out = out;
-  a.ldo = ld_out;
-  a.num_segments = keypoints_cap;
-  a.sorted = edges_sorted & 1;
-  a.sched = g_ws_pool_pct > 0 ? sched_ws : nullptr;
-  PGNN_HIP((hipError_t)arm_sched(a.sched, stream));
-  a.pool_pct = g_ws_pool_pct;
-  a.chunk = 1;
-  const size_t lds = (size_t)4 * 19 * 2 * 1024 + 16 * 19 * sizeof(float);
   a.l2_f16 = g_f16_pool >= 2 ? nullptr : hidden_image;
-  auto kern = a.l2_f16 ? pool_ws_f16x2_kernel<true> : pool_ws_f16x2_kernel<false>;
-  rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
+  rc = pool_ws_out(a, sa, sched_ws, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)cus), dim3(64 * kWsWaves), lds, stream,
-                     a, status);
-  PGNN_HIP(hipGetLastError());
-  return 0;
+  const size_t lds = (size_t)4 * 19 * 2 * 1024 + 16 * 19 * sizeof(float);
+  return launch_lds(a.l2_f16 ? pool_ws_f16x2_kernel<true>
+                             : pool_ws_f16x2_kernel<false>,
+                    dim3((unsigned)cus), dim3(64 * kWsWaves), lds, stream, a,
+                    status);
   PGNN_GUARD_END
 }
 
@@ -2009,8 +1488,7 @@ extern "C" int pgnn_point_set_pooling_workspace_bytes(
   Plan p;
   int rc = make_plan(layers, n_layers, n_feat + 3, p);
   if (rc) return rc;
-  int cus = device_cu_count();
-  if (g_ws_reserve > 0 && cus - g_ws_reserve >= 64) cus -= g_ws_reserve;
+  const int cus = ws_cus(device_cu_count());  // (no stream to ask here)
   const int64_t n_sel =
       (edges_hint > 0 && edges_hint < edges_cap) ? edges_hint : edges_cap;
   if (pool_split_applies(p, n_sel, cus))
@@ -2173,11 +1651,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void vertex_pre_edge_kernel(
   // expected count and strides
   for (int64_t row0 = (int64_t)blockIdx.x * ROWS; row0 < n_rows;
        row0 += STRIDE ? (int64_t)gridDim.x * ROWS : n_rows) {
-    // (an opaque per-tile copy of the lane id: the per-lane weight addresses
-    // of every layer are loop invariant, and hoisted out of the tile loop they
-    // cost ~100 VGPRs -- spills in the capacity-form kernels)
-    int lane;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(lane_id));
+    const int lane = opaque_lane(lane_id);
   const int rows_valid =
       (int)((n_rows - row0 < ROWS) ? (n_rows - row0) : ROWS);
   const int kc = 16 * pl.kq;
@@ -2309,11 +1783,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void vertex_update_pre_edge_kernel
   if (tsw && threadIdx.x == 0) tsw[15] = __builtin_amdgcn_s_memrealtime();
   for (int64_t row0 = (int64_t)blockIdx.x * ROWS; row0 < n_rows;
        row0 += STRIDE ? (int64_t)gridDim.x * ROWS : n_rows) {
-    // (an opaque per-tile copy of the lane id: the per-lane weight addresses
-    // of every layer are loop invariant, and hoisted out of the tile loop they
-    // cost ~100 VGPRs -- spills in the capacity-form kernels)
-    int lane;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(lane_id));
+    const int lane = opaque_lane(lane_id);
     const int rows_valid =
         (int)((n_rows - row0 < ROWS) ? (n_rows - row0) : ROWS);
     stamp();  // 0: entry
@@ -2400,11 +1870,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void vertex_mlp2_kernel(
   const int ld_b = lds_ld(kcb);
   for (int64_t row0 = (int64_t)blockIdx.x * ROWS; row0 < n_rows;
        row0 += STRIDE ? (int64_t)gridDim.x * ROWS : n_rows) {
-    // (an opaque per-tile copy of the lane id: the per-lane weight addresses
-    // of every layer are loop invariant, and hoisted out of the tile loop they
-    // cost ~100 VGPRs -- spills in the capacity-form kernels)
-    int lane;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(lane_id));
+    const int lane = opaque_lane(lane_id);
     const int rows_valid =
         (int)((n_rows - row0 < ROWS) ? (n_rows - row0) : ROWS);
     KrowPre pre;
@@ -2463,27 +1929,29 @@ __global__ __launch_bounds__(64 * kRowsWaves) void vertex_mlp2_kernel(
 }  // namespace
 
 namespace {
-int pre_edge_impl(
-    const float *h, int64_t ld_h, int32_t c, const float *xyz,
-    const pgnn_fc_layer *offset_layers, int32_t n_offset_layers,
-    const pgnn_fc_layer *p_layer, const float *wx, int64_t n_vertices, float *P,
-    float *Q, int64_t ld_pq, float *agg, int64_t ld_agg, hipStream_t stream,
-    const Dyn &dk) {
-  PGNN_REQUIRE(n_vertices >= 0 && c > 0 && ld_h >= c && n_offset_layers >= 0 &&
-                   n_offset_layers <= PGNN_MAX_LAYERS && p_layer,
-               PGNN_E_INVALID, "vertex_pre_edge: bad argument");
-  if (n_vertices == 0) return 0;
-  PGNN_REQUIRE(h && xyz && wx && P && Q && (!agg || ld_agg > 0), PGNN_E_INVALID,
-               "vertex_pre_edge: null pointer");
+// What the two entries that end in pre_edge_tail share: the P layer, the offset
+// chain with the LDS scratch its activations need, and the kernel's arguments
+// but h / ld_h.  name: the entry's, for the messages; kq_max: the widest
+// [h | x] (16-column groups) the entry's kernel can hold, 0 = no limit of its
+// own.
+int plan_pre_edge(const char *name, int32_t c, const float *xyz,
+                  const pgnn_fc_layer *offset_layers, int32_t n_offset_layers,
+                  const pgnn_fc_layer *p_layer, const float *wx,
+                  int64_t n_vertices, float *P, float *Q, int64_t ld_pq,
+                  float *agg, int64_t ld_agg, const Dyn &dk, int kq_max,
+                  ChainDev &off, LayerDev &pl, PreEdgeArgs &a) {
+  const auto msg = [name](const char *what) { return std::string(name) + what; };
   Plan pp;
   int rc = make_plan(p_layer, 1, c + 3, pp);
   if (rc) return rc;
-  const LayerDev pl = pp.chain.l[0];
+  pl = pp.chain.l[0];
   PGNN_REQUIRE(p_layer->k_in == c + 3 && pl.nt <= kMaxTilesPerPass &&
                    ld_pq == 16 * pl.nt,
                PGNN_E_INVALID,
-               "vertex_pre_edge: P layer must be [c+3 -> n], ld_pq = padded n");
-  ChainDev off = {};
+               msg(": P layer must be [c+3 -> n], ld_pq = padded n").c_str());
+  PGNN_REQUIRE(kq_max == 0 || pl.kq <= kq_max, PGNN_E_UNSUPPORTED,
+               msg(": more than 317 features").c_str());
+  off = {};
   int scratch_ld = lds_ld(16);
   if (n_offset_layers > 0) {
     Plan po;
@@ -2494,7 +1962,8 @@ int pre_edge_impl(
                      offset_layers[n_offset_layers - 1].n_out >= 3 &&
                      off.l[0].kq <= pl.kq &&
                      off.l[n_offset_layers - 1].nt <= kMaxTilesPerPass,
-                 PGNN_E_INVALID, "vertex_pre_edge: offset chain must be [c -> ... -> 3]");
+                 PGNN_E_INVALID,
+                 msg(": offset chain must be [c -> ... -> 3]").c_str());
     for (int i = 0; i < n_offset_layers; ++i) {
       const int ld = lds_ld(16 * off.l[i].nt);
       if (ld > scratch_ld) scratch_ld = ld;
@@ -2502,9 +1971,6 @@ int pre_edge_impl(
         scratch_ld = lds_ld(16 * off.l[i].kq);
     }
   }
-  PreEdgeArgs a;
-  a.h = h;
-  a.ld_h = ld_h;
   a.c = c;
   a.xyz = xyz;
   a.wx = wx;
@@ -2517,19 +1983,38 @@ int pre_edge_impl(
   a.ld_agg = ld_agg;
   a.ld_tile = lds_ld(16 * pl.kq);
   a.ld_scratch = scratch_ld;
+  return 0;
+}
+
+int pre_edge_impl(
+    const float *h, int64_t ld_h, int32_t c, const float *xyz,
+    const pgnn_fc_layer *offset_layers, int32_t n_offset_layers,
+    const pgnn_fc_layer *p_layer, const float *wx, int64_t n_vertices, float *P,
+    float *Q, int64_t ld_pq, float *agg, int64_t ld_agg, hipStream_t stream,
+    const Dyn &dk) {
+  PGNN_REQUIRE(n_vertices >= 0 && c > 0 && ld_h >= c && n_offset_layers >= 0 &&
+                   n_offset_layers <= PGNN_MAX_LAYERS && p_layer,
+               PGNN_E_INVALID, "vertex_pre_edge: bad argument");
+  if (n_vertices == 0) return 0;
+  PGNN_REQUIRE(h && xyz && wx && P && Q && (!agg || ld_agg > 0), PGNN_E_INVALID,
+               "vertex_pre_edge: null pointer");
+  ChainDev off;
+  LayerDev pl;
+  PreEdgeArgs a;
+  const int rc = plan_pre_edge("vertex_pre_edge", c, xyz, offset_layers,
+                               n_offset_layers, p_layer, wx, n_vertices, P, Q,
+                               ld_pq, agg, ld_agg, dk, 0, off, pl, a);
+  if (rc) return rc;
+  a.h = h;
+  a.ld_h = ld_h;
   const size_t lds =
       (size_t)16 * (a.ld_tile + a.ld_scratch + lds_ld(16 * pl.nt)) * 4;
   PGNN_REQUIRE(lds <= 160 * 1024, PGNN_E_UNSUPPORTED,
                "vertex_pre_edge: layer too wide for the LDS tile");
-  auto kern = dk.dev ? vertex_pre_edge_kernel<true> : vertex_pre_edge_kernel<false>;
-  {
-    const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
-    if (lrc) return lrc;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)dyn_grid_tiles(dk, n_vertices)),
-                     dim3(64 * kRowsWaves), lds, stream, off, pl, a);
-  PGNN_HIP(hipGetLastError());
-  return 0;
+  return launch_lds(
+      dk.dev ? vertex_pre_edge_kernel<true> : vertex_pre_edge_kernel<false>,
+      dim3((unsigned)dyn_grid_tiles(dk, n_vertices)), dim3(64 * kRowsWaves), lds,
+      stream, off, pl, a);
 }
 }  // namespace
 
@@ -2589,67 +2074,24 @@ int update_pre_edge_impl(
                    16 * pf.chain.l[n_front - 1].nt < c + 16,
                PGNN_E_INVALID,
                "vertex_update_pre_edge: front chain must produce c features");
-  Plan pp;
-  rc = make_plan(p_layer, 1, c + 3, pp);
-  if (rc) return rc;
-  const LayerDev pl = pp.chain.l[0];
-  PGNN_REQUIRE(p_layer->k_in == c + 3 && pl.nt <= kMaxTilesPerPass &&
-                   ld_pq == 16 * pl.nt,
-               PGNN_E_INVALID,
-               "vertex_update_pre_edge: P layer must be [c+3 -> n], ld_pq = "
-               "padded n");
-  PGNN_REQUIRE(pl.kq <= kMaxTilesPerPass, PGNN_E_UNSUPPORTED,
-               "vertex_update_pre_edge: more than 317 features");
-  ChainDev off = {};
-  int scratch_ld = lds_ld(16);
-  if (n_offset_layers > 0) {
-    Plan po;
-    rc = make_plan(offset_layers, n_offset_layers, c, po);
-    if (rc) return rc;
-    off = po.chain;
-    PGNN_REQUIRE(offset_layers[0].k_in == c &&
-                     offset_layers[n_offset_layers - 1].n_out >= 3 &&
-                     off.l[0].kq <= pl.kq &&
-                     off.l[n_offset_layers - 1].nt <= kMaxTilesPerPass,
-                 PGNN_E_INVALID,
-                 "vertex_update_pre_edge: offset chain must be [c -> ... -> 3]");
-    for (int i = 0; i < n_offset_layers; ++i) {
-      const int ld = lds_ld(16 * off.l[i].nt);
-      if (ld > scratch_ld) scratch_ld = ld;
-      if (i > 0 && lds_ld(16 * off.l[i].kq) > scratch_ld)
-        scratch_ld = lds_ld(16 * off.l[i].kq);
-    }
-  }
+  ChainDev off;
+  LayerDev pl;
   PreEdgeArgs a;
+  rc = plan_pre_edge("vertex_update_pre_edge", c, xyz, offset_layers,
+                     n_offset_layers, p_layer, wx, n_vertices, P, Q, ld_pq, agg,
+                     ld_agg, dk, kMaxTilesPerPass, off, pl, a);
+  if (rc) return rc;
   a.h = nullptr;  // the tile is filled from the front chain, not from HBM
   a.ld_h = 0;
-  a.c = c;
-  a.xyz = xyz;
-  a.wx = wx;
-  a.n = n_vertices;
-  a.n_dev = dk.dev;
-  a.P = P;
-  a.Q = Q;
-  a.ld_pq = ld_pq;
-  a.agg = agg;
-  a.ld_agg = ld_agg;
-  a.ld_tile = lds_ld(16 * pl.kq);
-  a.ld_scratch = scratch_ld;
   if (f.ld_buf < a.ld_tile) f.ld_buf = a.ld_tile;
   if (f.ld_stage < lds_ld(16 * pl.nt)) f.ld_stage = lds_ld(16 * pl.nt);
   const size_t lds = (size_t)16 * (f.ld_buf + a.ld_scratch + f.ld_stage) * 4;
   PGNN_REQUIRE(lds <= 160 * 1024, PGNN_E_UNSUPPORTED,
                "vertex_update_pre_edge: layers too wide for the LDS tile");
-  auto kern = dk.dev ? vertex_update_pre_edge_kernel<true>
-                     : vertex_update_pre_edge_kernel<false>;
-  {
-    const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
-    if (lrc) return lrc;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)dyn_grid_tiles(dk, n_vertices)),
-                     dim3(64 * kRowsWaves), lds, stream, pf.chain, f, off, pl, a);
-  PGNN_HIP(hipGetLastError());
-  return 0;
+  return launch_lds(dk.dev ? vertex_update_pre_edge_kernel<true>
+                           : vertex_update_pre_edge_kernel<false>,
+                    dim3((unsigned)dyn_grid_tiles(dk, n_vertices)),
+                    dim3(64 * kRowsWaves), lds, stream, pf.chain, f, off, pl, a);
 }
 
 int mlp2_impl(const float *x, int64_t ld_x, int32_t nx,
@@ -2688,16 +2130,10 @@ int mlp2_impl(const float *x, int64_t ld_x, int32_t nx,
   const size_t lds = (size_t)16 * (f.ld_buf + f.ld_stage) * 4;
   PGNN_REQUIRE(lds <= 160 * 1024, PGNN_E_UNSUPPORTED,
                "mlp2: layers too wide for the LDS tile");
-  auto kern = dk.dev ? vertex_mlp2_kernel<true> : vertex_mlp2_kernel<false>;
-  {
-    const int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
-    if (lrc) return lrc;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)dyn_grid_tiles(dk, n_rows)),
-                     dim3(64 * kRowsWaves), lds, stream, pf.chain, f, pb.chain,
-                     ro, n_rows, dk.dev);
-  PGNN_HIP(hipGetLastError());
-  return 0;
+  return launch_lds(dk.dev ? vertex_mlp2_kernel<true> : vertex_mlp2_kernel<false>,
+                    dim3((unsigned)dyn_grid_tiles(dk, n_rows)),
+                    dim3(64 * kRowsWaves), lds, stream, pf.chain, f, pb.chain,
+                    ro, n_rows, dk.dev);
 }
 }  // namespace
 
@@ -2814,8 +2250,7 @@ extern "C" int pgnn_point_set_pooling_rows_fwd(
   const int out_cols = 16 * p.chain.l[n_layers - 1].nt;
   PGNN_REQUIRE(out && ld_out >= out_cols && ld_last >= out_cols && ld_last % 4 == 0,
                PGNN_E_INVALID, "point_set_pooling_rows: bad output");
-  int cus = stream_cu_count(stream);
-  if (g_ws_reserve > 0 && cus - g_ws_reserve >= 64) cus -= g_ws_reserve;
+  const int cus = ws_cus(stream);
   if (n_edges == 0 || num_keypoints == 0 || !pool_ws_applies(p, n_edges, cus))
     return PGNN_E_UNSUPPORTED;
   PGNN_REQUIRE(point_xyz && keypoint_indices && edges && (n_feat == 0 || point_features),
@@ -2859,8 +2294,7 @@ extern "C" int pgnn_edge_mlp_scatter_max_rows_fwd(
   PGNN_REQUIRE(out && ld_out >= out_cols && rows_out && ld_rows >= out_cols &&
                    ld_rows % 4 == 0 && (uintptr_t)rows_out % 16 == 0,
                PGNN_E_INVALID, "edge_mlp_rows: bad output");
-  int cus = stream_cu_count(stream);
-  if (g_ws_reserve > 0 && cus - g_ws_reserve >= 64) cus -= g_ws_reserve;
+  const int cus = ws_cus(stream);
   if (n_edges == 0 || num_vertices == 0 || !edge_ws_applies(p, n_edges, cus))
     return PGNN_E_UNSUPPORTED;  // (no message: an expected answer)
   PGNN_REQUIRE(P && Q && edges, PGNN_E_INVALID, "edge_mlp_rows: null input");
@@ -2895,9 +2329,7 @@ extern "C" int pgnn_offset_apply(const float *xyz, const float *delta,
   const int64_t total = n_rows * ld_q;
   int64_t blocks = (total + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(offset_apply_kernel, dim3((unsigned)blocks), dim3(256), 0,
-                     stream, xyz, delta, ld_delta, n_rows, wx, xyz_out, Q, ld_q);
-  PGNN_HIP(hipGetLastError());
-  return 0;
+  return launch_lds(offset_apply_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                    stream, xyz, delta, ld_delta, n_rows, wx, xyz_out, Q, ld_q);
   PGNN_GUARD_END
 }

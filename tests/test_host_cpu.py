@@ -438,7 +438,8 @@ def test_sched_ws_size_matches_header():
     hdr = open(os.path.join(ROOT, "include", "pointgnn_hip.h")).read()
     m = re.search(r"#define\s+PGNN_SCHED_WS_INTS\s+(\d+)", hdr)
     assert m and int(m.group(1)) == _lib.SCHED_WS_INTS
-    src = open(os.path.join(ROOT, "point-gnn_amd", "csrc", "edge_ws.h")).read()
+    src = open(os.path.join(ROOT, "point-gnn_amd", "csrc",
+                            "ws_partition.h")).read()
     slices = int(re.search(r"kWsMaxSlices\s*=\s*(\d+)", src).group(1))
     groups = int(re.search(r"kWsMaxGroups\s*=\s*(\d+)", src).group(1))
     assert 2 + slices * groups <= _lib.SCHED_WS_INTS
@@ -615,3 +616,160 @@ def test_batch_norm_layers_are_folded_and_training_refuses_them():
         with pytest.raises(NotImplementedError, match="no training path"):
             train.check_trainable_kinds(cfg)
     train.check_trainable_kinds(configs.get_config("car_auto_T3"))
+
+
+# ---- the weights-stationary partition (csrc/ws_partition.h), host only --------
+_WS_WRAPPERS = r"""
+#include "ws_partition.h"
+using namespace pgnn;
+extern "C" {
+int t_sizeof() { return (int)sizeof(WsGeometry); }
+int t_slices(int cus, int ws_xcds) { return ws_slice_count(cus, ws_xcds); }
+int t_feasible(int nt, int ntmax, int cus, int slices) {
+  return ws_feasible(nt, ntmax, cus, slices) ? 1 : 0;
+}
+int t_partition(WsGeometry *g, int nt, int ntmax, int cus, int slices) {
+  return ws_partition(*g, nt, ntmax, cus, slices);
+}
+void t_balance(WsGeometry *g, int cus, const double *cost, int pool) {
+  ws_balance(*g, cus, cost, pool != 0);
+}
+}
+"""
+
+
+def _ws_partition_lib(tmp_path):
+    """csrc/ws_partition.h alone, through the host C++ compiler (g++, else the
+    clang++ hipcc drives): the header must not need HIP."""
+    import shutil
+    import subprocess
+    cands = [shutil.which("g++")]
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(hipcc)))
+    cands += [os.path.join(rocm, "lib", "llvm", "bin", "clang++"),
+              os.path.join(rocm, "llvm", "bin", "clang++")]
+    cxx = next((c for c in cands if c and os.path.exists(c)), None)
+    assert cxx, "no host C++ compiler (g++ or ROCm's clang++) found"
+    src = tmp_path / "ws_partition_test.cpp"
+    src.write_text(_WS_WRAPPERS)
+    so = tmp_path / "libws_partition_test.so"
+    subprocess.check_call([cxx, "-O1", "-std=c++17", "-Wall", "-shared",
+                           "-fPIC", "-I", os.path.join(ROOT, "point-gnn_amd",
+                                                       "csrc"),
+                           "-o", str(so), str(src)])
+    return ctypes.CDLL(str(so))
+
+
+class _WsGeometry(ctypes.Structure):
+    _fields_ = [("groups", ctypes.c_int), ("xcds", ctypes.c_int),
+                ("tile0", ctypes.c_int * 5), ("wg0", ctypes.c_int * 5),
+                ("balanced", ctypes.c_int), ("n_wg", ctypes.c_int * 4),
+                ("swg0", (ctypes.c_short * 5) * 8),
+                ("sbase", (ctypes.c_short * 4) * 8)]
+
+
+def _ws_partition_py(nt, ntmax, cus, slices):
+    """The partition restated: column tiles as evenly as possible in
+    ceil(nt / ntmax) groups, a slice's workgroups in proportion to the tiles,
+    largest remainder, the first maximum wins.  None: cannot be served."""
+    groups = -(-nt // ntmax)
+    per_slice = cus // slices
+    if groups > 4 or per_slice < groups:
+        return None
+    base, extra = divmod(nt, groups)
+    size = [base + (1 if g < extra else 0) for g in range(groups)]
+    if base < ntmax - 1 or max(size) > ntmax:
+        return None
+    cnt = [max(1, per_slice * s // nt) for s in size]
+    frac = [per_slice * s % nt for s in size]
+    if sum(cnt) > per_slice:
+        return None
+    while sum(cnt) < per_slice:
+        best = frac.index(max(frac))
+        cnt[best] += 1
+        frac[best] = -1
+    tile0 = [sum(size[:g]) for g in range(groups + 1)]
+    wg0 = [sum(cnt[:g]) for g in range(groups + 1)]
+    return tile0, wg0
+
+
+def test_ws_partition_header_on_every_geometry(tmp_path):
+    """csrc/ws_partition.h is the one statement of the column-group partition
+    (the `*_applies` predicates and every launcher go through it): on the six
+    (column tiles, largest group) shapes in use x CU counts 8..512 x ws_xcds
+    1..64 its feasibility answer IS the partition's, the partition equals a
+    restatement in Python, and the balanced form keeps its invariants under
+    the five cost models of the callers."""
+    lib = _ws_partition_lib(tmp_path)
+    assert lib.t_sizeof() == ctypes.sizeof(_WsGeometry)
+    lib.t_balance.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                              ctypes.c_int]
+    shapes = [(19, 7), (16, 8), (32, 8), (19, 5), (16, 5), (16, 6)]
+    # relative cost of a row tile of `size` column tiles, per caller:
+    # fp32 at KQ = 19 / 16, bf16x3 at KB = 10 / 8, f16x2 at KB = 10 (gnn.hip's
+    # launchers; f16x2 at KB = 8 is 0.8 of a model already here up to scale)
+    models = [lambda s: 128.0 * 19 * s + 1900.0,
+              lambda s: 128.0 * 16 * s + 1900.0,
+              lambda s: 960.0 * s + 2400.0,
+              lambda s: 960.0 * 8 / 10 * s + 2400.0,
+              lambda s: 480.0 * s + 1600.0]
+    n_cases = n_feasible = n_balanced = 0
+    for nt, ntmax in shapes:
+        for cus in range(8, 513, 8):
+            for ws_xcds in range(1, 65):
+                n_cases += 1
+                slices = lib.t_slices(cus, ws_xcds)
+                assert slices == (ws_xcds if cus % ws_xcds == 0 else 8)
+                g = _WsGeometry()
+                why = lib.t_partition(ctypes.byref(g), nt, ntmax, cus, slices)
+                feasible = lib.t_feasible(nt, ntmax, cus, slices)
+                assert feasible == (1 if why == 0 else 0)
+                want = _ws_partition_py(nt, ntmax, cus, slices)
+                assert (want is not None) == (why == 0), (nt, ntmax, cus, slices)
+                if want is None:
+                    continue
+                n_feasible += 1
+                tile0, wg0 = want
+                assert g.groups == len(tile0) - 1 and g.xcds == slices
+                assert list(g.tile0)[:g.groups + 1] == tile0
+                assert list(g.wg0)[:g.groups + 1] == wg0
+                assert wg0[-1] == cus // slices and tile0[-1] == nt
+                for model in models:
+                    cost = (ctypes.c_double * 4)(*[
+                        model(tile0[i + 1] - tile0[i])
+                        for i in range(g.groups)])
+                    lib.t_balance(ctypes.byref(g), cus, cost, 1)
+                    assert g.balanced == 0          # never with a tile pool
+                    lib.t_balance(ctypes.byref(g), cus, cost, 0)
+                    if not g.balanced:
+                        assert slices > 8 or g.groups < 2, (nt, cus, slices)
+                        continue
+                    n_balanced += 1
+                    per_slice = cus // slices
+                    run = [0] * g.groups
+                    for s in range(slices):
+                        c = [g.swg0[s][i + 1] - g.swg0[s][i]
+                             for i in range(g.groups)]
+                        assert g.swg0[s][0] == 0 and min(c) >= 1
+                        assert sum(c) == per_slice
+                        assert [g.sbase[s][i] for i in range(g.groups)] == run
+                        run = [a + b for a, b in zip(run, c)]
+                    assert run == list(g.n_wg)[:g.groups]
+                    assert sum(run) == per_slice * slices
+    assert n_cases == 24576 and n_feasible == 23601
+    assert n_balanced > 0
+    # the splits the design documents for the whole chip, 256 CUs in 8 slices:
+    # fp32, 7/6/6 tiles: 12/10/10 workgroups in every slice (static)
+    g = _WsGeometry()
+    assert lib.t_partition(ctypes.byref(g), 19, 7, 256, 8) == 0
+    assert list(g.tile0)[:4] == [0, 7, 13, 19]
+    assert list(g.wg0)[:4] == [0, 12, 22, 32]
+    # bf16x3, 5/5/5/4 tiles: 9/8/8/7 workgroups per XCD as the static split,
+    # balanced to 66/66/66/58 over the chip (shares 66.21 x 3 and 57.38: the
+    # 256th workgroup goes to the largest remainder)
+    assert lib.t_partition(ctypes.byref(g), 19, 5, 256, 8) == 0
+    assert list(g.tile0)[:5] == [0, 5, 10, 15, 19]
+    assert list(g.wg0)[:5] == [0, 9, 17, 25, 32]
+    cost = (ctypes.c_double * 4)(*[models[2](s) for s in (5, 5, 5, 4)])
+    lib.t_balance(ctypes.byref(g), 256, cost, 0)
+    assert g.balanced == 1 and list(g.n_wg) == [66, 66, 66, 58]

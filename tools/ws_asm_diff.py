@@ -4,14 +4,17 @@
     hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 \\
           --cuda-device-only -S -I include -I point-gnn_amd/csrc \\
           point-gnn_amd/csrc/gnn.hip -o X.s          (before and after a change)
-    tools/ws_asm_diff.py A.s B.s [kernel-name-substring]
+    tools/ws_asm_diff.py [--all] A.s B.s [kernel-name-substring]
 
-For every *ws*kernel* symbol: `same` when the instruction streams and the
-kernel descriptors agree after renumbering labels, otherwise the register /
-scratch / LDS figures and instruction counts of both sides (and, for the
-kernels that match the substring, a unified diff).  Kernels are paired by
-demangled name; the two split-precision edge kernels are also found under the
-names they had as separate kernels.  Needs c++filt."""
+For every *ws*kernel* symbol -- with --all: for every kernel of the two files,
+the check of a change that must leave the whole device side alone -- `same`
+when the instruction streams and the kernel descriptors agree after
+renumbering labels, otherwise the register / scratch / LDS / kernarg figures
+and instruction counts of both sides (and, for the kernels that match the
+substring, a unified diff).  Kernels are paired by demangled name; the two
+split-precision edge kernels are also found under the names they had as
+separate kernels.  The last line counts the kernels compared; exit status 1
+when any differs.  Needs c++filt."""
 import re
 import subprocess
 import sys
@@ -22,6 +25,10 @@ RENAME = [
     (r"edge_ws_f16x2_kernel<(\d+), (\d+)>", r"edge_ws_split_kernel<pgnn::F16x2, \1, \2>"),
 ]
 COUNT = ["v_mfma", "ds_read", "global_load", "v_pk_"]
+META = (r"\.amdhsa_(next_free_vgpr|next_free_sgpr|accum_offset|"
+        r"group_segment_fixed_size|private_segment_fixed_size|kernarg_size)\s+(\S+)")
+ARGS = [x for x in sys.argv[1:] if x != "--all"]
+ALL = "--all" in sys.argv[1:]
 
 
 def kernels(path):
@@ -31,13 +38,13 @@ def kernels(path):
         s = line.strip()
         if name is None:
             m = re.match(r"^(_Z\w+):", line)
-            if m and ("ws_" in m.group(1)) and "kernel" in m.group(1):
+            if m and "kernel" in m.group(1) and (ALL or "ws_" in m.group(1)):
                 name, body = m.group(1), []
             m = re.match(r"\.amdhsa_kernel\s+(\S+)", s)
             if m:
                 cur = m.group(1)
                 meta[cur] = {}
-            m = re.match(r"\.amdhsa_(next_free_vgpr|next_free_sgpr|accum_offset|group_segment_fixed_size|private_segment_fixed_size)\s+(\S+)", s)
+            m = re.match(META, s)
             if m and meta:
                 meta[cur][m.group(1)] = m.group(2)
             continue
@@ -48,7 +55,7 @@ def kernels(path):
         if not s or s.startswith(";"):
             continue
         if s.startswith(".amdhsa_") or s.startswith(".end_amdhsa") or s.startswith(".section") or s == ".text":
-            m = re.match(r"\.amdhsa_(next_free_vgpr|next_free_sgpr|accum_offset|group_segment_fixed_size|private_segment_fixed_size|kernarg_size)\s+(\S+)", s)
+            m = re.match(META, s)
             if m:
                 meta.setdefault(name, {})[m.group(1)] = m.group(2)
             continue
@@ -59,7 +66,7 @@ def kernels(path):
                          capture_output=True, text=True).stdout.split("\n")
     res = {}
     for n, d in zip(names, dem):
-        d = re.sub(r"^void ", "", d)
+        d = re.sub(r"^void ", "", d).replace("(anonymous namespace)", "{anon}")
         d = re.sub(r"\(.*$", "", d)
         for a, b in RENAME:
             d = re.sub(a, b, d)
@@ -83,21 +90,22 @@ def counts(body):
     return c
 
 
-a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
-show = len(sys.argv) > 3
+a, b = kernels(ARGS[0]), kernels(ARGS[1])
+show = len(ARGS) > 2
 bad = 0
 for k in sorted(set(a) | set(b)):
     if k not in a or k not in b:
         print("ONLY in", "A" if k in a else "B", k)
         bad += 1
         continue
-    same = a[k][0] == b[k][0]
+    same = a[k][0] == b[k][0] and a[k][1] == b[k][1]
     print("%-9s %s" % ("same" if same else "DIFFERENT", k))
-    if not same or a[k][1] != b[k][1]:
-        bad += not same
+    if not same:
+        bad += 1
         print("   A", a[k][1], counts(a[k][0]))
         print("   B", b[k][1], counts(b[k][0]))
-        if show and sys.argv[3] in k:
+        if show and ARGS[2] in k:
             for l in difflib.unified_diff(a[k][0], b[k][0], lineterm="", n=2):
                 print("     ", l)
+print("%d kernels compared, %d differ" % (len(set(a) | set(b)), bad))
 sys.exit(1 if bad else 0)
