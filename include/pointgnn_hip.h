@@ -525,6 +525,79 @@ int pgnn_edge_mlp_scatter_max_fwd_dyn(const float *P, const float *Q,
                                       const pgnn_dyn_count *num_vertices,
                                       void *stream);
 
+/* ---- sum / mean aggregation of the two fused stages ----------------------
+ * The reference injects the aggregator into both operators (gnn.py:211-220,
+ * 285-296) and ships three: graph_scatter_max_fn, graph_scatter_sum_fn and
+ * graph_scatter_mean_fn (gnn.py:106-119).  The four *_agg_* entries below are
+ * the entries above with the aggregator as an argument:
+ *   PGNN_AGG_MAX   exactly the entry above (workspace not read);
+ *   PGNN_AGG_SUM   tf.math.unsorted_segment_sum of the per-edge rows
+ *                  act(h W + b): a segment without edges gives a row of zeros,
+ *                  ids outside [0, K) contribute nothing, pad columns are 0;
+ *   PGNN_AGG_MEAN  tf.math.unsorted_segment_mean: the sum, then every row
+ *                  divided by max(in-degree, 1) in one finishing pass (the
+ *                  in-degrees: one pass over the dst column, integer atomics);
+ *   anything else  PGNN_E_INVALID.
+ * Sum and mean zero `out` themselves (bit 1 of edges_sorted is ignored) and
+ * run the weights-stationary kernels with the sum epilogue (csrc/ws_sum.h)
+ * where the max entries run theirs: one 300x300 / 256x256 edge layer, car's
+ * 4-32-64-128-300 point MLP, ~65k edges and more.  Bias and ReLU are applied
+ * to every edge row before it is added (they do not commute with a sum).
+ * Whole segments are stored, segments that span two waves' ranges or belong to
+ * an unsorted list are added with float atomics: their last bits may differ
+ * from run to run, as with TensorFlow's kernel.  Anywhere else the host-sized
+ * entries compose the stage from pgnn_edge_hidden_fwd / pgnn_pool_features_fwd,
+ * pgnn_mlp_fwd and pgnn_scatter_sum_f32 with the per-edge rows in `workspace`;
+ * the _dyn entries return PGNN_E_UNSUPPORTED there, having enqueued nothing.
+ * `workspace`: device memory, 16-byte aligned, owned by the caller, free for
+ * reuse once the call's work on `stream` is done; the *_agg_workspace_bytes
+ * query says how much a call takes (the in-degrees for a mean, the rows of the
+ * composed path; 0: may be NULL) for the stream it will run on --
+ * capacity_form != 0 asks for the _dyn entry (edges_hint as
+ * pgnn_dyn_count.hint, 0 = none) and returns PGNN_E_UNSUPPORTED where that
+ * entry would.  Too small: PGNN_E_WORKSPACE, nothing launched.                */
+#define PGNN_AGG_MAX 0
+#define PGNN_AGG_SUM 1
+#define PGNN_AGG_MEAN 2
+/* gnn.py:362-365 with any of the three aggregators */
+int pgnn_edge_mlp_scatter_agg_workspace_bytes(
+    const pgnn_fc_layer *layers_host, int32_t n_layers, int32_t width,
+    int64_t edges_cap, int64_t edges_hint, int32_t vertices_cap,
+    int32_t aggregation, int32_t capacity_form, void *stream, size_t *bytes);
+int pgnn_edge_mlp_scatter_agg_fwd(
+    const float *P, const float *Q, int64_t ld_pq, int32_t width,
+    const int32_t *edges, int64_t n_edges, int32_t num_vertices,
+    const pgnn_fc_layer *layers_host, int32_t n_layers, int32_t edges_sorted,
+    float *out, int64_t ld_out, int32_t *sched_ws, int32_t aggregation,
+    void *workspace, size_t workspace_bytes, void *stream);
+/* ... in capacity form; the finishing pass of the mean covers
+ * min(*num_vertices, vertices_cap) rows */
+int pgnn_edge_mlp_scatter_agg_fwd_dyn(
+    const float *P, const float *Q, int64_t ld_pq, int32_t width,
+    const int32_t *edges, int64_t edges_cap, int32_t vertices_cap,
+    const pgnn_fc_layer *layers_host, int32_t n_layers, int32_t edges_sorted,
+    float *out, int64_t ld_out, int32_t *sched_ws,
+    const pgnn_dyn_count *n_edges, const pgnn_dyn_count *num_vertices,
+    int32_t aggregation, void *workspace, size_t workspace_bytes, void *stream);
+/* gnn.py:275-277 with any of the three aggregators (n_feat <= 13) */
+int pgnn_point_set_pooling_agg_workspace_bytes(
+    const pgnn_fc_layer *layers_host, int32_t n_layers, int32_t n_feat,
+    int64_t edges_cap, int64_t edges_hint, int32_t keypoints_cap,
+    int32_t aggregation, int32_t capacity_form, void *stream, size_t *bytes);
+int pgnn_point_set_pooling_agg_fwd(
+    const float *point_features, int32_t n_feat, const float *point_xyz,
+    const int32_t *keypoint_indices, const int32_t *edges, int64_t n_edges,
+    int32_t num_keypoints, const pgnn_fc_layer *layers_host, int32_t n_layers,
+    int32_t edges_sorted, float *out, int64_t ld_out, int32_t *sched_ws,
+    int32_t aggregation, void *workspace, size_t workspace_bytes, void *stream);
+int pgnn_point_set_pooling_agg_fwd_dyn(
+    const float *point_features, int32_t n_feat, const float *point_xyz,
+    const int32_t *keypoint_indices, const int32_t *edges, int64_t edges_cap,
+    int32_t keypoints_cap, const pgnn_fc_layer *layers_host, int32_t n_layers,
+    int32_t edges_sorted, float *out, int64_t ld_out, int32_t *sched_ws,
+    const pgnn_dyn_count *n_edges, const pgnn_dyn_count *num_keypoints,
+    int32_t aggregation, void *workspace, size_t workspace_bytes, void *stream);
+
 /* SECONDARY arithmetic for the same stage with ONE remaining edge layer of
  * 300x300 or 256x256 (csrc/edge_ws_split.h, Bf16x3): the layer's product runs on the
  * bf16 matrix pipe with BOTH operands split exactly into three bf16 parts

@@ -198,6 +198,39 @@ _SIGNATURES = {
                                                   ctypes.POINTER(DynCount),
                                                   ctypes.POINTER(DynCount),
                                                   c_vp]),
+    # sum / mean aggregation of the two fused stages (csrc/ws_sum.h)
+    "pgnn_edge_mlp_scatter_agg_workspace_bytes": (c_i32, [
+        ctypes.POINTER(FcLayer), c_i32, c_i32, c_i64, c_i64, c_i32, c_i32,
+        c_i32, c_vp, ctypes.POINTER(c_sz)]),
+    "pgnn_edge_mlp_scatter_agg_fwd": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp,
+                                              c_i64, c_i32,
+                                              ctypes.POINTER(FcLayer), c_i32,
+                                              c_i32, c_vp, c_i64, c_vp, c_i32,
+                                              c_vp, c_sz, c_vp]),
+    "pgnn_edge_mlp_scatter_agg_fwd_dyn": (c_i32, [c_vp, c_vp, c_i64, c_i32,
+                                                  c_vp, c_i64, c_i32,
+                                                  ctypes.POINTER(FcLayer),
+                                                  c_i32, c_i32, c_vp, c_i64,
+                                                  c_vp,
+                                                  ctypes.POINTER(DynCount),
+                                                  ctypes.POINTER(DynCount),
+                                                  c_i32, c_vp, c_sz, c_vp]),
+    "pgnn_point_set_pooling_agg_workspace_bytes": (c_i32, [
+        ctypes.POINTER(FcLayer), c_i32, c_i32, c_i64, c_i64, c_i32, c_i32,
+        c_i32, c_vp, ctypes.POINTER(c_sz)]),
+    "pgnn_point_set_pooling_agg_fwd": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp,
+                                               c_i64, c_i32,
+                                               ctypes.POINTER(FcLayer), c_i32,
+                                               c_i32, c_vp, c_i64, c_vp, c_i32,
+                                               c_vp, c_sz, c_vp]),
+    "pgnn_point_set_pooling_agg_fwd_dyn": (c_i32, [c_vp, c_i32, c_vp, c_vp,
+                                                   c_vp, c_i64, c_i32,
+                                                   ctypes.POINTER(FcLayer),
+                                                   c_i32, c_i32, c_vp, c_i64,
+                                                   c_vp,
+                                                   ctypes.POINTER(DynCount),
+                                                   ctypes.POINTER(DynCount),
+                                                   c_i32, c_vp, c_sz, c_vp]),
     "pgnn_vertex_pre_edge_fwd_dyn": (c_i32, [c_vp, c_i64, c_i32, c_vp,
                                              ctypes.POINTER(FcLayer), c_i32,
                                              ctypes.POINTER(FcLayer), c_vp,
@@ -473,6 +506,8 @@ def load():
 E_INVALID = -1       # PGNN_E_* of include/pointgnn_hip.h
 E_WORKSPACE = -2
 E_UNSUPPORTED = -3
+# `aggregation` of the pgnn_*_agg_* entries (PGNN_AGG_* of the header)
+AGG_MAX, AGG_SUM, AGG_MEAN = 0, 1, 2
 
 
 def check(rc, what=""):

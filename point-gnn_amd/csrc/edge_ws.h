@@ -288,6 +288,13 @@ __device__ __forceinline__ void ws_epilogue(const ARGS &a, const float *bias_lds
   st.has = cur_has;
 }
 
+}  // namespace pgnn
+
+// the sum epilogue (ws_flush_sum, ws_epilogue_sum) and the policies WsMax / WsSum
+#include "ws_sum.h"
+
+namespace pgnn {
+
 // tiles [tile_first, tile_last) of 16 edge rows, column tiles t0 .. t0+NTG-1
 // whose fragments sit in `wl` ([KQ][NTG][64] float4)
 //
@@ -295,7 +302,10 @@ __device__ __forceinline__ void ws_epilogue(const ARGS &a, const float *bias_lds
 // 16 KQ floats per edge ([n_edges, 4 * ldv4]; `Q` and the edges' src column are
 // not read): the second half of the split pooling stage (pool_split.h), where
 // the rows are the point MLP's hidden activations.
-template <int KQ, int NTG, bool EMIT, bool ROWS = false>
+//
+// POL: what is kept of a segment's rows -- WsMax: their maximum (ws_epilogue);
+// WsSum: their sum (ws_sum.h), the open run's identity 0 instead of lowest().
+template <int KQ, int NTG, bool EMIT, bool ROWS = false, class POL = WsMax>
 __device__ __forceinline__ void edge_ws_body(const EdgeWsArgs &a,
                                              const v4f *__restrict__ wl, int t0,
                                              const float *bias_lds,
@@ -320,10 +330,11 @@ __device__ __forceinline__ void edge_ws_body(const EdgeWsArgs &a,
   cur_d = __builtin_amdgcn_readfirstlane(cur_d);
   d_after = __builtin_amdgcn_readfirstlane(d_after);
   bool cur_left_closed = false, cur_has = false;
+  constexpr float kIdentity = POL::kSum ? 0.0f : kFloatLowest;
   v4f carry[NTG];
 #pragma unroll
   for (int t = 0; t < NTG; ++t)
-    carry[t] = (v4f){kFloatLowest, kFloatLowest, kFloatLowest, kFloatLowest};
+    carry[t] = (v4f){kIdentity, kIdentity, kIdentity, kIdentity};
 
   // (src, dst) of a tile's rows are requested one tile ahead.  The request is
   // unconditional (clamped index) and the validity select happens where the
@@ -529,8 +540,12 @@ __device__ __forceinline__ void edge_ws_body(const EdgeWsArgs &a,
     starts = (unsigned)(__ballot(my_d != prev) & 0xFFFFull);
     }  // !fin
     WsRun st = {cur_d, cur_left_closed, cur_has};
-    ws_epilogue<NTG>(a, bias_lds, t0, lane, acc, carry, starts, my_d, st, fin,
-                     d_after, inf);
+    if constexpr (POL::kSum)
+      ws_epilogue_sum<NTG>(a, bias_lds, t0, lane, acc, carry, starts, my_d, st,
+                           fin, d_after, inf);
+    else
+      ws_epilogue<NTG>(a, bias_lds, t0, lane, acc, carry, starts, my_d, st, fin,
+                       d_after, inf);
     cur_d = st.cur_d;
     cur_left_closed = st.left_closed;
     cur_has = st.has;
@@ -687,7 +702,8 @@ __device__ __forceinline__ void ws_pool_rearm(int32_t *sched, int n_counters,
   }
 }
 
-template <int KQ, int NTMAX, bool EMIT = false, bool ROWS = false>
+template <int KQ, int NTMAX, bool EMIT = false, bool ROWS = false,
+          class POL = WsMax>
 __global__ __launch_bounds__(64 * kWsWaves) void edge_ws_kernel(EdgeWsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   v4f *wl = reinterpret_cast<v4f *>(smem);
@@ -759,11 +775,11 @@ __global__ __launch_bounds__(64 * kWsWaves) void edge_ws_kernel(EdgeWsArgs a) {
   int32_t *counter = a.sched ? a.sched + 2 + slice * kWsMaxGroups + grp : nullptr;
   for (;;) {
     if (ntg == NTMAX)
-      edge_ws_body<KQ, NTMAX, EMIT, ROWS>(a, wl, t0, bias_lds, tile_first,
+      edge_ws_body<KQ, NTMAX, EMIT, ROWS, POL>(a, wl, t0, bias_lds, tile_first,
                                           tile_last, lane, tsw, stamped,
                                           n_edges);
     else
-      edge_ws_body<KQ, NTMAX - 1, EMIT, ROWS>(a, wl, t0, bias_lds, tile_first,
+      edge_ws_body<KQ, NTMAX - 1, EMIT, ROWS, POL>(a, wl, t0, bias_lds, tile_first,
                                               tile_last, lane, tsw, stamped,
                                               n_edges);
     if (pool == 0) break;

@@ -1545,6 +1545,321 @@ extern "C" int pgnn_edge_mlp_scatter_max_fwd_dyn(
   PGNN_GUARD_END
 }
 
+// ---- sum / mean aggregation of the two fused stages --------------------------
+// graph_scatter_sum_fn / graph_scatter_mean_fn (gnn.py:111-119) as the injected
+// aggregator of PointSetPooling (gnn.py:275-277) and GraphNetAutoCenter
+// (gnn.py:362-365).  Weights-stationary kernels with the sum epilogue
+// (ws_sum.h) where they apply; otherwise -- host-sized calls only -- the stage
+// composed from the entries that materialise its rows: gather, pgnn_mlp_fwd,
+// scatter-add (a list grouped by destination: added in row order without
+// atomics, scatter_max.hip).  The mean is the sum, then one pass that divides every row by
+// max(in-degree, 1); the in-degrees come from a pass over the dst column with
+// integer atomics (exact, order-free).  The division is not folded into the
+// kernel's flush: a run at a range boundary is a partial sum.
+namespace {
+
+__global__ void fill_zero_kernel(float *__restrict__ out, int64_t total) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = 0.0f;
+}
+// (a kernel, not hipMemsetAsync: see arm_sched in pgnn_common.h.  Capacity form:
+// the whole capacity is zeroed, rows behind the count included.)
+int fill_zero(float *out, int64_t total, hipStream_t stream) {
+  if (total <= 0) return 0;
+  int64_t blocks = (total + 1023) / 1024;
+  if (blocks > 4096) blocks = 4096;
+  return launch_lds(fill_zero_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                    stream, out, total);
+}
+
+// Workspace of an aggregating call: [the in-degrees, int32 per segment, mean
+// only][general path only: the gathered input rows, edges x ld_in floats][...:
+// the per-edge output rows, edges x out_cols floats], every part 64-byte
+// aligned.
+struct AggWork {
+  size_t counts, in_rows, out_rows;
+  size_t total() const { return counts + in_rows + out_rows; }
+};
+inline size_t agg_round(size_t bytes) { return (bytes + 63) / 64 * 64; }
+AggWork agg_work(int aggregation, int64_t segments, bool general, int64_t edges,
+                 int64_t ld_in, int64_t out_cols) {
+  AggWork w = {0, 0, 0};
+  if (aggregation == PGNN_AGG_MEAN) w.counts = agg_round((size_t)segments * 4);
+  if (general) {
+    w.in_rows = agg_round((size_t)edges * ld_in * sizeof(float));
+    w.out_rows = agg_round((size_t)edges * out_cols * sizeof(float));
+  }
+  return w;
+}
+int agg_workspace_ok(const AggWork &w, const void *workspace, size_t bytes,
+                     const char *who) {
+  if (w.total() == 0) return 0;
+  PGNN_REQUIRE(workspace != nullptr && bytes >= w.total(), PGNN_E_WORKSPACE,
+               (std::string(who) + ": workspace missing or too small").c_str());
+  PGNN_REQUIRE((uintptr_t)workspace % 16 == 0, PGNN_E_INVALID,
+               (std::string(who) + ": workspace not 16-byte aligned").c_str());
+  return 0;
+}
+
+// query != nullptr: only says how much workspace the call would take
+int edge_agg_impl(const float *P, const float *Q, int64_t ld_pq, int32_t width,
+                  const int32_t *edges, int64_t n_edges, int32_t num_vertices,
+                  const pgnn_fc_layer *layers, int32_t n_layers,
+                  int32_t edges_sorted, float *out, int64_t ld_out,
+                  int32_t *sched_ws, int32_t aggregation, void *workspace,
+                  size_t workspace_bytes, hipStream_t stream, const Dyn &de,
+                  const Dyn &dk, bool dyn, size_t *query) {
+  PGNN_REQUIRE(aggregation == PGNN_AGG_MAX || aggregation == PGNN_AGG_SUM ||
+                   aggregation == PGNN_AGG_MEAN,
+               PGNN_E_INVALID, "edge_mlp_agg: unknown aggregation");
+  if (query) *query = 0;
+  if (aggregation == PGNN_AGG_MAX) {
+    if (query) return 0;
+    return edge_fwd_impl(P, Q, ld_pq, width, edges, n_edges, num_vertices, layers,
+                         n_layers, edges_sorted, out, ld_out, sched_ws, stream, de,
+                         dk);
+  }
+  PGNN_REQUIRE(n_edges >= 0 && num_vertices >= 0 && width > 0, PGNN_E_INVALID,
+               "edge_mlp_agg: bad sizes");
+  Plan p;
+  int rc = make_plan(layers, n_layers, width, p);
+  if (rc) return rc;
+  const int out_cols = 16 * p.chain.l[n_layers - 1].nt;
+  const int cus = ws_cus(stream);
+  const bool ws = edge_ws_applies<WsSum>(p, expected(de, n_edges), cus);
+  // capacity form: the general path sizes its launches on the host
+  if (dyn && !ws) return PGNN_E_UNSUPPORTED;  // (no message: an expected answer)
+  const AggWork w = agg_work(aggregation, num_vertices, !ws, n_edges,
+                             16 * p.chain.l[0].kq, out_cols);
+  if (query) {
+    *query = w.total();
+    return 0;
+  }
+  PGNN_REQUIRE(ld_pq == 16 * p.chain.l[0].kq, PGNN_E_INVALID,
+               "edge_mlp_agg: ld_pq must equal the padded width 16*ceil(width/16)");
+  PGNN_REQUIRE(ld_out >= out_cols, PGNN_E_INVALID,
+               "edge_mlp_agg: ld_out < padded output width");
+  if (num_vertices == 0) return 0;
+  PGNN_REQUIRE(out != nullptr, PGNN_E_INVALID, "edge_mlp_agg: null output");
+  rc = agg_workspace_ok(w, workspace, workspace_bytes, "edge_mlp_agg");
+  if (rc) return rc;
+  // (bit 1 of edges_sorted -- "out holds lowest()" -- means nothing to a sum)
+  rc = fill_zero(out, (int64_t)num_vertices * ld_out, stream);
+  if (rc || n_edges == 0) return rc;
+  PGNN_REQUIRE(P && Q && edges, PGNN_E_INVALID, "edge_mlp_agg: null input");
+  PGNN_REQUIRE(((uintptr_t)P % 16 == 0) && ((uintptr_t)Q % 16 == 0),
+               PGNN_E_INVALID, "edge_mlp_agg: P/Q must be 16-byte aligned");
+  char *wsp = static_cast<char *>(workspace);
+  int32_t *counts = reinterpret_cast<int32_t *>(wsp);
+  const bool mean = aggregation == PGNN_AGG_MEAN;
+  if (!ws) {
+    float *h1 = reinterpret_cast<float *>(wsp + w.counts);
+    float *rows = reinterpret_cast<float *>(wsp + w.counts + w.in_rows);
+    rc = pgnn_edge_hidden_fwd(P, Q, ld_pq, edges, n_edges, h1, stream);
+    if (rc) return rc;
+    rc = mlp_fwd_impl(h1, ld_pq, width, nullptr, 0, 0, n_edges, layers, n_layers,
+                      nullptr, 0, rows, out_cols, stream, dyn_of(nullptr));
+    if (rc) return rc;
+    return scatter_sum_strided(rows, out_cols, edges + 1, 2, n_edges, out_cols,
+                               num_vertices, out, ld_out, mean ? 1 : 0, counts,
+                               edges_sorted & 1, stream);
+  }
+  const EdgeArgs ea = {P, Q, ld_pq, edges};
+  const SegArgs sa = {out, ld_out, num_vertices, edges_sorted & 1};
+  if (p.chain.l[0].nt == 19)
+    rc = launch_edge_ws<19, 7, WsSum>(p.chain.l[0], ea, n_edges, sa, cus, sched_ws,
+                                      stream, nullptr, 0, nullptr, de.dev);
+  else
+    rc = launch_edge_ws<16, 8, WsSum>(p.chain.l[0], ea, n_edges, sa, cus, sched_ws,
+                                      stream, nullptr, 0, nullptr, de.dev);
+  if (rc || !mean) return rc;
+  rc = segment_counts(edges + 1, 2, n_edges, de.dev, num_vertices, counts, stream);
+  if (rc) return rc;
+  return segment_mean_finish(out, ld_out, out_cols, num_vertices, counts, dk.dev,
+                             stream);
+}
+
+int pooling_agg_impl(const float *point_features, int32_t n_feat,
+                     const float *point_xyz, const int32_t *keypoint_indices,
+                     const int32_t *edges, int64_t n_edges,
+                     int32_t num_keypoints, const pgnn_fc_layer *layers,
+                     int32_t n_layers, int32_t edges_sorted, float *out,
+                     int64_t ld_out, int32_t *sched_ws, int32_t aggregation,
+                     void *workspace, size_t workspace_bytes, hipStream_t stream,
+                     const Dyn &de, const Dyn &dk, bool dyn, size_t *query) {
+  PGNN_REQUIRE(aggregation == PGNN_AGG_MAX || aggregation == PGNN_AGG_SUM ||
+                   aggregation == PGNN_AGG_MEAN,
+               PGNN_E_INVALID, "pooling_agg: unknown aggregation");
+  if (query) *query = 0;
+  if (aggregation == PGNN_AGG_MAX) {
+    if (query) return 0;
+    return pooling_fwd_impl(point_features, n_feat, point_xyz, keypoint_indices,
+                            edges, n_edges, num_keypoints, layers, n_layers,
+                            edges_sorted, out, ld_out, sched_ws, stream, de, dk);
+  }
+  PGNN_REQUIRE(n_edges >= 0 && num_keypoints >= 0 && n_feat >= 0 && n_feat <= 13,
+               PGNN_E_INVALID, "pooling_agg: bad sizes (n_feat <= 13)");
+  Plan p;
+  int rc = make_plan(layers, n_layers, n_feat + 3, p);
+  if (rc) return rc;
+  PGNN_REQUIRE(p.chain.l[0].kq == 1, PGNN_E_UNSUPPORTED,
+               "pooling_agg: first layer k_in must be <= 16");
+  const int out_cols = 16 * p.chain.l[n_layers - 1].nt;
+  const int cus = ws_cus(stream);
+  const bool ws = pool_ws_applies<WsSum>(p, expected(de, n_edges), cus);
+  if (dyn && !ws) return PGNN_E_UNSUPPORTED;  // (no message: an expected answer)
+  const AggWork w =
+      agg_work(aggregation, num_keypoints, !ws, n_edges, 16, out_cols);
+  if (query) {
+    *query = w.total();
+    return 0;
+  }
+  PGNN_REQUIRE(ld_out >= out_cols, PGNN_E_INVALID,
+               "pooling_agg: ld_out < padded output width");
+  if (num_keypoints == 0) return 0;
+  PGNN_REQUIRE(out != nullptr, PGNN_E_INVALID, "pooling_agg: null output");
+  rc = agg_workspace_ok(w, workspace, workspace_bytes, "pooling_agg");
+  if (rc) return rc;
+  rc = fill_zero(out, (int64_t)num_keypoints * ld_out, stream);
+  if (rc || n_edges == 0) return rc;
+  PGNN_REQUIRE((n_feat == 0 || point_features) && point_xyz &&
+                   keypoint_indices && edges,
+               PGNN_E_INVALID, "pooling_agg: null input");
+  char *wsp = static_cast<char *>(workspace);
+  int32_t *counts = reinterpret_cast<int32_t *>(wsp);
+  const bool mean = aggregation == PGNN_AGG_MEAN;
+  if (!ws) {
+    float *f = reinterpret_cast<float *>(wsp + w.counts);
+    float *rows = reinterpret_cast<float *>(wsp + w.counts + w.in_rows);
+    rc = pgnn_pool_features_fwd(point_features, n_feat, point_xyz,
+                                keypoint_indices, edges, n_edges, f, stream);
+    if (rc) return rc;
+    rc = mlp_fwd_impl(f, 16, n_feat + 3, nullptr, 0, 0, n_edges, layers, n_layers,
+                      nullptr, 0, rows, out_cols, stream, dyn_of(nullptr));
+    if (rc) return rc;
+    return scatter_sum_strided(rows, out_cols, edges + 1, 2, n_edges, out_cols,
+                               num_keypoints, out, ld_out, mean ? 1 : 0, counts,
+                               edges_sorted & 1, stream);
+  }
+  const PoolArgs pa = {point_features, n_feat, point_xyz, keypoint_indices, edges,
+                       0};
+  const SegArgs sa = {out, ld_out, num_keypoints, edges_sorted & 1};
+  rc = launch_pool_ws<WsSum>(p, pa, n_edges, sa, cus, sched_ws, stream, nullptr, 0,
+                             de.dev);
+  if (rc || !mean) return rc;
+  rc = segment_counts(edges + 1, 2, n_edges, de.dev, num_keypoints, counts,
+                      stream);
+  if (rc) return rc;
+  return segment_mean_finish(out, ld_out, out_cols, num_keypoints, counts, dk.dev,
+                             stream);
+}
+}  // namespace
+
+extern "C" int pgnn_edge_mlp_scatter_agg_workspace_bytes(
+    const pgnn_fc_layer *layers, int32_t n_layers, int32_t width,
+    int64_t edges_cap, int64_t edges_hint, int32_t vertices_cap,
+    int32_t aggregation, int32_t capacity_form, void *stream_, size_t *bytes) {
+  PGNN_GUARD_BEGIN
+  PGNN_REQUIRE(bytes && layers, PGNN_E_INVALID,
+               "edge_mlp_agg_workspace_bytes: bad arguments");
+  // capacity form: the kernel is chosen on the expected count (and the general
+  // path, the only part sized by the edge count, is not available)
+  const int64_t n_sel =
+      (capacity_form && edges_hint > 0 && edges_hint < edges_cap) ? edges_hint
+                                                                  : edges_cap;
+  return edge_agg_impl(nullptr, nullptr, 0, width, nullptr, n_sel, vertices_cap,
+                       layers, n_layers, 0, nullptr, 0, nullptr, aggregation,
+                       nullptr, 0, (hipStream_t)stream_, dyn_of(nullptr),
+                       dyn_of(nullptr), capacity_form != 0, bytes);
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_edge_mlp_scatter_agg_fwd(
+    const float *P, const float *Q, int64_t ld_pq, int32_t width,
+    const int32_t *edges, int64_t n_edges, int32_t num_vertices,
+    const pgnn_fc_layer *layers, int32_t n_layers, int32_t edges_sorted,
+    float *out, int64_t ld_out, int32_t *sched_ws, int32_t aggregation,
+    void *workspace, size_t workspace_bytes, void *stream_) {
+  PGNN_GUARD_BEGIN
+  return edge_agg_impl(P, Q, ld_pq, width, edges, n_edges, num_vertices, layers,
+                       n_layers, edges_sorted, out, ld_out, sched_ws, aggregation,
+                       workspace, workspace_bytes, (hipStream_t)stream_,
+                       dyn_of(nullptr), dyn_of(nullptr), false, nullptr);
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_edge_mlp_scatter_agg_fwd_dyn(
+    const float *P, const float *Q, int64_t ld_pq, int32_t width,
+    const int32_t *edges, int64_t edges_cap, int32_t vertices_cap,
+    const pgnn_fc_layer *layers, int32_t n_layers, int32_t edges_sorted,
+    float *out, int64_t ld_out, int32_t *sched_ws,
+    const pgnn_dyn_count *n_edges, const pgnn_dyn_count *num_vertices,
+    int32_t aggregation, void *workspace, size_t workspace_bytes,
+    void *stream_) {
+  PGNN_GUARD_BEGIN
+  PGNN_REQUIRE(n_edges && n_edges->dev && num_vertices && num_vertices->dev,
+               PGNN_E_INVALID, "edge_mlp_agg_dyn: null count");
+  return edge_agg_impl(P, Q, ld_pq, width, edges, edges_cap, vertices_cap, layers,
+                       n_layers, edges_sorted, out, ld_out, sched_ws, aggregation,
+                       workspace, workspace_bytes, (hipStream_t)stream_,
+                       dyn_of(n_edges), dyn_of(num_vertices), true, nullptr);
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_point_set_pooling_agg_workspace_bytes(
+    const pgnn_fc_layer *layers, int32_t n_layers, int32_t n_feat,
+    int64_t edges_cap, int64_t edges_hint, int32_t keypoints_cap,
+    int32_t aggregation, int32_t capacity_form, void *stream_, size_t *bytes) {
+  PGNN_GUARD_BEGIN
+  PGNN_REQUIRE(bytes && layers, PGNN_E_INVALID,
+               "pooling_agg_workspace_bytes: bad arguments");
+  const int64_t n_sel =
+      (capacity_form && edges_hint > 0 && edges_hint < edges_cap) ? edges_hint
+                                                                  : edges_cap;
+  return pooling_agg_impl(nullptr, n_feat, nullptr, nullptr, nullptr, n_sel,
+                          keypoints_cap, layers, n_layers, 0, nullptr, 0, nullptr,
+                          aggregation, nullptr, 0, (hipStream_t)stream_,
+                          dyn_of(nullptr), dyn_of(nullptr), capacity_form != 0,
+                          bytes);
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_point_set_pooling_agg_fwd(
+    const float *point_features, int32_t n_feat, const float *point_xyz,
+    const int32_t *keypoint_indices, const int32_t *edges, int64_t n_edges,
+    int32_t num_keypoints, const pgnn_fc_layer *layers, int32_t n_layers,
+    int32_t edges_sorted, float *out, int64_t ld_out, int32_t *sched_ws,
+    int32_t aggregation, void *workspace, size_t workspace_bytes,
+    void *stream_) {
+  PGNN_GUARD_BEGIN
+  return pooling_agg_impl(point_features, n_feat, point_xyz, keypoint_indices,
+                          edges, n_edges, num_keypoints, layers, n_layers,
+                          edges_sorted, out, ld_out, sched_ws, aggregation,
+                          workspace, workspace_bytes, (hipStream_t)stream_,
+                          dyn_of(nullptr), dyn_of(nullptr), false, nullptr);
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_point_set_pooling_agg_fwd_dyn(
+    const float *point_features, int32_t n_feat, const float *point_xyz,
+    const int32_t *keypoint_indices, const int32_t *edges, int64_t edges_cap,
+    int32_t keypoints_cap, const pgnn_fc_layer *layers, int32_t n_layers,
+    int32_t edges_sorted, float *out, int64_t ld_out, int32_t *sched_ws,
+    const pgnn_dyn_count *n_edges, const pgnn_dyn_count *num_keypoints,
+    int32_t aggregation, void *workspace, size_t workspace_bytes,
+    void *stream_) {
+  PGNN_GUARD_BEGIN
+  PGNN_REQUIRE(n_edges && n_edges->dev && num_keypoints && num_keypoints->dev,
+               PGNN_E_INVALID, "pooling_agg_dyn: null count");
+  return pooling_agg_impl(point_features, n_feat, point_xyz, keypoint_indices,
+                          edges, edges_cap, keypoints_cap, layers, n_layers,
+                          edges_sorted, out, ld_out, sched_ws, aggregation,
+                          workspace, workspace_bytes, (hipStream_t)stream_,
+                          dyn_of(n_edges), dyn_of(num_keypoints), true, nullptr);
+  PGNN_GUARD_END
+}
+
 // ---- vertex side of one GraphNetAutoCenter iteration, before the edge kernel ----
 // gnn.py:341-356 per vertex: delta = offset MLP(h); Q = (x + delta) W1[C:];
 // P = [h, x] W1 + b1; plus the lowest() fill of the aggregation buffer.  Three

@@ -141,6 +141,19 @@ size_t device_max_lds();
 // replayed ped_cyl frame then skipped pool tiles, tools/ped_check.py)
 int arm_sched(int32_t *sched, hipStream_t stream);
 
+// scatter_max.hip, for gnn.hip's sum / mean aggregation (see there)
+int scatter_sum_strided(const float *data, int64_t ld_data,
+                        const int32_t *seg_ids, int64_t seg_stride,
+                        int64_t n_rows, int32_t n_cols, int32_t num_segments,
+                        float *out, int64_t ld_out, int32_t mean,
+                        int32_t *counts_ws, int32_t ids_sorted,
+                        hipStream_t stream);
+int segment_counts(const int32_t *seg_ids, int64_t seg_stride, int64_t n_rows,
+                   const int32_t *n_dev, int32_t num_segments, int32_t *counts,
+                   hipStream_t stream);
+int segment_mean_finish(float *out, int64_t ld_out, int32_t n_cols,
+                        int32_t num_segments, const int32_t *counts,
+                        const int32_t *ns_dev, hipStream_t stream);
 // gnn.hip, for trainer.hip: y = gate > 0 ? x W : 0 (one layer, rows to HBM) --
 // a backward dX pass with the ReluGrad of the layer below in its epilogue.
 int mlp_rows_gated(const float *x, int64_t ld_x, int32_t nx, int64_t n_rows,

@@ -110,7 +110,8 @@ __device__ __forceinline__ void pool_ws_block(const v4f *const (&wfrag)[3],
 
 // tiles [tile_first, tile_last) of 16 edge rows; last layer = 8 K groups x 19
 // column tiles in LDS
-template <bool EMIT>
+// POL: WsMax / WsSum, as in edge_ws_body
+template <bool EMIT, class POL = WsMax>
 __device__ __forceinline__ void pool_ws_body(const PoolWsArgs &a,
                                              const v4f *__restrict__ wl,
                                              const float *bias_lds,
@@ -129,13 +130,14 @@ __device__ __forceinline__ void pool_ws_body(const PoolWsArgs &a,
   cur_d = __builtin_amdgcn_readfirstlane(cur_d);
   d_after = __builtin_amdgcn_readfirstlane(d_after);
   WsRun run = {cur_d, false, false};
+  constexpr float kIdentity = POL::kSum ? 0.0f : kFloatLowest;
   v4f carry0[7], carry1[6], carry2[6];  // one per column block
 #pragma unroll
   for (int t = 0; t < 7; ++t) {
-    carry0[t] = (v4f){kFloatLowest, kFloatLowest, kFloatLowest, kFloatLowest};
+    carry0[t] = (v4f){kIdentity, kIdentity, kIdentity, kIdentity};
     if (t < 6) {
-      carry1[t] = (v4f){kFloatLowest, kFloatLowest, kFloatLowest, kFloatLowest};
-      carry2[t] = (v4f){kFloatLowest, kFloatLowest, kFloatLowest, kFloatLowest};
+      carry1[t] = (v4f){kIdentity, kIdentity, kIdentity, kIdentity};
+      carry2[t] = (v4f){kIdentity, kIdentity, kIdentity, kIdentity};
     }
   }
   const float inf = opaque_inf();
@@ -275,8 +277,12 @@ __device__ __forceinline__ void pool_ws_body(const PoolWsArgs &a,
       }                                                                        \
       if (a.prio) __builtin_amdgcn_s_setprio(3);                               \
       run = run0;                                                              \
-      ws_epilogue<NTB>(a, bias_lds + 16 * (TB), TB, lane, acc, CARRY, starts,  \
-                       my_d, run, fin, d_after, inf);                          \
+      if constexpr (POL::kSum)                                                 \
+        ws_epilogue_sum<NTB>(a, bias_lds + 16 * (TB), TB, lane, acc, CARRY,    \
+                             starts, my_d, run, fin, d_after, inf);            \
+      else                                                                     \
+        ws_epilogue<NTB>(a, bias_lds + 16 * (TB), TB, lane, acc, CARRY,        \
+                         starts, my_d, run, fin, d_after, inf);                \
       __builtin_amdgcn_s_setprio(0);                                           \
     }
     PGNN_POOL_WS_BLOCK(7, 0, carry0)
@@ -296,7 +302,7 @@ __device__ __forceinline__ void pool_ws_body(const PoolWsArgs &a,
   __builtin_amdgcn_s_setprio(0);
 }
 
-template <bool EMIT = false>
+template <bool EMIT = false, class POL = WsMax>
 __global__ __launch_bounds__(64 * kWsWaves) void pool_ws_kernel(PoolWsArgs a) {
   constexpr int KQ = 8, NT = 19;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -332,7 +338,7 @@ __global__ __launch_bounds__(64 * kWsWaves) void pool_ws_kernel(PoolWsArgs a) {
   }
   int stamped = 0;
   for (;;) {
-    pool_ws_body<EMIT>(a, wl, bias_lds, tile_first, tile_last, lane, tsw,
+    pool_ws_body<EMIT, POL>(a, wl, bias_lds, tile_first, tile_last, lane, tsw,
                        stamped, n_edges);
     if (pool == 0) break;
     const int c = ws_pool_claim(&a.sched[2], a.chunk, lane);

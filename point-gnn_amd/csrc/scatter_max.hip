@@ -258,8 +258,10 @@ extern "C" int pgnn_scatter_max_f32(const float *data, int64_t ld_data,
 // so the summation order is unspecified there too); mean = sum / max(count, 1).
 namespace {
 
+// (seg_stride: the ids of an [n_rows, 2] edge list's dst column come with 2)
 __global__ void scatter_add_kernel(const float *__restrict__ data, int64_t ld,
-                                   const int32_t *__restrict__ seg, int64_t n_rows,
+                                   const int32_t *__restrict__ seg,
+                                   int64_t seg_stride, int64_t n_rows,
                                    int32_t n_cols, int32_t num_segments,
                                    float *__restrict__ out, int64_t ldo,
                                    int32_t *__restrict__ counts) {
@@ -268,16 +270,82 @@ __global__ void scatter_add_kernel(const float *__restrict__ data, int64_t ld,
        i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = i / n_cols;
     const int c = (int)(i - r * n_cols);
-    const int s = seg[r];
+    const int s = seg[r * seg_stride];
     if (s < 0 || s >= num_segments) continue;
     atomicAdd(out + (int64_t)s * ldo + c, data[r * ld + c]);
     if (counts && c == 0) atomicAdd(counts + s, 1);
   }
 }
 
+// in-degrees alone (the fused sum kernels of gnn.hip add the rows themselves):
+// integer atomics, exact in any order.  n_dev (nullable): capacity form,
+// min(*n_dev, n_rows) ids are read.
+__global__ void segment_count_kernel(const int32_t *__restrict__ seg,
+                                     int64_t seg_stride, int64_t n_rows,
+                                     const int32_t *__restrict__ n_dev,
+                                     int32_t num_segments,
+                                     int32_t *__restrict__ counts) {
+  if (n_dev) {
+    const int64_t nd = *n_dev;
+    n_rows = nd < n_rows ? nd : n_rows;
+  }
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rows;
+       r += (int64_t)gridDim.x * blockDim.x) {
+    const int s = seg[r * seg_stride];
+    if (s < 0 || s >= num_segments) continue;
+    atomicAdd(counts + s, 1);
+  }
+}
+
+// ids non-decreasing (an edge list grouped by destination): a workgroup per
+// segment finds its rows with two binary searches and every thread adds its
+// column in row order -- no atomics, no fill, the in-degree is the range's
+// length, and the result is the same bits on every run.  (A segment is one
+// workgroup's work however long it is: the path of small and odd shapes.)
+__global__ void segment_sum_sorted_kernel(const float *__restrict__ data,
+                                          int64_t ld,
+                                          const int32_t *__restrict__ seg,
+                                          int64_t seg_stride, int64_t n_rows,
+                                          int32_t n_cols, int32_t num_segments,
+                                          float *__restrict__ out, int64_t ldo,
+                                          int32_t mean) {
+  for (int s = blockIdx.x; s < num_segments; s += gridDim.x) {
+    int64_t bound[2];
+    for (int j = 0; j < 2; ++j) {  // first row with id >= s + j
+      int64_t lo = 0, hi = n_rows;
+      while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (seg[mid * seg_stride] < s + j)
+          lo = mid + 1;
+        else
+          hi = mid;
+      }
+      bound[j] = lo;
+    }
+    const int64_t n = bound[1] - bound[0];
+    for (int c = threadIdx.x; c < n_cols; c += blockDim.x) {
+      float acc = 0.0f;
+      for (int64_t r = bound[0]; r < bound[1]; ++r) acc += data[r * ld + c];
+      if (mean) acc = acc / (float)(n > 1 ? n : 1);
+      out[(int64_t)s * ldo + c] = acc;
+    }
+  }
+}
+
+__global__ void zero_i32_kernel(int32_t *__restrict__ x, int32_t n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) x[i] = 0;
+}
+
+// ns_dev (nullable): capacity form, min(*ns_dev, num_segments) rows exist
 __global__ void scatter_mean_finish_kernel(float *__restrict__ out, int64_t ldo,
                                            int32_t n_cols, int32_t num_segments,
-                                           const int32_t *__restrict__ counts) {
+                                           const int32_t *__restrict__ counts,
+                                           const int32_t *__restrict__ ns_dev) {
+  if (ns_dev) {
+    const int32_t nd = *ns_dev;
+    num_segments = nd < num_segments ? (nd > 0 ? nd : 0) : num_segments;
+  }
   const int64_t total = (int64_t)num_segments * n_cols;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (int64_t)gridDim.x * blockDim.x) {
@@ -290,17 +358,34 @@ __global__ void scatter_mean_finish_kernel(float *__restrict__ out, int64_t ldo,
 
 }  // namespace
 
-extern "C" int pgnn_scatter_sum_f32(const float *data, int64_t ld_data,
-                                    const int32_t *seg_ids, int64_t n_rows,
-                                    int32_t n_cols, int32_t num_segments,
-                                    float *out, int64_t ld_out, int32_t mean,
-                                    int32_t *counts_ws, void *stream_) {
-  PGNN_GUARD_BEGIN
-  hipStream_t stream = (hipStream_t)stream_;
+// Library-internal (gnn.hip, the sum / mean aggregation of the fused stages):
+// pgnn_scatter_sum_f32 with the ids `seg_stride` int32 apart (ids_sorted != 0
+// promises that they are non-decreasing: the atomic-free kernel), and the two
+// halves of the mean on their own -- the in-degree of every segment into
+// `counts` (zeroed here), and out[s] /= max(counts[s], 1) over n_cols columns.
+namespace pgnn {
+int scatter_sum_strided(const float *data, int64_t ld_data,
+                        const int32_t *seg_ids, int64_t seg_stride,
+                        int64_t n_rows, int32_t n_cols, int32_t num_segments,
+                        float *out, int64_t ld_out, int32_t mean,
+                        int32_t *counts_ws, int32_t ids_sorted,
+                        hipStream_t stream) {
   PGNN_REQUIRE(n_rows >= 0 && n_cols > 0 && num_segments >= 0, PGNN_E_INVALID,
                "scatter_sum: negative size");
   PGNN_REQUIRE(ld_data >= n_cols && ld_out >= n_cols, PGNN_E_INVALID,
                "scatter_sum: row stride smaller than n_cols");
+  if (ids_sorted && num_segments > 0 && n_rows > 0) {
+    PGNN_REQUIRE(out && data && seg_ids, PGNN_E_INVALID,
+                 "scatter_sum: null argument");
+    const int threads = n_cols >= 256 ? 256 : 64;
+    hipLaunchKernelGGL(segment_sum_sorted_kernel,
+                       dim3((unsigned)(num_segments < 65536 ? num_segments : 65536)),
+                       dim3(threads), 0, stream, data, ld_data, seg_ids,
+                       seg_stride, n_rows, n_cols, num_segments, out, ld_out,
+                       mean);
+    PGNN_HIP(hipGetLastError());
+    return 0;
+  }
   PGNN_REQUIRE(!mean || counts_ws, PGNN_E_INVALID,
                "scatter_sum: mean needs the int32[num_segments] workspace");
   if (num_segments == 0) return 0;
@@ -317,19 +402,60 @@ extern "C" int pgnn_scatter_sum_f32(const float *data, int64_t ld_data,
     const int64_t cap = (int64_t)pgnn::device_cu_count() * 16;
     if (blocks > cap) blocks = cap;
     hipLaunchKernelGGL(scatter_add_kernel, dim3((unsigned)blocks), dim3(256), 0,
-                       stream, data, ld_data, seg_ids, n_rows, n_cols,
+                       stream, data, ld_data, seg_ids, seg_stride, n_rows, n_cols,
                        num_segments, out, ld_out, mean ? counts_ws : nullptr);
     PGNN_HIP(hipGetLastError());
   }
-  if (mean) {
-    const int64_t total = (int64_t)num_segments * n_cols;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(scatter_mean_finish_kernel, dim3((unsigned)blocks),
-                       dim3(256), 0, stream, out, ld_out, n_cols, num_segments,
-                       counts_ws);
-    PGNN_HIP(hipGetLastError());
-  }
+  if (mean)
+    return segment_mean_finish(out, ld_out, n_cols, num_segments, counts_ws,
+                               nullptr, stream);
   return 0;
+}
+
+int segment_counts(const int32_t *seg_ids, int64_t seg_stride, int64_t n_rows,
+                   const int32_t *n_dev, int32_t num_segments, int32_t *counts,
+                   hipStream_t stream) {
+  if (num_segments <= 0) return 0;
+  PGNN_REQUIRE(counts != nullptr, PGNN_E_INVALID, "segment_counts: null counts");
+  // (a kernel, not hipMemsetAsync: see arm_sched in pgnn_common.h)
+  hipLaunchKernelGGL(zero_i32_kernel, dim3((unsigned)((num_segments + 255) / 256)),
+                     dim3(256), 0, stream, counts, num_segments);
+  PGNN_HIP(hipGetLastError());
+  if (n_rows <= 0) return 0;
+  PGNN_REQUIRE(seg_ids != nullptr, PGNN_E_INVALID, "segment_counts: null ids");
+  int64_t blocks = (n_rows + 255) / 256;
+  const int64_t cap = (int64_t)pgnn::device_cu_count() * 8;
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(segment_count_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                     stream, seg_ids, seg_stride, n_rows, n_dev, num_segments,
+                     counts);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+}
+
+int segment_mean_finish(float *out, int64_t ld_out, int32_t n_cols,
+                        int32_t num_segments, const int32_t *counts,
+                        const int32_t *ns_dev, hipStream_t stream) {
+  if (num_segments <= 0 || n_cols <= 0) return 0;
+  const int64_t total = (int64_t)num_segments * n_cols;
+  int64_t blocks = (total + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(scatter_mean_finish_kernel, dim3((unsigned)blocks),
+                     dim3(256), 0, stream, out, ld_out, n_cols, num_segments,
+                     counts, ns_dev);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+}
+}  // namespace pgnn
+
+extern "C" int pgnn_scatter_sum_f32(const float *data, int64_t ld_data,
+                                    const int32_t *seg_ids, int64_t n_rows,
+                                    int32_t n_cols, int32_t num_segments,
+                                    float *out, int64_t ld_out, int32_t mean,
+                                    int32_t *counts_ws, void *stream_) {
+  PGNN_GUARD_BEGIN
+  return pgnn::scatter_sum_strided(data, ld_data, seg_ids, 1, n_rows, n_cols,
+                                   num_segments, out, ld_out, mean, counts_ws, 0,
+                                   (hipStream_t)stream_);
   PGNN_GUARD_END
 }

@@ -39,7 +39,9 @@ inline int ws_partition_rc(int why) {
 // tiles in groups that fit the LDS, the 16-row tiles in one slice per XCD.
 // plan_edge_ws fills the kernel's arguments, geometry included, and enqueues
 // nothing; run_edge_ws launches them.  ROWS: `ea.P` holds one ready input row
-// per edge (pool_split.h).
+// per edge (pool_split.h).  POL (WsMax / WsSum, ws_sum.h): the aggregation; the
+// partition, the tile pool and the balance do not depend on it, and the sum
+// kernels exist without EMIT and ROWS only.
 template <int KQ, int NTMAX>
 int plan_edge_ws(EdgeWsArgs &a, const LayerDev &L, const EdgeArgs &ea,
                  int64_t n_edges, const SegArgs &sa, int cus, int32_t *sched,
@@ -84,19 +86,20 @@ int plan_edge_ws(EdgeWsArgs &a, const LayerDev &L, const EdgeArgs &ea,
   return 0;
 }
 
-template <int KQ, int NTMAX, bool ROWS>
+template <int KQ, int NTMAX, bool ROWS, class POL = WsMax>
 int run_edge_ws(const EdgeWsArgs &a, int cus, hipStream_t stream) {
+  static_assert(!POL::kSum || !ROWS, "the sum kernels read no ready rows");
   PGNN_HIP((hipError_t)arm_sched(a.sched, stream));
   const size_t lds = (size_t)KQ * NTMAX * 1024 + 16 * NTMAX * sizeof(float);
-  auto kern = edge_ws_kernel<KQ, NTMAX, false, ROWS>;
-  if constexpr (!ROWS) {  // training forward: the rows are written as well
+  auto kern = edge_ws_kernel<KQ, NTMAX, false, ROWS, POL>;
+  if constexpr (!ROWS && !POL::kSum) {  // training forward: the rows are written as well
     if (a.rows_out) kern = edge_ws_kernel<KQ, NTMAX, true>;
   }
   return launch_lds(kern, dim3((unsigned)(cus / a.xcds * a.xcds)),
                     dim3(64 * kWsWaves), lds, stream, a);
 }
 
-template <int KQ, int NTMAX>
+template <int KQ, int NTMAX, class POL = WsMax>
 int launch_edge_ws(const LayerDev &L, const EdgeArgs &ea, int64_t n_edges,
                    const SegArgs &sa, int cus, int32_t *sched,
                    hipStream_t stream, float *rows_out = nullptr,
@@ -105,11 +108,14 @@ int launch_edge_ws(const LayerDev &L, const EdgeArgs &ea, int64_t n_edges,
   EdgeWsArgs a;
   const int rc = plan_edge_ws<KQ, NTMAX>(a, L, ea, n_edges, sa, cus, sched,
                                          rows_out, ld_rows, h1_out, n_dev);
-  return rc ? rc : run_edge_ws<KQ, NTMAX, false>(a, cus, stream);
+  return rc ? rc : run_edge_ws<KQ, NTMAX, false, POL>(a, cus, stream);
 }
 
 // the shapes edge_ws.h is instantiated for: one square layer of 19 (C = 300)
-// or 16 (C = 256) column tiles, a CU count that splits into 8 slices
+// or 16 (C = 256) column tiles, a CU count that splits into 8 slices.  (The
+// sum kernels share the max kernels' geometry, LDS image and threshold: the
+// answer is the same for every policy.)
+template <class POL = WsMax>
 bool edge_ws_applies(const Plan &p, int64_t n_edges, int cus) {
   if (g_mlp_debug & 2048) return false;
   const LayerDev &L = p.chain.l[0];
@@ -129,6 +135,7 @@ bool edge_ws_applies(const Plan &p, int64_t n_edges, int cus) {
 }
 
 // Weights-stationary pooling kernel (pool_ws.h): car's 4-32-64-128-300 chain.
+template <class POL = WsMax>
 bool pool_ws_applies(const Plan &p, int64_t n_edges, int cus) {
   if (g_mlp_debug & (8192 | 1024)) return false;
   const ChainDev &c = p.chain;
@@ -181,6 +188,7 @@ int pool_ws_out(PoolWsArgs &a, const SegArgs &sa, int32_t *sched,
   return 0;
 }
 
+template <class POL = WsMax>
 int launch_pool_ws(const Plan &p, const PoolArgs &pa, int64_t n_edges,
                    const SegArgs &sa, int cus, int32_t *sched,
                    hipStream_t stream, float *const *acts = nullptr,
@@ -198,8 +206,12 @@ int launch_pool_ws(const Plan &p, const PoolArgs &pa, int64_t n_edges,
   const int rc = pool_ws_out(a, sa, sched, stream);
   if (rc) return rc;
   const size_t lds = (size_t)8 * 19 * 1024 + 16 * 19 * sizeof(float);
-  return launch_lds(acts ? pool_ws_kernel<true> : pool_ws_kernel<false>,
-                    dim3((unsigned)cus), dim3(64 * kWsWaves), lds, stream, a);
+  auto kern = pool_ws_kernel<false, POL>;
+  if constexpr (!POL::kSum) {
+    if (acts) kern = pool_ws_kernel<true>;
+  }
+  return launch_lds(kern, dim3((unsigned)cus), dim3(64 * kWsWaves), lds, stream,
+                    a);
 }
 
 // Split pooling stage (pool_split.h): ped_cyl's 4-32-64-128-256-512 chain, the

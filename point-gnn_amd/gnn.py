@@ -13,9 +13,11 @@ implementation is eager, so the two implicit TF mechanisms are explicit here:
         h = gnn.GraphNetAutoCenter().apply_regular(h, xyz, None, edges, **kw)
 
 Only what every shipped config uses has a device path: activation 'ReLU',
-normalization 'NONE', scatter-max aggregation (other registry keys of
-gnn.py:17-32 raise NotImplementedError).  Tensors are torch CUDA float32 /
-int32; activations are kept zero-padded to a multiple of 16 columns
+normalization 'NONE' (other registry keys of gnn.py:17-32 raise
+NotImplementedError); the aggregator of the two graph operators is any of the
+reference's three (graph_scatter_max_fn / _sum_fn / _mean_fn).  Tensors are
+torch CUDA float32 / int32; activations are kept zero-padded to a multiple of
+16 columns
 (`padded_width`) between operators -- `.features(t, width)` strips the pad.
 """
 import contextlib
@@ -32,7 +34,8 @@ from .weights import mlp_names
 __all__ = ["PointSetPooling", "GraphNetAutoCenter", "ClassAwarePredictor",
            "fuse_vertex_stages",
            "multi_layer_neural_network_fn", "multi_layer_fc_fn",
-           "graph_scatter_max_fn", "ParamStore", "parameters",
+           "graph_scatter_max_fn", "graph_scatter_sum_fn",
+           "graph_scatter_mean_fn", "ParamStore", "parameters",
            "variable_scope", "padded_width"]
 
 
@@ -448,14 +451,66 @@ def _scatter_sum(point_features, point_centers, num_centers, mean):
 
 
 def graph_scatter_sum_fn(point_features, point_centers, num_centers):
-    """gnn.py:111-114 = tf.math.unsorted_segment_sum (standalone op; the fused
-    layers implement scatter-max only, like every shipped config)."""
+    """gnn.py:111-114 = tf.math.unsorted_segment_sum.  Standalone op; as the
+    `aggregation_fn` of PointSetPooling / GraphNetAutoCenter it selects the
+    fused kernels' sum epilogue (csrc/ws_sum.h)."""
     return _scatter_sum(point_features, point_centers, num_centers, False)
 
 
 def graph_scatter_mean_fn(point_features, point_centers, num_centers):
-    """gnn.py:116-119 = tf.math.unsorted_segment_mean."""
+    """gnn.py:116-119 = tf.math.unsorted_segment_mean (as `aggregation_fn`:
+    the fused sum and one finishing pass that divides by max(in-degree, 1))."""
     return _scatter_sum(point_features, point_centers, num_centers, True)
+
+
+def _aggregation_code(aggregation_fn):
+    """PGNN_AGG_* of an injected aggregator: chosen by IDENTITY of this
+    module's three functions (the reference's gnn.py:106-119); any other
+    callable has no fused form."""
+    for fn, code in ((graph_scatter_max_fn, _lib.AGG_MAX),
+                     (graph_scatter_sum_fn, _lib.AGG_SUM),
+                     (graph_scatter_mean_fn, _lib.AGG_MEAN)):
+        if aggregation_fn is fn:
+            return code
+    raise NotImplementedError(
+        "aggregation_fn must be graph_scatter_max_fn, graph_scatter_sum_fn or "
+        "graph_scatter_mean_fn of this module: only those are fused")
+
+
+# when set to a list, every PointSetPooling / GraphNetAutoCenter call appends
+# the tensor its aggregation wrote ([K, padded width], before the output /
+# update MLP): the tests of the sum and mean aggregation read the stage here
+AGGREGATE_TAP = None
+
+
+def _aggregate(lib, name, query_head, args, n_e, k, cnt_e, cnt_k, code, device):
+    """A fused stage with sum / mean aggregation: pgnn_<name>_fwd(_dyn) with
+    the workspace its query asks for (a stream-ordered allocation of the
+    caching allocator).  Capacity form exists only where the
+    weights-stationary kernel applies."""
+    dyn = cnt_e is not None
+    limit = ("sum / mean aggregation in capacity form needs the "
+             "weights-stationary kernel (one 300- or 256-wide edge layer, "
+             "car's 4-32-64-128-300 point MLP; about 65k edges and more)")
+    nbytes = ctypes.c_size_t(0)
+    rc = getattr(lib, "pgnn_%s_workspace_bytes" % name)(
+        *query_head, n_e, int(cnt_e.hint) if dyn else 0, k, code,
+        1 if dyn else 0, _lib.stream_ptr(), ctypes.byref(nbytes))
+    if dyn and rc == _lib.E_UNSUPPORTED:
+        raise NotImplementedError(limit)
+    _lib.check(rc, "pgnn_%s_workspace_bytes" % name)
+    work = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32,
+                       device=device) if nbytes.value else None
+    tail = (code, _lib.ptr(work), nbytes.value, _lib.stream_ptr())
+    if not dyn:
+        _lib.check(getattr(lib, "pgnn_%s_fwd" % name)(*(args + tail)),
+                   "pgnn_%s_fwd" % name)
+        return
+    rc = getattr(lib, "pgnn_%s_fwd_dyn" % name)(
+        *(args + (cnt_e.arg(), cnt_k.arg()) + tail))
+    if rc == _lib.E_UNSUPPORTED:
+        raise NotImplementedError(limit)
+    _lib.check(rc, "pgnn_%s_fwd_dyn" % name)
 
 
 def _edges_sorted_flag(edges):
@@ -502,8 +557,7 @@ class PointSetPooling(object):
     def __init__(self, point_feature_fn=multi_layer_neural_network_fn,
                  aggregation_fn=graph_scatter_max_fn,
                  output_fn=multi_layer_neural_network_fn):
-        if aggregation_fn is not graph_scatter_max_fn:
-            raise NotImplementedError("only scatter-max aggregation is fused")
+        self._aggregation = _aggregation_code(aggregation_fn)
         self._point_feature_fn = point_feature_fn
         self._aggregation_fn = aggregation_fn
         self._output_fn = output_fn
@@ -558,9 +612,14 @@ class PointSetPooling(object):
                 rows_in.stride(0), _lib.stream_ptr()),
                 "pgnn_pool_features_wide_fwd")
             rows = mlp_forward(point_chain, rows_in, point_chain.k_in)
-            agg = graph_scatter_max_fn(
-                rows, edges[:, 1], k,
-                ids_sorted=_edges_sorted_flag(set_indices) == 1)
+            if self._aggregation == _lib.AGG_MAX:
+                agg = graph_scatter_max_fn(
+                    rows, edges[:, 1], k,
+                    ids_sorted=_edges_sorted_flag(set_indices) == 1)
+            else:
+                agg = self._aggregation_fn(rows, edges[:, 1], k)
+            if AGGREGATE_TAP is not None:
+                AGGREGATE_TAP.append(agg)
             with variable_scope('combined_features'):
                 out_chain = _relu_chain(store, _scope(),
                                         list(output_MLP_depth_list), False)
@@ -579,7 +638,14 @@ class PointSetPooling(object):
             cnt_k, cnt_e = _both_counts(cnt_k, k, cnt_e, int(edges.shape[0]),
                                         xyz.device)
         done = False
-        if store.edge_arith == 'f16x2' and point_chain.n == 4:
+        if self._aggregation != _lib.AGG_MAX:
+            # sum / mean (csrc/ws_sum.h; fp32 whatever the model's edge_arith)
+            _aggregate(lib, "point_set_pooling_agg",
+                       (point_chain.array, point_chain.n, n_feat), args,
+                       int(edges.shape[0]), k, cnt_e, cnt_k, self._aggregation,
+                       xyz.device)
+            done = True
+        elif store.edge_arith == 'f16x2' and point_chain.n == 4:
             # the model's 16-bit arithmetic covers this stage's wide layer too
             # (csrc/pool_ws_f16.h); other shapes / few edges: the fp32 kernel
             with variable_scope('extract_vertex_features'):
@@ -645,6 +711,8 @@ class PointSetPooling(object):
             _lib.check(lib.pgnn_point_set_pooling_fwd_dyn(
                 *args, cnt_e.arg(), cnt_k.arg(), _lib.stream_ptr()),
                 "pgnn_point_set_pooling_fwd_dyn")
+        if AGGREGATE_TAP is not None:
+            AGGREGATE_TAP.append(agg)
         with variable_scope('combined_features'):
             out_chain = _relu_chain(store, _scope(),
                                     list(output_MLP_depth_list), False)
@@ -679,6 +747,9 @@ EDGE_INPUT_TAP = None
 #               the wide last layer of PointSetPooling's point MLP
 #               (csrc/pool_ws_f16.h, pgnn_point_set_pooling_f16x2_fwd; car's
 #               4-32-64-128-300 chain), same representation, same guard.
+# The split-precision kernels are max-only: a layer built with
+# graph_scatter_sum_fn / graph_scatter_mean_fn runs the fp32 kernel under
+# 'bf16x3' and 'f16x2' too.
 EDGE_ARITHS = ('f32', 'bf16x3', 'f16x2')
 
 
@@ -689,8 +760,7 @@ class GraphNetAutoCenter(object):
                  aggregation_fn=graph_scatter_max_fn,
                  update_fn=multi_layer_neural_network_fn,
                  auto_offset_fn=multi_layer_neural_network_fn):
-        if aggregation_fn is not graph_scatter_max_fn:
-            raise NotImplementedError("only scatter-max aggregation is fused")
+        self._aggregation = _aggregation_code(aggregation_fn)
         self._edge_feature_fn = edge_feature_fn
         self._aggregation_fn = aggregation_fn
         self._update_fn = update_fn
@@ -809,7 +879,15 @@ class GraphNetAutoCenter(object):
                      _edges_sorted_flag(edges) | 2, _lib.ptr(agg),
                      agg.stride(0), _lib.ptr(_lib.sched_ws(h.device)))
         done = False
-        if store.edge_arith != 'f32' and rest.n == 1:
+        if self._aggregation != _lib.AGG_MAX:
+            # sum / mean: the entry zeroes `agg` itself (the lowest() the
+            # per-vertex launch wrote is max's identity) and runs in fp32
+            _aggregate(lib, "edge_mlp_scatter_agg",
+                       (rest.array, rest.n, int(rest.k_in)), edge_args,
+                       int(e.shape[0]), k, cnt_e, cnt_k, self._aggregation,
+                       h.device)
+            done = True
+        elif store.edge_arith != 'f32' and rest.n == 1:
             done = self._edge_split(lib, store, edge_scope, edge_widths, p, q,
                                     wq, rest, e, k, edges, agg, cnt_e, cnt_k,
                                     st)
@@ -822,6 +900,8 @@ class GraphNetAutoCenter(object):
             _lib.check(lib.pgnn_edge_mlp_scatter_max_fwd_dyn(
                 *edge_args, cnt_e.arg(), cnt_k.arg(), st),
                 "pgnn_edge_mlp_scatter_max_fwd_dyn")
+        if AGGREGATE_TAP is not None:
+            AGGREGATE_TAP.append(agg)
         # update + residual, gnn.py:367-372
         upd_chain = _relu_chain(store, scope + '/combined_features',
                                 list(update_MLP_depth_list), True)

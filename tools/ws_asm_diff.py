@@ -21,6 +21,8 @@ import sys
 import difflib
 
 RENAME = [
+    # the aggregation policy (ws_sum.h) defaults to the max the kernels had
+    (r", pgnn::WsMax>", r">"),
     (r"edge_ws_bf16x3_kernel<(\d+), (\d+)>", r"edge_ws_split_kernel<pgnn::Bf16x3, \1, \2>"),
     (r"edge_ws_f16x2_kernel<(\d+), (\d+)>", r"edge_ws_split_kernel<pgnn::F16x2, \1, \2>"),
 ]
