@@ -2236,8 +2236,9 @@ extern "C" int pgnn_weight_grad_many_f32(const pgnn_wgrad_job *jobs,
 
 namespace {
 void pn_split(int64_t rows, int64_t &rps, int &slices) {
-  // one wave of workgroups (3 per CU at 48 KB of LDS; tunable with the
-  // weight-gradient kernels' `wgrad_wg_target`)
+  // one wave of workgroups: `wgrad_wg_target` slices (default 512 = 2 per CU on
+  // 256 CUs, the residency __launch_bounds__(256, 2) sizes the kernel's
+  // registers for; 48 KB of LDS each), shared with the weight-gradient kernels
   int64_t s = g_wgrad_wg_target;
   const int64_t max_s = (rows + kPnRows - 1) / kPnRows;
   if (s > max_s) s = max_s;

@@ -1036,6 +1036,10 @@ class Trainer(object):
         return out
 
     def _scatter_max_bwd(self, data, dst, out, gout):
+        """Dense adjoint of out = scatter_max(data) for `data` that left a
+        ReLU: relu_mask = 1 whatever the order of the ids (rows tied at a
+        maximum of exactly 0 get nothing, TF's ReluGrad; both callers hand
+        the result to fc_bwd(..., relu=False) as dZ)."""
         k, cols = int(out.shape[0]), int(data.shape[1])
         ties = torch.empty(k * cols, dtype=torch.int32, device=self.device)
         gdata = torch.empty_like(data)
@@ -1043,8 +1047,7 @@ class Trainer(object):
             _lib.ptr(data), data.stride(0), _lib.ptr(dst), int(data.shape[0]),
             cols, k, _lib.ptr(out), out.stride(0), _lib.ptr(gout),
             gout.stride(0), _lib.ptr(ties), _lib.ptr(gdata), gdata.stride(0),
-            int(getattr(dst, "_pgnn_sorted", 0)), self._st()),
-            "pgnn_scatter_max_bwd_f32")
+            1, self._st()), "pgnn_scatter_max_bwd_f32")
         return gdata
 
     def _segmax_fc_bwd(self, name, y, dst, out, gout, x, need_dx=True,

@@ -588,6 +588,135 @@ def test_full_gradient_matches_mask_matched_oracle(dev, name):
                   {k: "%.2g" % v for k, v in worst.items()}))
 
 
+def _reordered(batch, order, seed=11):
+    """`batch` with both levels' edge rows in another order: 'permuted' (a
+    seeded random permutation) or 'one_swap' (the last row moved to the front:
+    nearly grouped by destination, but not)."""
+    edges = []
+    for lvl, e in enumerate(batch[3]):
+        if order == "permuted":
+            e = e[np.random.default_rng(seed + lvl).permutation(len(e))]
+        elif order == "one_swap":
+            e = np.concatenate([e[-1:], e[:-1]])
+        else:
+            assert order == "sorted"
+        edges.append(np.ascontiguousarray(e))
+    return tuple(batch[:3]) + (edges,) + tuple(batch[4:])
+
+
+def _unordered_case(order, num_classes, dev):
+    """(batch on the unordered lists, the same batch on the sorted lists, the
+    NumPy form of the first for the oracle).  'mixed_batch': two frames merged
+    on the device by train.batch_data, the first sorted and tagged the way
+    graph_gen tags its lists, the second permuted and untagged."""
+    import torch
+    from pointgnn_amd import gnn, train
+    base = _tiny_batch(seed=3, num_classes=num_classes)
+    for e in base[3]:
+        assert np.all(np.diff(e[:, 1]) >= 0), "the fixture's lists are sorted"
+    if order != "mixed_batch":
+        b = _reordered(base, order)
+        return b, base, b
+    second = _tiny_batch(seed=4, num_classes=num_classes)
+
+    def to_dev(b, tag):
+        f = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        out = (f(b[0]), [f(c) for c in b[1]], [f(k) for k in b[2]],
+               [f(e) for e in b[3]], f(b[4]), f(b[5]), f(b[6]))
+        if tag:
+            for e in out[3]:
+                gnn.mark_sorted(e)
+        return out
+    npy = lambda b: (b[0].cpu().numpy(), [c.cpu().numpy() for c in b[1]],
+                     [k.cpu().numpy() for k in b[2]],
+                     [e.cpu().numpy() for e in b[3]], b[4].cpu().numpy(),
+                     b[5].cpu().numpy(), b[6].cpu().numpy())
+    merged = train.batch_data([to_dev(base, True),
+                               to_dev(_reordered(second, "permuted"), False)])
+    assert merged[3][0].is_cuda
+    for e in merged[3]:
+        assert getattr(e, "_pgnn_sorted", 0) != 1, \
+            "a merge with an unsorted frame is tagged as sorted"
+    both_sorted = train.batch_data([to_dev(base, True), to_dev(second, True)])
+    assert all(getattr(e, "_pgnn_sorted", 0) == 1 for e in both_sorted[3])
+    return merged, both_sorted, npy(merged)
+
+
+@pytest.mark.parametrize("order", ["permuted", "one_swap", "mixed_batch"])
+@pytest.mark.parametrize("name", ["car_auto_T3", "ped_cyl_auto_T3"])
+def test_training_step_on_unordered_edge_lists(dev, name, order):
+    """The whole step on edge lists that are NOT grouped by destination (the
+    `sorted = 0` branches of the rows-forward kernels, the routing passes and
+    the scatter adjoints), all three ways of running it.  The lists are passed
+    untagged: gnn._edges_sorted_flag decides, and the native batch's
+    edges_sorted flags are 0.
+      forward   logits and boxes are bit-identical to the same Trainer's run
+                on the sorted lists: the max is exact and an edge row's
+                arithmetic does not depend on its position;
+      backward  every entry of every variable's gradient agrees with the
+                float64 oracle under the device's own decisions (taken from
+                the device forward on the same unordered lists) within the bar
+                of test_full_gradient_matches_mask_matched_oracle;
+      determinism ('permuted') two native steps agree within the same bar
+                (atomics may reorder the last bits)."""
+    import torch
+    from pointgnn_amd import gnn, train
+    cfg = configs.get_config(name)
+    params = weights.init_params(cfg, seed=5, bias_scale=0.1)
+    batch, batch_sorted, batch_np = _unordered_case(order, cfg["num_classes"],
+                                                    dev)
+    for e in batch[3]:
+        assert gnn._edges_sorted_flag(torch.as_tensor(e)) == 0
+    tr = train.Trainer(cfg, params=params, device=dev)
+    tr.native = False
+    tr.forward(*batch[:4])
+    masks = _device_decisions(tr, cfg)
+    dec = to.Decisions(masks)
+    loss, g_ref, _ = to.step_gradients(params, cfg, [batch_np], decisions=[dec])
+    assert dec.pos == len(masks)
+    worst, failures = {}, []
+    for mode, (native, sparse) in (("native", (True, True)),
+                                   ("python", (False, True)),
+                                   ("dense", (False, False))):
+        t2 = train.Trainer(cfg, params=params, device=dev)
+        t2.native, t2.sparse_adjoint = native, sparse
+        lg_s, bx_s = [t.clone() for t in t2.forward(*batch_sorted[:4])]
+        lg_u, bx_u = [t.clone() for t in t2.forward(*batch[:4])]
+        if not torch.equal(lg_s, lg_u) or not torch.equal(bx_s, bx_u):
+            failures.append("%s: forward differs from the sorted lists' "
+                            "(logits %.3g, boxes %.3g)" % (
+                                mode, (lg_s - lg_u).abs().max().item(),
+                                (bx_s - bx_u).abs().max().item()))
+        if native:
+            nb, keep = t2._native_batch(*batch[:4])
+            assert [nb.edges_sorted[l] for l in range(nb.n_levels)] == \
+                [0] * nb.n_levels
+            del nb, keep
+        out = t2.train_step(batch, apply=False)
+        assert abs(out['cls_loss'] - loss['cls_loss']) < 1e-5 * max(1, loss['cls_loss'])
+        assert abs(out['loc_loss'] - loss['loc_loss']) < 1e-5 * max(1, loss['loc_loss'])
+        got = t2.grad_dict()
+        w = 0.0
+        for n, ref in g_ref.items():
+            e_max, _ = _grad_errors(got[n], ref)
+            w = max(w, e_max)
+            if not e_max < 1e-5:
+                failures.append("%s %s: max-entry rel err %.3g" % (mode, n,
+                                                                   e_max))
+        worst[mode] = w
+        if native and order == "permuted":
+            t2.train_step(batch, apply=False)
+            again = t2.grad_dict()
+            for n, ref in g_ref.items():
+                scale = np.abs(ref).max() + 1e-12
+                d = np.abs(again[n] - got[n]).max() / scale
+                if not d < 1e-5:
+                    failures.append("native %s: two steps differ by %.3g" % (n, d))
+    print("%s %s: worst entry error under the device's decisions %s" % (
+        name, order, {k: "%.2g" % v for k, v in worst.items()}))
+    assert not failures, "\n".join(failures)
+
+
 def test_sgd_step_and_loss_decrease(dev):
     from pointgnn_amd import train
     cfg = configs.car_auto_config(1)
@@ -886,17 +1015,26 @@ def test_batch_data_on_the_device_equals_the_numpy_merge(dev):
     assert out[1][0].shape[0] == 2 * wide[1][0].shape[0]
 
 
-@pytest.mark.parametrize("rows,k_in,n_cols,nseg,ties", [
+_SEGMAX_FC_SHAPES = [
     (4000, 300, 300, 90, False), (4000, 300, 300, 90, True),
     (9000, 128, 300, 150, False), (3000, 256, 256, 40, True),
-    (2500, 256, 512, 60, False), (700, 40, 70, 9, True), (5, 16, 16, 3, False)])
+    (2500, 256, 512, 60, False), (700, 40, 70, 9, True), (5, 16, 16, 3, False)]
+
+
+# (the sorted cases keep the ids they had before `order` existed)
+@pytest.mark.parametrize("rows,k_in,n_cols,nseg,ties,order", [
+    pytest.param(*(s + (o,)), id="-".join(str(v) for v in s) +
+                 ("" if o == "sorted" else "-" + o))
+    for o in ("sorted", "permuted") for s in _SEGMAX_FC_SHAPES])
 def test_segmax_fc_bwd_matches_dense_adjoint(dev, rows, k_in, n_cols, nseg,
-                                             ties):
+                                             ties, order):
     """pgnn_segmax_fc_bwd_f32 (sparse adjoint of out = segment_max(ReLU(XW+b)))
     against the dense chain in float64: dZ = TF's tie-sharing scatter-max
     gradient * [Y > 0], dX = (dZ W^T) * [X > 0], dW = X^T dZ, db = sum dZ.
     `ties`: duplicated X rows inside segments give equal POSITIVE maxima
-    (duplicate points of a cloud), which share the gradient equally."""
+    (duplicate points of a cloud), which share the gradient equally.
+    `order` 'permuted': the same rows in a random order, the maxima taken with
+    ids_sorted = False -- the references do not depend on the order."""
     import torch
     from pointgnn_amd import _lib, gnn
     from pointgnn_amd.gnn import padded_width
@@ -912,6 +1050,10 @@ def test_segmax_fc_bwd_matches_dense_adjoint(dev, rows, k_in, n_cols, nseg,
         for t in range(0, rows - 3, 7):                  # duplicate neighbours
             if seg[t] == seg[t + 1]:
                 x[t + 1] = x[t]
+    if order == "permuted":
+        perm = np.random.default_rng(rows).permutation(rows)
+        x, seg = x[perm], seg[perm]
+        assert rows < 50 or not np.all(np.diff(seg) >= 0)
     w = (rng.standard_normal((k_in, n_cols)) / np.sqrt(k_in)).astype(np.float32)
     b = (0.1 * rng.standard_normal(n_cols)).astype(np.float32)
     y = np.zeros((rows, cp), np.float32)
@@ -922,7 +1064,7 @@ def test_segmax_fc_bwd_matches_dense_adjoint(dev, rows, k_in, n_cols, nseg,
     wt[:, :k_in] = w.T
     yd, xd, sd, wtd, god = (T(y, dev), T(x, dev), T(seg, dev), T(wt, dev),
                             T(gout, dev))
-    out = gnn.graph_scatter_max_fn(yd, sd, nseg, ids_sorted=True)
+    out = gnn.graph_scatter_max_fn(yd, sd, nseg, ids_sorted=order == "sorted")
     dx = torch.full((rows, kp), 7.0, dtype=torch.float32, device=dev)
     dw = torch.full((k_in, n_cols), 0.25, dtype=torch.float32, device=dev)
     db = torch.full((n_cols,), -0.5, dtype=torch.float32, device=dev)
@@ -1107,10 +1249,28 @@ def _check_edge_segmax(c, form, res, with_db=True):
                                    rtol=2e-4, err_msg="db")
 
 
-@pytest.mark.parametrize("form", ["h1", "pq", "x"])
-@pytest.mark.parametrize("ties,with_db", [
-    ("cap", True), ("cap+1", True), ("cap+1", False), ("4cap", False)])
-def test_segmax_fc_bwd_at_the_tie_list_capacity(dev, form, ties, with_db):
+def _permute_edge_segmax_case(c, seed=3):
+    """The case with its edge rows (and what belongs to them) in a random
+    order; the per-vertex references do not depend on it."""
+    perm = np.random.default_rng(seed).permutation(len(c['edges']))
+    c = dict(c)
+    for key in ('edges', 'h1', 'y', 'ref_dx'):
+        c[key] = np.ascontiguousarray(c[key][perm])
+    assert not np.all(np.diff(c['edges'][:, 1]) >= 0)
+    return c
+
+
+_TIE_CASES = [("cap", True), ("cap+1", True), ("cap+1", False), ("4cap", False)]
+
+
+# (the sorted cases keep the ids they had before `order` existed)
+@pytest.mark.parametrize("ties,with_db,form,order", [
+    pytest.param(t, d, f, o, id="%s-%s-%s" % (t, d, f) +
+                 ("" if o == "sorted" else "-" + o))
+    for t, d in _TIE_CASES
+    for f, o in (("h1", "sorted"), ("pq", "sorted"), ("x", "sorted"),
+                 ("pq", "permuted"))])
+def test_segmax_fc_bwd_at_the_tie_list_capacity(dev, form, ties, with_db, order):
     """The further rows of tied positive maxima reach the weight gradient
     through a list of kTieCap = 65536 (row, column) entries; past it
     segmax_wgrad_ties_kernel scans every row instead.  Exactly kTieCap ties
@@ -1118,7 +1278,8 @@ def test_segmax_fc_bwd_at_the_tie_list_capacity(dev, form, ties, with_db):
     float64 adjoint: pgnn_edge_segmax_fc_bwd_f32 with the H1 rows given
     ('h1') and recomputed from P and Q ('pq'), pgnn_segmax_fc_bwd_f32 on the
     materialised rows ('x'); dW / db accumulate into prefilled buffers, db
-    may be NULL, garbage in dP / dQ / dX is overwritten."""
+    may be NULL, garbage in dP / dQ / dX is overwritten.  `order` 'permuted'
+    (form 'pq'): the same edges in a random order, not grouped by dst."""
     nseg = {"cap": 256, "cap+1": 256, "4cap": 1024}[ties]
     c = _edge_segmax_case(nseg, nseg, extra_tie=(ties == "cap+1"))
     if ties == "4cap":
@@ -1126,6 +1287,8 @@ def test_segmax_fc_bwd_at_the_tie_list_capacity(dev, form, ties, with_db):
     else:
         want = K_TIE_CAP + (1 if ties == "cap+1" else 0)
         assert c['ties'] == want, (c['ties'], want)
+    if order == "permuted":
+        c = _permute_edge_segmax_case(c)
     rc, res, guard_ok = _run_edge_segmax(dev, c, form, with_db=with_db)
     assert rc == 0
     assert guard_ok
