@@ -838,6 +838,43 @@ typedef struct pgnn_merge_job {
 } pgnn_merge_job;
 int pgnn_merge_rows(const pgnn_merge_job *jobs_host, int32_t n_jobs,
                     void *stream);
+/* Two capacity-form frames (graph_gen's deferred_counts) merged into one, on
+ * the device: what batch_data does for host-sized frames, for frames whose
+ * sizes exist only in their count records.  A record is int32 [2 + 2 L]: K,
+ * kd-tree status, then (rows written, rows required) per edge level.
+ *   - points [n_points, 3] / features [n_points, n_feat]: host-known rows; B's
+ *     follow A's at row a->n_points;
+ *   - kp_xyz [kp_cap, 3] / kp_idx [kp_cap]: the first K rows exist; B's rows
+ *     follow A's at row K_A (read from A's record), indices + a->n_points;
+ *   - edges[l] [edge_caps[l], 2] (source, centre), l < n_levels <=
+ *     PGNN_MERGE_MAX_LEVELS: the first `rows written` exist; B's follow A's,
+ *     centres + K_A, sources + a->n_points on level 0 (points -> keypoints)
+ *     and + K_A above it (keypoints -> keypoints).  Lists grouped by ascending
+ *     centre stay grouped;
+ *   - merged->counts: the merged record in the same layout: sums of K, of the
+ *     rows written (as far as the merged capacities hold them) and of the rows
+ *     required, so a frame whose list overflowed its capacity shows in the
+ *     merged record too; status: A's if non-zero, else B's.
+ * Only the first `count` rows of an input are read, rows behind the merged
+ * counts are not written, nothing is read back; one launch.  merged->n_points
+ * must be a->n_points + b->n_points.  words_hint (0: none): the expected
+ * length, in 4-byte words, of the longest list; it sizes the grid only.      */
+#define PGNN_MERGE_MAX_LEVELS 4
+typedef struct pgnn_frame_arrays {
+  int32_t *counts;
+  float *points;
+  float *features;
+  int64_t n_points;
+  float *kp_xyz;
+  int32_t *kp_idx;
+  int64_t kp_cap;
+  int32_t *edges[PGNN_MERGE_MAX_LEVELS];
+  int64_t edge_caps[PGNN_MERGE_MAX_LEVELS];
+} pgnn_frame_arrays;
+int pgnn_merge_frames_dyn(const pgnn_frame_arrays *a_host,
+                          const pgnn_frame_arrays *b_host,
+                          const pgnn_frame_arrays *merged_host, int32_t n_feat,
+                          int32_t n_levels, int64_t words_hint, void *stream);
 /* PointSetPooling edge features [f(src), xyz(src) - xyz(kp(dst)), 0...] as a
  * [n_edges, 16] matrix (gnn.py:256-267).                                     */
 int pgnn_pool_features_fwd(const float *point_features, int32_t n_feat,
@@ -1450,6 +1487,17 @@ int pgnn_kitti_cam_points_voxel_in_image(
  * Every key accepted here leaves results bit-identical (tested).
  * Returns 0, or PGNN_E_INVALID for an unknown key / value out of range.     */
 int pgnn_set_tunable(const char *key, int value);
+/* What the compiler and the occupancy calculator say about one of the 16-row
+ * per-vertex kernels: "vertex_pre_edge", "vertex_update_pre_edge",
+ * "vertex_mlp2" (host-sized form) or the same with "_dyn" (capacity form,
+ * which strides over its tiles and is built for two workgroups per CU).
+ * lds_bytes < 0: the dynamic LDS of that kernel's last launch in this process
+ * (PGNN_E_INVALID when there was none).  Writes the registers per thread, the
+ * scratch bytes per thread, the workgroups of the launch's block size that
+ * fit one CU, and the LDS bytes the answer is for.                           */
+int pgnn_kernel_occupancy(const char *kernel, int64_t lds_bytes,
+                          int32_t *vgprs, int32_t *scratch_bytes,
+                          int32_t *workgroups_per_cu, int64_t *lds_used);
 /* Device buffer for per-tile cycle stamps of the fused kernels
  * (tools/tile_timeline.py, tools/ws_timeline.py); NULL disables.           */
 int pgnn_set_debug_buffer(void *device_ptr);

@@ -46,6 +46,17 @@ class MergeJob(ctypes.Structure):
                 ("add0", c_i32), ("add1", c_i32)]
 
 
+MERGE_MAX_LEVELS = 4   # PGNN_MERGE_MAX_LEVELS
+
+
+class FrameArrays(ctypes.Structure):
+    """struct pgnn_frame_arrays (pgnn_merge_frames_dyn)"""
+    _fields_ = [("counts", c_vp), ("points", c_vp), ("features", c_vp),
+                ("n_points", c_i64), ("kp_xyz", c_vp), ("kp_idx", c_vp),
+                ("kp_cap", c_i64), ("edges", c_vp * MERGE_MAX_LEVELS),
+                ("edge_caps", c_i64 * MERGE_MAX_LEVELS)]
+
+
 class PackJob(ctypes.Structure):
     """One record of pgnn_pack_fc_many's job table."""
     _fields_ = [("w", c_vp), ("b", c_vp), ("dst", c_vp), ("k_in", c_i32),
@@ -352,6 +363,15 @@ _SIGNATURES = {
                                        c_vp, c_vp]),
     "pgnn_relu_mask_mul": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
     "pgnn_merge_rows": (c_i32, [ctypes.POINTER(MergeJob), c_i32, c_vp]),
+    "pgnn_merge_frames_dyn": (c_i32, [ctypes.POINTER(FrameArrays),
+                                      ctypes.POINTER(FrameArrays),
+                                      ctypes.POINTER(FrameArrays), c_i32,
+                                      c_i32, c_i64, c_vp]),
+    "pgnn_kernel_occupancy": (c_i32, [ctypes.c_char_p, c_i64,
+                                      ctypes.POINTER(c_i32),
+                                      ctypes.POINTER(c_i32),
+                                      ctypes.POINTER(c_i32),
+                                      ctypes.POINTER(c_i64)]),
     "pgnn_scatter_max_bwd_f32": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32,
                                          c_i32, c_vp, c_i64, c_vp, c_i64, c_vp,
                                          c_vp, c_i64, c_i32, c_vp]),
@@ -579,6 +599,18 @@ def tag_count(t, count):
 
 def count_of(t):
     return getattr(t, "_pgnn_count", None) if t is not None else None
+
+
+def kernel_occupancy(kernel, lds_bytes=-1):
+    """pgnn_kernel_occupancy -> dict(vgprs, scratch_bytes, workgroups_per_cu,
+    lds_bytes); lds_bytes < 0: that of the kernel's last launch."""
+    v, sc, wg = c_i32(0), c_i32(0), c_i32(0)
+    used = c_i64(0)
+    check(load().pgnn_kernel_occupancy(
+        kernel.encode(), int(lds_bytes), ctypes.byref(v), ctypes.byref(sc),
+        ctypes.byref(wg), ctypes.byref(used)), "pgnn_kernel_occupancy")
+    return {"vgprs": v.value, "scratch_bytes": sc.value,
+            "workgroups_per_cu": wg.value, "lds_bytes": used.value}
 
 
 def set_tunable(key, value):

@@ -12,6 +12,8 @@
 //                   complete segments (sorted edges) and are stored plainly,
 //                   boundary runs use float atomic-max.
 // The E x C activations never reach HBM.
+#include <atomic>
+
 #include "mlp_engine.h"
 #include "edge_ws.h"
 #include "edge_ws_split.h"
@@ -268,8 +270,9 @@ constexpr int kRowSteps = 10;  // 10 x 32 = 320 columns = kMaxTilesPerPass tiles
 __device__ __forceinline__ void consume_rows16(const float *__restrict__ stage,
                                                int ld, int64_t row0,
                                                int rows_valid, int col0,
-                                               int ncols, const RowsArgs &ra) {
-  const int r = threadIdx.x >> 5, c0 = threadIdx.x & 31;
+                                               int ncols, const RowsArgs &ra,
+                                               int tid = (int)threadIdx.x) {
+  const int r = tid >> 5, c0 = tid & 31;
   const int64_t row = row0 + (r < rows_valid ? r : rows_valid - 1);
   float add[kRowSteps];
   if (ra.res) {
@@ -337,8 +340,9 @@ __device__ __forceinline__ void tap_rows16(float *tile, int ld, int64_t row0,
 __device__ __forceinline__ void load_rows16(const float *__restrict__ x,
                                             int64_t ldx, int nx, float *tile,
                                             int ld0, int kc, int64_t row0,
-                                            int rows_valid) {
-  const int r = threadIdx.x >> 5, c0 = threadIdx.x & 31;
+                                            int rows_valid,
+                                            int tid = (int)threadIdx.x) {
+  const int r = tid >> 5, c0 = tid & 31;
   const float *__restrict__ xr =
       x + (row0 + (r < rows_valid ? r : rows_valid - 1)) * ldx;
   for (int cb = 0; cb < kc; cb += 32 * kRowSteps) {
@@ -974,6 +978,13 @@ int launch_fused(const Plan &p, int64_t n_rows, const RowsArgs &ra,
 // waves split the output columns 8 ways (<= 3 column tiles each) and give
 // every SIMD two waves.
 constexpr int kRowsWaves = 8;  // (16 waves: 128 VGPRs, spills, 13 % slower)
+// waves per SIMD with two such workgroups on a CU: what the capacity-form
+// (STRIDE) vertex kernels are compiled for (<= 128 VGPRs)
+constexpr int kRowsWavesPerSimd2 = 2 * kRowsWaves / 4;
+// ... with one weight-prefetch stage fewer than PGNN_PF1: the fourth stage's
+// 16 registers are the difference between 128 and spills, and a second
+// resident workgroup hides more latency than a deeper pipeline of one
+constexpr int kRowsPf2 = PGNN_PF1 < 3 ? PGNN_PF1 : 3;
 
 template <bool TAPS>
 __global__ __launch_bounds__(64 * kRowsWaves) void rows_mlp_kernel(
@@ -1887,12 +1898,14 @@ struct PreEdgeArgs {
 // What vertex_pre_edge_kernel does once the tile holds [h | x | 0] (and the
 // workgroup has met at a barrier): offset chain, Q, P.  Shared with the fused
 // update + pre-edge kernel below.
+template <int PF>
 __device__ __forceinline__ void pre_edge_tail(const ChainDev &off,
                                               const LayerDev &pl,
                                               const PreEdgeArgs &a, float *tile,
                                               float *scratch, float *stage,
                                               int64_t row0, int rows_valid,
-                                              int wave, int lane, KrowPre &pre) {
+                                              int wave, int lane,
+                                              KrowPreT<PF> &pre, int tid) {
   // (`pre`: krow_prefetch of the first pass below -- off.l[0], or pl without
   // an offset chain)
   // offset chain: first layer reads the h columns of the tile (its packed
@@ -1911,7 +1924,7 @@ __device__ __forceinline__ void pre_edge_tail(const ChainDev &off,
   // Q = (x + delta) @ wx, the same expression as offset_apply_kernel; thread
   // (r, c0) as in consume_rows16, the three wx rows requested up front
   {
-    const int r = threadIdx.x >> 5, c0 = threadIdx.x & 31;
+    const int r = tid >> 5, c0 = tid & 31;
     const int ldq = (int)a.ld_pq;  // <= 320
     const int64_t row = row0 + (r < rows_valid ? r : rows_valid - 1);
     float x0 = a.xyz[row * 3], x1 = a.xyz[row * 3 + 1], x2 = a.xyz[row * 3 + 2];
@@ -1943,11 +1956,11 @@ __device__ __forceinline__ void pre_edge_tail(const ChainDev &off,
   RowsArgs ra = {};
   ra.y = a.P;
   ra.ldy = a.ld_pq;
-  consume_rows16(stage, ld_st, row0, rows_valid, 0, 16 * pl.nt, ra);
+  consume_rows16(stage, ld_st, row0, rows_valid, 0, 16 * pl.nt, ra, tid);
 }
 
 template <bool STRIDE>
-__global__ __launch_bounds__(64 * kRowsWaves) void vertex_pre_edge_kernel(
+__global__ __launch_bounds__(64 * kRowsWaves, STRIDE ? kRowsWavesPerSimd2 : 1) void vertex_pre_edge_kernel(
     ChainDev off, LayerDev pl, PreEdgeArgs a) {
   constexpr int ROWS = 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1967,16 +1980,17 @@ __global__ __launch_bounds__(64 * kRowsWaves) void vertex_pre_edge_kernel(
   for (int64_t row0 = (int64_t)blockIdx.x * ROWS; row0 < n_rows;
        row0 += STRIDE ? (int64_t)gridDim.x * ROWS : n_rows) {
     const int lane = opaque_lane(lane_id);
+    const int tid = STRIDE ? opaque_lane(threadIdx.x) : (int)threadIdx.x;
   const int rows_valid =
       (int)((n_rows - row0 < ROWS) ? (n_rows - row0) : ROWS);
   const int kc = 16 * pl.kq;
-  KrowPre pre;
+  KrowPreT<STRIDE ? kRowsPf2 : PGNN_PF1> pre;
   krow_prefetch(off.n > 0 ? off.l[0] : pl, 0, wave, lane, pre);
   {
     // 32 threads per row; unconditional clamped loads, select on the value,
     // all in flight before the first LDS write (see load_rows16)
     static_assert(64 * kRowsWaves == 32 * ROWS, "one 32-thread group per row");
-    const int r = threadIdx.x >> 5, c0 = threadIdx.x & 31;
+    const int r = tid >> 5, c0 = tid & 31;
     const int64_t rowc = row0 + (r < rows_valid ? r : rows_valid - 1);
     const float *__restrict__ hr = a.h + rowc * a.ld_h;
     const float *__restrict__ xr = a.xyz + rowc * 3;
@@ -2002,12 +2016,12 @@ __global__ __launch_bounds__(64 * kRowsWaves) void vertex_pre_edge_kernel(
   }
   // lowest() rows of the aggregation buffer the edge kernel maxes into
   if (a.agg) {
-    for (int idx = threadIdx.x; idx < rows_valid * (int)a.ld_agg; idx += 64 * kRowsWaves)
+    for (int idx = tid; idx < rows_valid * (int)a.ld_agg; idx += 64 * kRowsWaves)
       a.agg[row0 * a.ld_agg + idx] = kFloatLowest;
   }
   __syncthreads();
   pre_edge_tail(off, pl, a, tile, scratch, stage, row0, rows_valid, wave, lane,
-                pre);
+                pre, tid);
   if (STRIDE) __syncthreads();  // the next tile overwrites tile / scratch / stage
   }
 }
@@ -2045,9 +2059,11 @@ struct FrontArgs {
 // dimension lds_ld(16 kq0)); its last layer's activated output lands in `stage`
 // (`pre`: krow_prefetch of front.l[0]; comes back holding `after`'s, the first
 // layer of whatever follows the front chain)
+template <int PF>
 __device__ __forceinline__ void front_chain(const ChainDev &front, float *tile,
                                             float *stage, int ld_stage,
-                                            int wave, int lane, KrowPre &pre,
+                                            int wave, int lane,
+                                            KrowPreT<PF> &pre,
                                             const LayerDev after,
                                             long long *tsw, int &n_stamp) {
   for (int li = 0; li + 1 < front.n; ++li) {
@@ -2066,7 +2082,7 @@ __device__ __forceinline__ void front_chain(const ChainDev &front, float *tile,
 }
 
 template <bool STRIDE>
-__global__ __launch_bounds__(64 * kRowsWaves) void vertex_update_pre_edge_kernel(
+__global__ __launch_bounds__(64 * kRowsWaves, STRIDE ? kRowsWavesPerSimd2 : 1) void vertex_update_pre_edge_kernel(
     ChainDev front, FrontArgs f, ChainDev off, LayerDev pl, PreEdgeArgs a) {
   constexpr int ROWS = 16;
   static_assert(64 * kRowsWaves == 32 * ROWS, "one 32-thread group per row");
@@ -2099,15 +2115,16 @@ __global__ __launch_bounds__(64 * kRowsWaves) void vertex_update_pre_edge_kernel
   for (int64_t row0 = (int64_t)blockIdx.x * ROWS; row0 < n_rows;
        row0 += STRIDE ? (int64_t)gridDim.x * ROWS : n_rows) {
     const int lane = opaque_lane(lane_id);
+    const int tid = STRIDE ? opaque_lane(threadIdx.x) : (int)threadIdx.x;
     const int rows_valid =
         (int)((n_rows - row0 < ROWS) ? (n_rows - row0) : ROWS);
     stamp();  // 0: entry
-    KrowPre pre;
+    KrowPreT<STRIDE ? kRowsPf2 : PGNN_PF1> pre;
     krow_prefetch(front.l[0], 0, wave, lane, pre);
-    load_rows16(f.x, f.ldx, f.nx, tile, lds_ld(kc0), kc0, row0, rows_valid);
+    load_rows16(f.x, f.ldx, f.nx, tile, lds_ld(kc0), kc0, row0, rows_valid, tid);
     // lowest() rows of the aggregation buffer the NEXT edge kernel maxes into
     if (a.agg) {
-      for (int idx = threadIdx.x; idx < rows_valid * (int)a.ld_agg;
+      for (int idx = tid; idx < rows_valid * (int)a.ld_agg;
            idx += 64 * kRowsWaves)
         a.agg[row0 * a.ld_agg + idx] = kFloatLowest;
     }
@@ -2120,7 +2137,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void vertex_update_pre_edge_kernel
     // -- exactly what vertex_pre_edge_kernel would have read back.  Thread
     // (r, c0) as in consume_rows16; kc <= 320.
     {
-      const int r = threadIdx.x >> 5, c0 = threadIdx.x & 31;
+      const int r = tid >> 5, c0 = tid & 31;
       const int64_t row = row0 + (r < rows_valid ? r : rows_valid - 1);
       float add[kRowSteps];
       if (f.res) {
@@ -2156,7 +2173,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void vertex_update_pre_edge_kernel
     __syncthreads();
     stamp();  // y written, tile refilled
     pre_edge_tail(off, pl, a, tile, scratch, stage, row0, rows_valid, wave, lane,
-                  pre);
+                  pre, tid);
     stamp();  // offset chain + Q + P
     if (STRIDE) __syncthreads();
   }
@@ -2166,7 +2183,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void vertex_update_pre_edge_kernel
 // front chain (+ residual) -> y, then a second chain on y -> out (the last
 // update MLP and the predictor heads)
 template <bool STRIDE>
-__global__ __launch_bounds__(64 * kRowsWaves) void vertex_mlp2_kernel(
+__global__ __launch_bounds__(64 * kRowsWaves, STRIDE ? kRowsWavesPerSimd2 : 1) void vertex_mlp2_kernel(
     ChainDev front, FrontArgs f, ChainDev back, RowsArgs out, int64_t n_rows,
     const int32_t *n_dev) {
   constexpr int ROWS = 16;
@@ -2186,11 +2203,12 @@ __global__ __launch_bounds__(64 * kRowsWaves) void vertex_mlp2_kernel(
   for (int64_t row0 = (int64_t)blockIdx.x * ROWS; row0 < n_rows;
        row0 += STRIDE ? (int64_t)gridDim.x * ROWS : n_rows) {
     const int lane = opaque_lane(lane_id);
+    const int tid = STRIDE ? opaque_lane(threadIdx.x) : (int)threadIdx.x;
     const int rows_valid =
         (int)((n_rows - row0 < ROWS) ? (n_rows - row0) : ROWS);
-    KrowPre pre;
+    KrowPreT<STRIDE ? kRowsPf2 : PGNN_PF1> pre;
     krow_prefetch(front.l[0], 0, wave, lane, pre);
-    load_rows16(f.x, f.ldx, f.nx, tile, lds_ld(kc0), kc0, row0, rows_valid);
+    load_rows16(f.x, f.ldx, f.nx, tile, lds_ld(kc0), kc0, row0, rows_valid, tid);
     __syncthreads();
     int no_stamp = 0;
     front_chain(front, tile, stage, f.ld_stage, wave, lane, pre, back.l[0],
@@ -2199,7 +2217,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void vertex_mlp2_kernel(
     // are zero beyond k_in; rows_mlp_kernel zero-fills the same way)
     const int kmax = kcb > ncols_y ? kcb : ncols_y;  // <= 320
     {
-      const int r = threadIdx.x >> 5, c0 = threadIdx.x & 31;
+      const int r = tid >> 5, c0 = tid & 31;
       const int64_t row = row0 + (r < rows_valid ? r : rows_valid - 1);
       float add[kRowSteps];
       if (f.res) {
@@ -2236,7 +2254,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void vertex_mlp2_kernel(
     const int ld_st = lds_ld(16 * L.nt);
     krow_pass(tile, lds_ld(16 * L.kq), stage, ld_st, L, 0, wave, lane, pre,
               false, L, 0);
-    consume_rows16(stage, ld_st, row0, rows_valid, 0, 16 * L.nt, out);
+    consume_rows16(stage, ld_st, row0, rows_valid, 0, 16 * L.nt, out, tid);
     if (STRIDE) __syncthreads();
   }
 }
@@ -2244,6 +2262,10 @@ __global__ __launch_bounds__(64 * kRowsWaves) void vertex_mlp2_kernel(
 }  // namespace
 
 namespace {
+// dynamic LDS of each vertex kernel's last launch (pgnn_kernel_occupancy):
+// [pre_edge, update_pre_edge, mlp2][host-sized, capacity form]
+std::atomic<int64_t> g_vertex_lds[3][2] = {{{-1}, {-1}}, {{-1}, {-1}}, {{-1}, {-1}}};
+
 // What the two entries that end in pre_edge_tail share: the P layer, the offset
 // chain with the LDS scratch its activations need, and the kernel's arguments
 // but h / ld_h.  name: the entry's, for the messages; kq_max: the widest
@@ -2326,6 +2348,7 @@ int pre_edge_impl(
       (size_t)16 * (a.ld_tile + a.ld_scratch + lds_ld(16 * pl.nt)) * 4;
   PGNN_REQUIRE(lds <= 160 * 1024, PGNN_E_UNSUPPORTED,
                "vertex_pre_edge: layer too wide for the LDS tile");
+  g_vertex_lds[0][dk.dev ? 1 : 0] = (int64_t)lds;
   return launch_lds(
       dk.dev ? vertex_pre_edge_kernel<true> : vertex_pre_edge_kernel<false>,
       dim3((unsigned)dyn_grid_tiles(dk, n_vertices)), dim3(64 * kRowsWaves), lds,
@@ -2403,6 +2426,7 @@ int update_pre_edge_impl(
   const size_t lds = (size_t)16 * (f.ld_buf + a.ld_scratch + f.ld_stage) * 4;
   PGNN_REQUIRE(lds <= 160 * 1024, PGNN_E_UNSUPPORTED,
                "vertex_update_pre_edge: layers too wide for the LDS tile");
+  g_vertex_lds[1][dk.dev ? 1 : 0] = (int64_t)lds;
   return launch_lds(dk.dev ? vertex_update_pre_edge_kernel<true>
                            : vertex_update_pre_edge_kernel<false>,
                     dim3((unsigned)dyn_grid_tiles(dk, n_vertices)),
@@ -2445,6 +2469,7 @@ int mlp2_impl(const float *x, int64_t ld_x, int32_t nx,
   const size_t lds = (size_t)16 * (f.ld_buf + f.ld_stage) * 4;
   PGNN_REQUIRE(lds <= 160 * 1024, PGNN_E_UNSUPPORTED,
                "mlp2: layers too wide for the LDS tile");
+  g_vertex_lds[2][dk.dev ? 1 : 0] = (int64_t)lds;
   return launch_lds(dk.dev ? vertex_mlp2_kernel<true> : vertex_mlp2_kernel<false>,
                     dim3((unsigned)dyn_grid_tiles(dk, n_rows)),
                     dim3(64 * kRowsWaves), lds, stream, pf.chain, f, pb.chain,
@@ -2541,6 +2566,55 @@ extern "C" int pgnn_vertex_pre_edge_fwd_dyn(
   return pre_edge_impl(h, ld_h, c, xyz, offset_layers, n_offset_layers, p_layer,
                        wx, vertices_cap, P, Q, ld_pq, agg, ld_agg,
                        (hipStream_t)stream_, dyn_of(n_vertices));
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_kernel_occupancy(const char *kernel, int64_t lds_bytes,
+                                     int32_t *vgprs, int32_t *scratch_bytes,
+                                     int32_t *workgroups_per_cu,
+                                     int64_t *lds_used) {
+  PGNN_GUARD_BEGIN
+  PGNN_REQUIRE(kernel && vgprs && scratch_bytes && workgroups_per_cu,
+               PGNN_E_INVALID, "kernel_occupancy: null argument");
+  const std::string name(kernel);
+  const struct {
+    const char *name;
+    const void *fn[2];
+  } table[3] = {
+      {"vertex_pre_edge",
+       {reinterpret_cast<const void *>(vertex_pre_edge_kernel<false>),
+        reinterpret_cast<const void *>(vertex_pre_edge_kernel<true>)}},
+      {"vertex_update_pre_edge",
+       {reinterpret_cast<const void *>(vertex_update_pre_edge_kernel<false>),
+        reinterpret_cast<const void *>(vertex_update_pre_edge_kernel<true>)}},
+      {"vertex_mlp2",
+       {reinterpret_cast<const void *>(vertex_mlp2_kernel<false>),
+        reinterpret_cast<const void *>(vertex_mlp2_kernel<true>)}},
+  };
+  for (int i = 0; i < 3; ++i)
+    for (int dyn = 0; dyn < 2; ++dyn) {
+      if (name != std::string(table[i].name) + (dyn ? "_dyn" : "")) continue;
+      if (lds_bytes < 0) lds_bytes = g_vertex_lds[i][dyn];
+      PGNN_REQUIRE(lds_bytes >= 0 && lds_bytes <= 160 * 1024, PGNN_E_INVALID,
+                   "kernel_occupancy: no launch of this kernel yet, or more "
+                   "LDS than a CU has");
+      if (lds_bytes) {
+        const int rc = ensure_dynamic_lds(table[i].fn[dyn], (size_t)lds_bytes);
+        if (rc) return rc;
+      }
+      hipFuncAttributes attr;
+      PGNN_HIP(hipFuncGetAttributes(&attr, table[i].fn[dyn]));
+      int blocks = 0;
+      PGNN_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          &blocks, table[i].fn[dyn], 64 * kRowsWaves, (size_t)lds_bytes));
+      *vgprs = attr.numRegs;
+      *scratch_bytes = (int32_t)attr.localSizeBytes;
+      *workgroups_per_cu = blocks;
+      if (lds_used) *lds_used = lds_bytes;
+      return 0;
+    }
+  PGNN_REQUIRE(false, PGNN_E_INVALID, "kernel_occupancy: unknown kernel");
+  return 0;
   PGNN_GUARD_END
 }
 

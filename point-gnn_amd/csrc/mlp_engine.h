@@ -753,7 +753,7 @@ __device__ __forceinline__ void layer_pass(const float *in, int ld_in, float *ou
 // of a 24k-cycle pass (tools/krow_timeline.py; ablation without weight loads:
 // 20.7k).  Neither depends on the activations, so both are requested a pass
 // EARLY: `krow_prefetch` asks for a layer's bias values and the weight
-// fragments of its first PGNN_PF1 K-groups; a pass consumes the set requested
+// fragments of its first PF K-groups; a pass consumes the set requested
 // for it and, right after its own K loop (before its barriers and store),
 // requests the next pass's.  Same MFMA sequence per output element as
 // gemm_tile / store_acc: bit-identical results.
@@ -764,14 +764,19 @@ constexpr int kKrowNT = 3;  // column tiles per wave: 20 tiles over 8 waves
 // stages in it -- no copies (a member-by-member copy into a local pipeline
 // array is turned into wide vector loads from the struct, which then cannot
 // be promoted out of scratch memory).
-struct KrowPre {
-  v4f b[PGNN_PF1][kKrowNT];
+// (PF: register stages.  PGNN_PF1 everywhere but in the capacity-form vertex
+// kernels, which run two workgroups per CU and give a stage up for that.)
+template <int PF>
+struct KrowPreT {
+  v4f b[PF][kKrowNT];
   float bias[kKrowNT];
 };
+using KrowPre = KrowPreT<PGNN_PF1>;
 
+template <int PF>
 __device__ __forceinline__ void krow_prefetch_w(const LayerDev &L, int t0,
                                                 int wave, int lane,
-                                                KrowPre &p) {
+                                                KrowPreT<PF> &p) {
   const v4f *__restrict__ wp = reinterpret_cast<const v4f *>(L.wp) + lane;
   const int qstride = L.nt * 64;
 #pragma unroll
@@ -779,16 +784,17 @@ __device__ __forceinline__ void krow_prefetch_w(const LayerDev &L, int t0,
     int t = t0 + wave + 8 * j;
     if (t > L.nt - 1) t = L.nt - 1;  // clamp: something valid, discarded later
 #pragma unroll
-    for (int st = 0; st < PGNN_PF1; ++st) {
+    for (int st = 0; st < PF; ++st) {
       const int q = st < L.kq ? st : L.kq - 1;
       p.b[st][j] = wp[(size_t)q * qstride + t * 64];
     }
   }
 }
 
+template <int PF>
 __device__ __forceinline__ void krow_prefetch_bias(const LayerDev &L, int t0,
                                                    int wave, int lane,
-                                                   KrowPre &p) {
+                                                   KrowPreT<PF> &p) {
   const float *__restrict__ bias = L.wp + (size_t)L.kq * L.nt * 256;
 #pragma unroll
   for (int j = 0; j < kKrowNT; ++j) {
@@ -798,32 +804,24 @@ __device__ __forceinline__ void krow_prefetch_bias(const LayerDev &L, int t0,
   }
 }
 
+template <int PF>
 __device__ __forceinline__ void krow_prefetch(const LayerDev &L, int t0, int wave,
-                                              int lane, KrowPre &p) {
+                                              int lane, KrowPreT<PF> &p) {
   krow_prefetch_w(L, t0, wave, lane, p);
   krow_prefetch_bias(L, t0, wave, lane, p);
 }
 
-template <int NT>
-__device__ __forceinline__ void layer_pass_krow(const float *in, int ld_in,
-                                                float *out, int ld_out,
-                                                const LayerDev &L, int t0,
-                                                int wave, int lane, KrowPre &pre,
-                                                bool has_next,
-                                                const LayerDev next,
-                                                int next_t0) {
-  constexpr int PF = PGNN_PF1, NW = 8;
+// The K loop of one pass for a wave with NT column tiles (0: a wave without a
+// column tile in this pass -- narrow layers -- only keeps the workgroup's
+// barriers and the prefetch chain going).  Consumes `pre.b` in place.
+template <int NT, int PF>
+__device__ __forceinline__ void krow_gemm(const float *in, int ld_in,
+                                          const LayerDev &L, int t0, int wave,
+                                          int lane, KrowPreT<PF> &pre,
+                                          v4f (&acc)[kKrowNT]) {
+  constexpr int NW = 8;
   static_assert(NT <= kKrowNT, "prefetch slots");
-  if constexpr (NT == 0) {
-    // a wave without a column tile in this pass (narrow layers): it only
-    // keeps the workgroup's barriers and the prefetch chain going
-    if (has_next) krow_prefetch_w(next, next_t0, wave, lane, pre);
-    __syncthreads();
-    if (has_next) krow_prefetch_bias(next, next_t0, wave, lane, pre);
-    __syncthreads();
-    return;
-  } else {
-  v4f acc[NT];
+  if constexpr (NT > 0) {
   int toff[NT];
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
@@ -870,13 +868,46 @@ __device__ __forceinline__ void layer_pass_krow(const float *in, int ld_in,
               a[st][s], pre.b[st][j][s], acc[j], 0, 0, 0);
     }
   }
+  }
+}
+
+// one pass (<= 320 output columns from column tile t0) of layer L on the
+// 16-row tile; `pre` holds what krow_prefetch requested for (L, t0) and comes
+// back holding the request for (next, next_t0) when has_next.  (`next` by
+// value: a pointer to an element of a by-value kernel argument would force the
+// whole argument struct into scratch memory.)
+template <int PF>
+__device__ __forceinline__ void krow_pass(const float *in, int ld_in, float *out,
+                                          int ld_out, const LayerDev &L, int t0,
+                                          int wave, int lane, KrowPreT<PF> &pre,
+                                          bool has_next, const LayerDev next,
+                                          int next_t0) {
+  constexpr int NW = 8;
+  int tiles = L.nt - t0;
+  if (tiles > kMaxTilesPerPass) tiles = kMaxTilesPerPass;
+  // column tiles of THIS wave (t0 + wave + 8 j < L.nt; wave-uniform): 19 tiles
+  // are 3-3-3-2-2-2-2-2, i.e. 5-5-5-4 per SIMD.  (With ceil(tiles / 8) for
+  // every wave the five waves without a third tile computed a clamped one and
+  // threw it away: 6 tiles of MFMA issue per SIMD instead of 5.)
+  // Only the K loop is specialised on that count: the prefetch of the next
+  // pass and the store are ONE copy behind the switch, so `pre` is one set of
+  // registers wherever it is live (a copy per case cost the capacity-form
+  // vertex kernels a second set, and spills at 128 VGPRs).
+  const int ntw = tiles / 8 + (wave < tiles % 8 ? 1 : 0);
+  v4f acc[kKrowNT];
+  switch (ntw) {
+    case 0: krow_gemm<0>(in, ld_in, L, t0, wave, lane, pre, acc); break;
+    case 1: krow_gemm<1>(in, ld_in, L, t0, wave, lane, pre, acc); break;
+    case 2: krow_gemm<2>(in, ld_in, L, t0, wave, lane, pre, acc); break;
+    default: krow_gemm<3>(in, ld_in, L, t0, wave, lane, pre, acc); break;
+  }
   // the next pass's first weight fragments: requested now, used two barriers on
   if (has_next) krow_prefetch_w(next, next_t0, wave, lane, pre);
   __syncthreads();  // every wave is done reading `in` (in-place overwrite)
 #pragma unroll
-  for (int j = 0; j < NT; ++j) {
+  for (int j = 0; j < kKrowNT; ++j) {
     const int t = t0 + wave + NW * j;
-    if (t < L.nt && t - t0 < kMaxTilesPerPass) {
+    if (t < L.nt && t - t0 < kMaxTilesPerPass) {  // <=> j < ntw
       const int col = t * 16 + (lane & 15);
       const bool relu = col >= L.relu_from;
       const float bv = pre.bias[j];
@@ -892,32 +923,6 @@ __device__ __forceinline__ void layer_pass_krow(const float *in, int ld_in,
   // ... and its bias values, now that this pass's are used
   if (has_next) krow_prefetch_bias(next, next_t0, wave, lane, pre);
   __syncthreads();
-  }
-}
-
-// one pass (<= 320 output columns from column tile t0) of layer L on the
-// 16-row tile; `pre` holds what krow_prefetch requested for (L, t0) and comes
-// back holding the request for (next, next_t0) when has_next.  (`next` by
-// value: a pointer to an element of a by-value kernel argument would force the
-// whole argument struct into scratch memory.)
-__device__ __forceinline__ void krow_pass(const float *in, int ld_in, float *out,
-                                          int ld_out, const LayerDev &L, int t0,
-                                          int wave, int lane, KrowPre &pre,
-                                          bool has_next, const LayerDev next,
-                                          int next_t0) {
-  int tiles = L.nt - t0;
-  if (tiles > kMaxTilesPerPass) tiles = kMaxTilesPerPass;
-  // column tiles of THIS wave (t0 + wave + 8 j < L.nt; wave-uniform): 19 tiles
-  // are 3-3-3-2-2-2-2-2, i.e. 5-5-5-4 per SIMD.  (With ceil(tiles / 8) for
-  // every wave the five waves without a third tile computed a clamped one and
-  // threw it away: 6 tiles of MFMA issue per SIMD instead of 5.)
-  const int ntw = tiles / 8 + (wave < tiles % 8 ? 1 : 0);
-  switch (ntw) {
-    case 0: layer_pass_krow<0>(in, ld_in, out, ld_out, L, t0, wave, lane, pre, has_next, next, next_t0); break;
-    case 1: layer_pass_krow<1>(in, ld_in, out, ld_out, L, t0, wave, lane, pre, has_next, next, next_t0); break;
-    case 2: layer_pass_krow<2>(in, ld_in, out, ld_out, L, t0, wave, lane, pre, has_next, next, next_t0); break;
-    default: layer_pass_krow<3>(in, ld_in, out, ld_out, L, t0, wave, lane, pre, has_next, next, next_t0); break;
-  }
 }
 
 template <int MSUB, bool TRANSPOSED, int NW = 4>

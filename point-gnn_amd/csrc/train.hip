@@ -1730,6 +1730,147 @@ extern "C" int pgnn_merge_rows(const pgnn_merge_job *jobs_host, int32_t n_jobs,
   PGNN_GUARD_END
 }
 
+// ---- two capacity-form frames merged into one (inference on frame pairs) --------
+// What batch_data does for host-sized training frames, for two frames whose
+// sizes exist only in their FrameCounts records (K, status, then (rows written,
+// rows required) per level): frame B's rows follow frame A's ACTUAL rows, so
+// the merged arrays are capacity-form arrays again and the merged record has
+// the same layout.  blockIdx.y = 2 * array + frame; every block reads the
+// counts it needs itself and strides over its array, so nothing is read back
+// and one launch does all of it.  Only the first `count` rows of a
+// capacity-form input are read; rows behind the merged counts are not written.
+namespace {
+struct MergeFramesArgs {
+  pgnn_frame_arrays a, b, m;
+  int n_feat, n_levels;
+};
+
+// rows of a list the merged list takes: (from A, from B), clipped to the
+// capacities so that no index leaves an array whatever the records hold
+__device__ __forceinline__ void merge_split(int64_t na, int64_t cap_a,
+                                            int64_t nb, int64_t cap_b,
+                                            int64_t cap_m, int64_t &ta,
+                                            int64_t &tb) {
+  ta = na < 0 ? 0 : (na < cap_a ? na : cap_a);
+  if (ta > cap_m) ta = cap_m;
+  tb = nb < 0 ? 0 : (nb < cap_b ? nb : cap_b);
+  if (tb > cap_m - ta) tb = cap_m - ta;
+}
+
+__global__ void merge_frames_kernel(MergeFramesArgs g) {
+  const int arr = blockIdx.y >> 1, second = blockIdx.y & 1;
+  const pgnn_frame_arrays &f = second ? g.b : g.a;
+  int64_t ka, kb;
+  merge_split(g.a.counts[0], g.a.kp_cap, g.b.counts[0], g.b.kp_cap, g.m.kp_cap,
+              ka, kb);
+  const int64_t n_a = g.a.n_points;
+  const int32_t *src = nullptr;
+  int32_t *dst = nullptr;
+  int64_t n_words = 0;
+  int32_t add0 = 0, add1 = 0;
+  if (arr == 0) {  // level-0 coordinates: host-known rows
+    src = (const int32_t *)f.points;
+    dst = (int32_t *)g.m.points + (second ? 3 * n_a : 0);
+    n_words = 3 * f.n_points;
+  } else if (arr == 1) {  // level-0 features
+    src = (const int32_t *)f.features;
+    dst = (int32_t *)g.m.features + (second ? g.n_feat * n_a : 0);
+    n_words = (int64_t)g.n_feat * f.n_points;
+  } else if (arr == 2) {  // keypoint coordinates
+    src = (const int32_t *)f.kp_xyz;
+    dst = (int32_t *)g.m.kp_xyz + (second ? 3 * ka : 0);
+    n_words = 3 * (second ? kb : ka);
+  } else if (arr == 3) {  // keypoint indices: into the merged cloud
+    src = f.kp_idx;
+    dst = g.m.kp_idx + (second ? ka : 0);
+    n_words = second ? kb : ka;
+    add0 = add1 = second ? (int32_t)n_a : 0;
+  } else {  // edge rows (source, centre)
+    const int l = arr - 4;
+    int64_t ea, eb;
+    merge_split(g.a.counts[2 + 2 * l], g.a.edge_caps[l],
+                g.b.counts[2 + 2 * l], g.b.edge_caps[l], g.m.edge_caps[l], ea,
+                eb);
+    src = f.edges[l];
+    dst = g.m.edges[l] + (second ? 2 * ea : 0);
+    n_words = 2 * (second ? eb : ea);
+    if (second) {
+      add0 = l == 0 ? (int32_t)n_a : (int32_t)ka;  // level 0 gathers points
+      add1 = (int32_t)ka;
+    }
+    if (!second && l == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+      // the merged record, by one thread of the launch
+      g.m.counts[0] = (int32_t)(ka + kb);
+      g.m.counts[1] = g.a.counts[1] ? g.a.counts[1] : g.b.counts[1];
+      for (int j = 0; j < g.n_levels; ++j) {
+        int64_t wa, wb;
+        merge_split(g.a.counts[2 + 2 * j], g.a.edge_caps[j],
+                    g.b.counts[2 + 2 * j], g.b.edge_caps[j], g.m.edge_caps[j],
+                    wa, wb);
+        g.m.counts[2 + 2 * j] = (int32_t)(wa + wb);
+        // rows REQUIRED: a frame that overflowed (or a merged list that
+        // does not fit) shows as required > written in the merged record too
+        g.m.counts[3 + 2 * j] =
+            g.a.counts[3 + 2 * j] + g.b.counts[3 + 2 * j];
+      }
+    }
+  }
+  if (arr == 0 || arr == 1 || arr == 2) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words;
+         i += (int64_t)gridDim.x * blockDim.x)
+      dst[i] = src[i];
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words;
+         i += (int64_t)gridDim.x * blockDim.x)
+      dst[i] = src[i] + ((i & 1) ? add1 : add0);
+  }
+}
+}  // namespace
+
+extern "C" int pgnn_merge_frames_dyn(const pgnn_frame_arrays *a,
+                                     const pgnn_frame_arrays *b,
+                                     const pgnn_frame_arrays *merged,
+                                     int32_t n_feat, int32_t n_levels,
+                                     int64_t words_hint, void *stream_) {
+  PGNN_GUARD_BEGIN
+  PGNN_REQUIRE(a && b && merged && n_feat >= 0 && n_levels >= 1 &&
+                   n_levels <= PGNN_MERGE_MAX_LEVELS,
+               PGNN_E_INVALID, "merge_frames_dyn: bad argument");
+  MergeFramesArgs g = {*a, *b, *merged, n_feat, n_levels};
+  int64_t longest = 1;
+  for (const pgnn_frame_arrays *f : {a, b}) {
+    PGNN_REQUIRE(f->counts && f->n_points > 0 && f->points &&
+                     (n_feat == 0 || f->features) && f->kp_xyz && f->kp_idx &&
+                     f->kp_cap > 0,
+                 PGNN_E_INVALID, "merge_frames_dyn: null input");
+    for (int l = 0; l < n_levels; ++l) {
+      PGNN_REQUIRE(f->edges[l] && f->edge_caps[l] > 0, PGNN_E_INVALID,
+                   "merge_frames_dyn: null edge list");
+      if (2 * f->edge_caps[l] > longest) longest = 2 * f->edge_caps[l];
+    }
+    if (f->n_points * (n_feat > 3 ? n_feat : 3) > longest)
+      longest = f->n_points * (n_feat > 3 ? n_feat : 3);
+  }
+  PGNN_REQUIRE(merged->counts && merged->points && merged->kp_xyz &&
+                   merged->kp_idx && (n_feat == 0 || merged->features) &&
+                   merged->n_points == a->n_points + b->n_points &&
+                   merged->kp_cap > 0 &&
+                   merged->n_points <= (int64_t)INT32_MAX,
+               PGNN_E_INVALID, "merge_frames_dyn: bad output");
+  for (int l = 0; l < n_levels; ++l)
+    PGNN_REQUIRE(merged->edges[l] && merged->edge_caps[l] > 0, PGNN_E_INVALID,
+                 "merge_frames_dyn: null output edge list");
+  // the grid is sized for the expected longest list (words_hint; the
+  // capacities without one) and strides over whatever the counts turn out to be
+  if (words_hint > 0 && words_hint < longest) longest = words_hint;
+  hipLaunchKernelGGL(merge_frames_kernel,
+                     dim3(grid_for(longest, 1024), (unsigned)(2 * (4 + n_levels))),
+                     dim3(256), 0, (hipStream_t)stream_, g);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+  PGNN_GUARD_END
+}
+
 extern "C" int pgnn_relu_mask_mul(float *dY, const float *Y, int64_t count,
                                   void *stream_) {
   PGNN_GUARD_BEGIN

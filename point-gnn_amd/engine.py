@@ -98,13 +98,21 @@ class DeferredFrame(object):
     the graph builder and the model ran without the host reading K or an edge
     count.  `result()` is the frame's one host read: it waits for the frame,
     learns (K, E0, E1, ...), and returns (logits [K, nc], box_encodings
-    [K, nc, len]) -- views of the capacity-sized outputs."""
+    [K, nc, len]) -- views of the capacity-sized outputs.
 
-    def __init__(self, engine, xyz, intensity, logits, boxes, counts):
+    A frame that ran as half of a pair (run_frames_on_streams,
+    frames_per_pass=2) holds the PASS's outputs and `pair`, the FrameCounts of
+    both halves in row order: its rows follow the first half's K rows when it
+    is the second, and if either half overflowed a capacity both are rebuilt
+    singly."""
+
+    def __init__(self, engine, xyz, intensity, logits, boxes, counts,
+                 pair=None):
         self.engine = engine
         self.xyz, self.intensity = xyz, intensity
         self.logits, self.boxes = logits, boxes
         self.counts = counts
+        self.pair = pair
         self._out = None
 
     def result(self, host_counts=None):
@@ -123,9 +131,16 @@ class DeferredFrame(object):
             # with host-read sizes
             eng.deferred_overflows += 1
             self._out = eng.run_frame(self.xyz, self.intensity)
+        elif self.pair is not None and any(p.overflowed for p in self.pair):
+            # the other half of the pass lost rows, so the pass's edge lists
+            # are not this frame's either
+            self._out = eng.run_frame(self.xyz, self.intensity)
         else:
             eng.frame_shapes.append((k,) + tuple(edges))
-            self._out = (self.logits[:k], self.boxes[:k])
+            r0 = 0
+            if self.pair is not None and self.pair[0] is not c:
+                r0 = self.pair[0].k
+            self._out = (self.logits[r0:r0 + k], self.boxes[r0:r0 + k])
         return self._out
 
 
@@ -228,6 +243,57 @@ class InferenceEngine(object):
         self.last_graph = graph
         return DeferredFrame(self, xyz, intensity, logits, boxes,
                              edges[0]._pgnn_count.frame)
+
+    def _pairs_apply(self):
+        """Frame pairs (run_frames_on_streams) need size hints, the fp32 edge
+        stage (the 16-bit secondaries keep the single-frame path), the
+        multi-level generator without a fan-in cap, and ONE pooling level,
+        the first (graph_gen.merge_frames_dyn)."""
+        if self._hints is None or self.model.edge_arith != 'f32' or \
+                self.graph_fn is not graph_gen.gen_multi_level_local_graph_v3:
+            return False
+        # the one-launch per-vertex kernels take 32 rows per CU at the most
+        # (gnn.hip: update_pre_edge_impl); a pair beyond that would fall
+        # back to separate launches and lose what it is for
+        cus = torch.cuda.get_device_properties(
+            torch.cuda.current_device()).multi_processor_count
+        if 2 * self._hints.k > 32 * cus:
+            return False
+        levels = self.graph_kwargs.get('level_configs') or []
+        if not 1 <= len(levels) <= 4 or \
+                self.graph_kwargs.get('add_rnd3d', False):
+            return False
+        scales = [float(cfg['graph_scale']) for cfg in levels]
+        if abs(scales[0]) < 1e-8 or \
+                any(abs(s - scales[0]) > 1e-8 * abs(scales[0]) for s in scales):
+            return False
+        return all(
+            cfg['graph_gen_method'] == 'disjointed_rnn_local_graph_v3' and
+            int(cfg['graph_gen_kwargs'].get('num_neighbors', -1) or -1) <= 0
+            for cfg in levels)
+
+    def run_pair_deferred(self, frame_a, frame_b):
+        """Two frames as ONE pass, in capacity form: both graphs are built,
+        merged on the device (graph_gen.merge_frames_dyn) and the model runs
+        once over both -- half the launches, and per-vertex stages with twice
+        the tiles.  Every per-row computation is independent of the other
+        rows of its tile and the aggregations are order-independent maxima,
+        so each frame's rows are bit for bit those of run_frame_deferred.
+        Returns the two DeferredFrames."""
+        (xa, ia), (xb, ib) = frame_a, frame_b
+        # (both builds in series on this stream, beside the other passes'
+        # persistent kernels: the second build on a partner stream, joined
+        # before the merge, measured 308.7 against 325.2 frames/s --
+        # profiles/frame_pairs.md)
+        ga = self.build_graph_deferred(xa)
+        gb = self.build_graph_deferred(xb)
+        feats, coords, kps, edges = graph_gen.merge_frames_dyn(ga, ia, gb, ib)
+        logits, boxes = self.model.predict(feats, coords, kps, edges,
+                                           is_training=False)
+        self.last_graph = gb
+        pair = (ga[2][0]._pgnn_count.frame, gb[2][0]._pgnn_count.frame)
+        return (DeferredFrame(self, xa, ia, logits, boxes, pair[0], pair),
+                DeferredFrame(self, xb, ib, logits, boxes, pair[1], pair))
 
     def build_graph(self, xyz):
         """(vertex_coord_list, keypoint_indices_list, edges_list) on the
@@ -345,10 +411,19 @@ class InferenceEngine(object):
         torch.cuda.synchronize()
         return CapturedFrame(self, graph, side, xs, fs, frame)
 
-    def run_frames_on_streams(self, frames, n_streams=3, gnn_priority=False):
+    def run_frames_on_streams(self, frames, n_streams=3, gnn_priority=False,
+                              frames_per_pass=2):
         """Steady-state loop in capacity form: frame i -- graph build AND
         message passing -- runs wholly on stream i % n_streams, and nothing
-        is read back until every frame is enqueued.  Frames are independent
+        is read back until every frame is enqueued.
+        frames_per_pass=2 (default): consecutive frames (2j, 2j + 1) form one
+        pass on stream j % n_streams -- two builds, the merge, ONE
+        model.predict (run_pair_deferred): a frame's per-launch costs are
+        shared by two, at the price of frame 2j's result arriving with
+        frame 2j + 1's.  The first, un-hinted frame, empty or float64 clouds,
+        an odd last frame, the 16-bit edge arithmetics and graphs with more
+        than one pooling level run singly, as with frames_per_pass=1.
+        Frames are independent
         (SURVEY 8e), so the streams need no events between them: while one
         stream's persistent MFMA kernels fill the CUs, the latency-bound
         builder kernels of the other streams' frames run beside them (slowly:
@@ -408,6 +483,22 @@ class InferenceEngine(object):
                                              boxes, frame))
             for h in hi:
                 cur.wait_stream(h)
+        elif int(frames_per_pass) >= 2 and self._pairs_apply():
+            def pairable(fr):
+                return int(fr[0].shape[0]) > 0 and \
+                    fr[0].dtype == torch.float32 and \
+                    fr[1].dtype == torch.float32
+            for j in range((len(frames) + 1) // 2):
+                group = frames[2 * j:2 * j + 2]
+                with torch.cuda.stream(streams[j % len(streams)]):
+                    if len(group) == 2 and pairable(group[0]) and \
+                            pairable(group[1]) and \
+                            group[0][1].shape[1:] == group[1][1].shape[1:]:
+                        pending.extend(self.run_pair_deferred(*group))
+                    else:
+                        for xyz, intensity in group:
+                            pending.append(
+                                self.run_frame_deferred(xyz, intensity))
         else:
             for i, (xyz, intensity) in enumerate(frames):
                 with torch.cuda.stream(streams[i % len(streams)]):
@@ -421,7 +512,9 @@ class InferenceEngine(object):
         host = torch.stack([f.counts.tensor for f in live]).tolist() \
             if live else []
         for f, h in zip(live, host):
-            f.result(h)
+            # (every record before the first result: a half of a pair looks
+            # at the other half's record too)
+            f.counts._host = [int(v) for v in h]
         outs = [f.result() for f in pending]
         for lg, bx in outs:     # allocated on a side stream, used by the caller
             lg.record_stream(cur)
@@ -429,7 +522,8 @@ class InferenceEngine(object):
         if not self._edge_range_clean():
             return self._rerun_batch_f32(
                 lambda: self.run_frames_on_streams(frames, n_streams,
-                                                   gnn_priority))
+                                                   gnn_priority,
+                                                   frames_per_pass))
         return outs
 
     def _priority_streams(self, n):

@@ -35,7 +35,7 @@ __all__ = ["gen_disjointed_rnn_local_graph_v3",
            "gen_multi_level_local_graph_v3", "get_graph_generate_fn",
            "multi_layer_downsampling_select", "multi_layer_downsampling_random",
            "gen_multi_level_local_graph_v3_one_read",
-           "CountHints", "FrameCounts"]
+           "CountHints", "FrameCounts", "merge_frames_dyn"]
 
 
 class CountHints(object):
@@ -951,6 +951,99 @@ def _multi_level_graph_deferred(points_xyz, base_voxel_size, level_configs,
         _lib.count_of(e).frame = frame
     # job0 / side_jobs (their workspaces) die here: after the join was enqueued
     return coords, kps, edges_list
+
+
+def merge_frames_dyn(graph_a, features_a, graph_b, features_b):
+    """Two capacity-form frames (gen_multi_level_local_graph_v3 with
+    `deferred_counts`) as ONE capacity-form frame, merged on the device
+    (pgnn_merge_frames_dyn): nothing is read back, B's rows follow A's ACTUAL
+    rows -- keypoints at K_A, edge rows at A's rows written, both read from A's
+    record by the kernel -- and B's indices move up by A's points / keypoints.
+    The graphs must have one pooling level, the first (every later level on
+    the same vertices: the car and pedestrian configs), float32 clouds and no
+    fan-in cap.  Returns (features, vertex_coord_list, keypoint_indices_list,
+    edges_list) for `model.predict`; `edges_list[0]._pgnn_count.frame` is the
+    merged FrameCounts (sums of K, rows written and rows required), the
+    frames' own records stay what they are.  Rows [0, K_A) of anything the
+    model computes per vertex belong to frame A, rows [K_A, K_A + K_B) to B;
+    sorted edge lists merge into sorted lists."""
+    (ca, ka, ea), (cb, kb, eb) = graph_a, graph_b
+    n_levels = len(ea)
+    if n_levels != len(eb) or not 1 <= n_levels <= _lib.MERGE_MAX_LEVELS:
+        raise ValueError("merge_frames_dyn: 1..%d edge levels, the same in "
+                         "both frames" % _lib.MERGE_MAX_LEVELS)
+    recs = []
+    for coords, kps, edges in (graph_a, graph_b):
+        cnt = _lib.count_of(edges[0])
+        if cnt is None or cnt.frame is None or \
+                _lib.count_of(coords[1]) is None or \
+                any(c is not coords[1] for c in coords[2:]) or \
+                coords[0].dtype != torch.float32 or int(coords[0].shape[0]) == 0:
+            raise ValueError("merge_frames_dyn: capacity-form frames with one "
+                             "pooling level and a non-empty float32 cloud")
+        if int(cnt.frame.tensor.shape[0]) != 2 + 2 * n_levels:
+            raise ValueError("merge_frames_dyn: frames with a fan-in cap")
+        recs.append(cnt.frame)
+    fa, fb = features_a.contiguous(), features_b.contiguous()
+    n_feat = int(fa.shape[1])
+    if fa.dtype != torch.float32 or fb.dtype != torch.float32 or \
+            int(fb.shape[1]) != n_feat:
+        raise ValueError("merge_frames_dyn: float32 features of one width")
+    dev = ca[0].device
+    n_a, n_b = int(ca[0].shape[0]), int(cb[0].shape[0])
+    kp_cap = int(ca[1].shape[0]) + int(cb[1].shape[0])
+    caps = [int(ea[l].shape[0]) + int(eb[l].shape[0]) for l in range(n_levels)]
+    points = torch.empty((n_a + n_b, 3), dtype=torch.float32, device=dev)
+    feats = torch.empty((n_a + n_b, n_feat), dtype=torch.float32, device=dev)
+    kp_xyz = torch.empty((kp_cap, 3), dtype=torch.float32, device=dev)
+    kp_idx = torch.empty((kp_cap, 1), dtype=torch.int32, device=dev)
+    edges = [torch.empty((c, 2), dtype=torch.int32, device=dev) for c in caps]
+    counts = torch.empty(2 + 2 * n_levels, dtype=torch.int32, device=dev)
+
+    def arrays(rec, pts, ft, kxyz, kidx, es):
+        out = _lib.FrameArrays()
+        out.counts = rec.data_ptr()
+        out.points, out.features = pts.data_ptr(), ft.data_ptr()
+        out.n_points = int(pts.shape[0])
+        out.kp_xyz, out.kp_idx = kxyz.data_ptr(), kidx.data_ptr()
+        out.kp_cap = int(kxyz.shape[0])
+        for l, e in enumerate(es):
+            out.edges[l] = e.data_ptr()
+            out.edge_caps[l] = int(e.shape[0])
+        return out
+    ins = [(ca[0].contiguous(), ca[1].contiguous(), ka[0].contiguous(),
+            [e.contiguous() for e in ea]),
+           (cb[0].contiguous(), cb[1].contiguous(), kb[0].contiguous(),
+            [e.contiguous() for e in eb])]
+    hint_e = [[_lib.count_of(e).hint for e in es] for es in (ea, eb)]
+    hint_k = [_lib.count_of(c[1]).hint for c in (ca, cb)]
+    # the longest array one frame contributes, in 4-byte words (grid size only)
+    words = 0
+    if all(h > 0 for hs in hint_e for h in hs):
+        words = max([2 * h for hs in hint_e for h in hs] +
+                    [max(3, n_feat) * max(n_a, n_b)])
+    _lib.check(_lib.load().pgnn_merge_frames_dyn(
+        ctypes.byref(arrays(recs[0].tensor, ins[0][0], fa, ins[0][1],
+                            ins[0][2], ins[0][3])),
+        ctypes.byref(arrays(recs[1].tensor, ins[1][0], fb, ins[1][1],
+                            ins[1][2], ins[1][3])),
+        ctypes.byref(arrays(counts, points, feats, kp_xyz, kp_idx, edges)),
+        n_feat, n_levels, words, _lib.stream_ptr()), "pgnn_merge_frames_dyn")
+    frame = FrameCounts(counts, caps)
+    cnt_k = _lib.DeviceCount(counts[0:1], sum(hint_k) if all(hint_k) else 0,
+                             frame)
+    _lib.tag_count(kp_xyz, cnt_k)
+    _lib.tag_count(kp_idx, cnt_k)
+    coords = [points] + [kp_xyz] * (len(ca) - 1)
+    kps = [kp_idx] + [_lib.tag_count(_identity_indices(kp_cap, dev), cnt_k)
+                      for _ in range(len(ka) - 1)]
+    for l, e in enumerate(edges):
+        ha, hb = hint_e[0][l], hint_e[1][l]
+        _lib.tag_count(e, _lib.DeviceCount(
+            counts[2 + 2 * l:3 + 2 * l], ha + hb if ha and hb else 0, frame))
+        if all(getattr(x[l], "_pgnn_sorted", 0) for x in (ea, eb)):
+            e._pgnn_sorted = 1
+    return feats, coords, kps, edges
 
 
 def gen_multi_level_local_graph_v3_one_read(points_xyz, hints, **kwargs):

@@ -5,6 +5,12 @@ the one-launch forms (pgnn_vertex_update_pre_edge_fwd, pgnn_mlp2_fwd), HIP
 events round 50 back-to-back launches each.
 
     [PGNN_LIB=ab/lib<variant>.so] python tools/krow_bench.py [--k 3352] [--c 300]
+                                                              [--dyn [--cap ROWS]]
+
+--dyn times the one-launch forms through their capacity-form entries (the
+kernels the frame loop runs: K in device memory, a grid sized for the hint
+that strides over the tiles); --cap is the capacity of the arrays (a frame's:
+its point count; default K).
 """
 import os
 import sys
@@ -23,6 +29,8 @@ def arg(name, default):
 
 
 k, c = arg("--k", 3352), arg("--c", 300)
+dyn = "--dyn" in sys.argv
+cap = max(k, arg("--cap", k)) if dyn else k
 dev = torch.device("cuda", 0)
 lib = _lib.load()
 rng = np.random.default_rng(0)
@@ -53,13 +61,15 @@ wx_dev = T(wx)
 agg_in = T(np.pad(rnd(k, c), ((0, 0), (0, wq - c))))
 h_prev = T(np.pad(rnd(k, c), ((0, 0), (0, wq - c))))
 x = T(rng.uniform(-20, 20, (k, 3)).astype(np.float32))
-y = torch.empty((k, wq), device=dev)
-P = torch.empty((k, wq), device=dev)
-Q = torch.empty((k, wq), device=dev)
-agg = torch.empty((k, wq), device=dev)
-o = torch.empty((k, 48), device=dev)
+y = torch.empty((cap, wq), device=dev)
+P = torch.empty((cap, wq), device=dev)
+Q = torch.empty((cap, wq), device=dev)
+agg = torch.empty((cap, wq), device=dev)
+o = torch.empty((cap, 48), device=dev)
 st = _lib.stream_ptr()
 pre = (off.array, off.n, p_chain.array, _lib.ptr(wx_dev), k)
+pre_cap = pre[:-1] + (cap,)
+k_dev = _lib.DeviceCount(torch.tensor([k], dtype=torch.int32, device=dev), k)
 
 
 def run_update():
@@ -94,6 +104,21 @@ def run_mlp2():
         heads.array, heads.n, _lib.ptr(o), o.stride(0), k, st))
 
 
+def run_fused_dyn():
+    _lib.check(lib.pgnn_vertex_update_pre_edge_fwd_dyn(
+        _lib.ptr(agg_in), agg_in.stride(0), c, upd.array, upd.n,
+        _lib.ptr(h_prev), h_prev.stride(0), _lib.ptr(y), y.stride(0), c,
+        _lib.ptr(x), *pre_cap, _lib.ptr(P), _lib.ptr(Q), wq, _lib.ptr(agg), wq,
+        k_dev.arg(), st))
+
+
+def run_mlp2_dyn():
+    _lib.check(lib.pgnn_mlp2_fwd_dyn(
+        _lib.ptr(agg_in), agg_in.stride(0), c, upd.array, upd.n,
+        _lib.ptr(h_prev), h_prev.stride(0), _lib.ptr(y), y.stride(0), c,
+        heads.array, heads.n, _lib.ptr(o), o.stride(0), cap, k_dev.arg(), st))
+
+
 def timeit(fn, reps=50):
     for _ in range(5):
         fn()
@@ -109,15 +134,20 @@ def timeit(fn, reps=50):
 
 flops = {"update": 4 * c * c, "pre_edge": 2 * (c * 64 + 64 * 3 + (c + 3) * c),
          "heads": 2 * (c * 320 + 320 * 272 + 272 * 48)}
-print("lib %s  K %d C %d" % (os.environ.get("PGNN_LIB", "(tree)"), k, c))
-for name, fn, fl in (
+print("lib %s  K %d C %d%s" % (os.environ.get("PGNN_LIB", "(tree)"), k, c,
+                               "  capacity form, %d rows" % cap if dyn else ""))
+for name, fn, fl in ((
+        ("update + pre-edge, one launch, capacity form", run_fused_dyn,
+         flops["update"] + flops["pre_edge"]),
+        ("update + heads, one launch, capacity form", run_mlp2_dyn,
+         flops["update"] + flops["heads"])) if dyn else (
         ("update (pgnn_mlp_fwd)", run_update, flops["update"]),
         ("pre-edge (pgnn_vertex_pre_edge_fwd)", run_pre, flops["pre_edge"]),
         ("heads (pgnn_mlp_fwd)", run_heads, flops["heads"]),
         ("update + pre-edge, one launch", run_fused,
          flops["update"] + flops["pre_edge"]),
         ("update + heads, one launch", run_mlp2,
-         flops["update"] + flops["heads"])):
+         flops["update"] + flops["heads"]))):
     us = timeit(fn)
-    print("  %-40s %7.1f us  %6.1f TFLOP/s (%.2f of fp32-MFMA peak)" % (
+    print("  %-46s %7.1f us  %6.1f TFLOP/s (%.2f of fp32-MFMA peak)" % (
         name, us, fl * k / us / 1e6, fl * k / us / 1e6 / 157.3))
