@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "pgnn_common.h"
+#include "trainer_layout.h"
 
 namespace pgnn {
 // 1: the fused training forward of a GNN stage also writes the gathered hidden
@@ -28,8 +29,6 @@ int g_train_h1 = 1;
 
 namespace {
 using namespace pgnn;
-
-inline int pad16(int n) { return (n + 15) / 16 * 16; }
 
 // ---- glue kernels ---------------------------------------------------------------
 // dst[r, dc0 + c] (op)= src[r, sc0 + c], c < ncols; ADD: accumulate
@@ -229,6 +228,7 @@ struct StageDev {
 
 struct Trainer {
   pgnn_train_model m;
+  TrainerShape shape;  // what the workspace layout depends on
   // the `train_h1` tunable as the most recent pgnn_trainer_forward saw it: the
   // backward of that step reads (or not) the H1 rows the forward wrote (or
   // not), whatever the tunable says by then
@@ -354,70 +354,48 @@ size_t layout_images(Trainer &t) {
 }
 
 // ---- workspace ------------------------------------------------------------------------
-// Bump allocator that also runs "dry" (null base) to size the workspace: the
-// forward and the backward replay the same allocation sequence.
-struct Bump {
-  char *base;
-  size_t off, cap, high;
-  Bump(void *p, size_t n) : base((char *)p), off(0), cap(n), high(0) {}
-  void *raw(size_t bytes) {
-    const size_t at = align_up(off, 256);
-    off = at + bytes;
-    if (off > high) high = off;
-    if (!base) return (void *)(uintptr_t)(at + 256);  // dry run: never used
-    if (off > cap) return nullptr;
-    return base + at;
+// Where every buffer of a step lives is trainer_layout.h; the code below only
+// checks and launches.  The shape is taken in pgnn_trainer_create (the sizing
+// query may come before bind); nothing changes want_wt or the groups after it.
+TrainerShape shape_of(const Trainer &t) {
+  TrainerShape sh = {};
+  sh.n_stages = (int)t.stages.size();
+  auto dims = [](const std::vector<FcDev> &v, FcShape *out) {
+    for (size_t i = 0; i < v.size(); ++i) out[i] = {v[i].ref.k_in, v[i].ref.n_out};
+    return (int)v.size();
+  };
+  for (int si = 0; si < sh.n_stages; ++si) {
+    const StageDev &s = t.stages[(size_t)si];
+    StageShape &d = sh.stages[si];
+    d.kind = s.kind;
+    d.level = s.level;
+    d.n_a = dims(s.a, d.a);
+    d.n_b = dims(s.b, d.b);
+    d.n_c = dims(s.c, d.c);
+    d.want_wt = s.a.back().want_wt;
   }
-  float *f(int64_t rows, int64_t ld) { return (float *)raw((size_t)rows * ld * 4); }
-  int32_t *i32(int64_t n) { return (int32_t *)raw((size_t)n * 4); }
-};
-
-struct PoolSaved {
-  float *feat;                 // [E, 16]
-  float *act[PGNN_TRAIN_MAX_FC];   // outputs of the point MLP layers
-  int32_t *dst;
-  float *agg;                  // [K, pad(n_out of last a)]
-  float *oact[PGNN_TRAIN_MAX_FC];  // outputs of the output MLP layers
-};
-struct GnnSaved {
-  const float *h_in;           // [K, ld_h]
-  float *off_act[PGNN_TRAIN_MAX_FC];  // outputs of the offset MLP layers
-  float *xx, *xo, *q, *hx, *p;  // xx = [x; x'] [2K, 3], xo = x' its 2nd half
-  float *eact[PGNN_TRAIN_MAX_FC];  // eact[0] = H1, eact[i] = output of a[i]
-  int32_t *dst;
-  float *agg;
-  float *uact[PGNN_TRAIN_MAX_FC];  // outputs of the update MLP layers
-};
-struct HeadsSaved {
-  float *y1[4], *y2[4], *y3[4];  // fused groups: outputs of the three layers
-  float *c1, *logits;          // [K, 64], [K, pad(nc)]
-  float *l1[PGNN_TRAIN_MAX_CLASSES], *l2[PGNN_TRAIN_MAX_CLASSES],
-      *l3[PGNN_TRAIN_MAX_CLASSES];
-  float *pred;                 // [K, nc, L]
-};
-struct Saved {  // lives at the start of the workspace (host-visible copy kept
-                // in the handle would break re-entrancy: it is recomputed by
-                // replaying the allocation sequence in backward)
-  PoolSaved pool[PGNN_TRAIN_MAX_STAGES];
-  GnnSaved gnn[PGNN_TRAIN_MAX_STAGES];
-  HeadsSaved heads;
-  const float *h_final;
-  int ld_h_final;
-  int64_t k_final;
-  float *scratch;              // weight-grad / segmax workspace
-  size_t scratch_bytes;
-};
+  sh.n_groups = (int)t.groups.size();
+  for (int gi = 0; gi < sh.n_groups && gi < 4; ++gi)
+    for (int i = 0; i < 3; ++i)
+      sh.group_w[gi][i] = t.groups[(size_t)gi].f[i].ref.n_out;
+  sh.cls_w = t.cls[0].ref.n_out;
+  for (size_t j = 0; j < t.loc.size(); ++j)
+    sh.loc_w[j / 3][j % 3] = t.loc[j].ref.n_out;
+  sh.num_classes = t.m.num_classes;
+  sh.box_len = t.m.box_len;
+  return sh;
+}
 
 struct Ctx {
   Trainer &t;
   const pgnn_train_batch &b;
-  Bump &ws;
   hipStream_t stream;
-  bool dry;  // sizing run: allocate only
-  // weight gradients of the K-row layers, recorded by the backward and run in
-  // ONE launch pair at its end (pgnn_weight_grad_many_f32): only dX is on the
-  // backward's critical path.  Recorded in the sizing run too (the partial
-  // buffer comes out of the same workspace).
+  const Saved &sv;
+  // forward: the levels whose dst column has been extracted already
+  bool dst_done[PGNN_TRAIN_MAX_LEVELS];
+  // weight gradients of the K-row layers, recorded by the backward as it
+  // launches (by nothing else) and run in ONE launch pair at its end
+  // (pgnn_weight_grad_many_f32): only dX is on the backward's critical path
   std::vector<pgnn_wgrad_job> wjobs;
   // a second batch, run after the first: jobs that add into a dW the first
   // batch also writes (the Wx rows of a GNN stage's first edge layer)
@@ -443,12 +421,8 @@ int check_batch(const Trainer &t, const pgnn_train_batch *b) {
 int fc_fwd_from(Ctx &c, const FcDev &f, const float *x, int64_t ldx,
                 int64_t rows, int relu_from, const float *residual,
                 int64_t ld_res, float *y) {
-  if (c.dry || rows == 0) return 0;
-  pgnn_fc_layer L;
-  L.packed = f.packed;
-  L.k_in = f.ref.k_in;
-  L.n_out = f.ref.n_out;
-  L.relu_from = relu_from;
+  if (rows == 0) return 0;
+  const pgnn_fc_layer L = {f.packed, f.ref.k_in, f.ref.n_out, relu_from};
   return pgnn_mlp_fwd(x, ldx, f.ref.k_in, nullptr, 0, 0, rows, &L, 1, residual,
                       ld_res, y, pad16(f.ref.n_out), c.stream);
 }
@@ -466,17 +440,13 @@ int fc_fwd(Ctx &c, const FcDev &f, const float *x, int64_t ldx, int64_t rows,
 int fc_chain_fwd(Ctx &c, const FcDev *const *f, const int *relu_from, int n,
                  const float *x, int64_t ldx, int64_t rows, const float *residual,
                  int64_t ld_res, float *const *outs) {
-  if (c.dry || rows == 0 || n == 0) return 0;
+  if (rows == 0 || n == 0) return 0;
   if (n >= 2 && n <= PGNN_MAX_LAYERS) {
     pgnn_fc_layer L[PGNN_MAX_LAYERS];
     RowsTap taps[PGNN_MAX_LAYERS];
     for (int i = 0; i < n; ++i) {
-      L[i].packed = f[i]->packed;
-      L[i].k_in = f[i]->ref.k_in;
-      L[i].n_out = f[i]->ref.n_out;
-      L[i].relu_from = relu_from[i];
-      taps[i].mid = outs[i];
-      taps[i].gate = nullptr;
+      L[i] = {f[i]->packed, f[i]->ref.k_in, f[i]->ref.n_out, relu_from[i]};
+      taps[i] = {outs[i], nullptr};
     }
     const int rc = mlp_rows_chain(x, ldx, f[0]->ref.k_in, rows, L, n, taps,
                                   residual, ld_res, 0, outs[n - 1],
@@ -495,18 +465,42 @@ int fc_chain_fwd(Ctx &c, const FcDev *const *f, const int *relu_from, int n,
   return 0;
 }
 
+// The layers of a stage's MLP as the argument arrays of fc_chain_fwd (fs, rf:
+// every layer a ReLU layer, with linear_last all but the last) and of
+// fc_chain_bwd (fs, xin, ldx, gate: layer 0 read x0 [., ld0], layer i > 0 the
+// ReLU output acts[i - 1] of the layer below, whose ReluGrad leaves with dX).
+struct Chain {
+  const FcDev *fs[PGNN_TRAIN_MAX_FC];
+  int rf[PGNN_TRAIN_MAX_FC];
+  const float *xin[PGNN_TRAIN_MAX_FC];
+  int64_t ldx[PGNN_TRAIN_MAX_FC];
+  bool gate[PGNN_TRAIN_MAX_FC];
+  int n;
+};
+Chain chain_of(const std::vector<FcDev> &v, bool linear_last,
+               const float *x0 = nullptr, int64_t ld0 = 0,
+               float *const *acts = nullptr) {
+  Chain ch;
+  ch.n = (int)v.size();
+  for (int i = 0; i < ch.n; ++i) {
+    ch.fs[i] = &v[(size_t)i];
+    ch.rf[i] = linear_last && i + 1 == ch.n ? v[(size_t)i].ref.n_out : 0;
+    ch.xin[i] = i == 0 ? x0 : (acts ? acts[i - 1] : nullptr);
+    ch.ldx[i] = i == 0 ? ld0 : pad16(v[(size_t)i - 1].ref.n_out);
+    ch.gate[i] = i > 0;
+  }
+  return ch;
+}
+
 // dX = dY W^T through the forward engine on the transposed image
 // gate (nullable, [rows, ld_gate]): the layer's forward input when that is a
 // ReLU output -- the ReluGrad of the layer below, dx = gate > 0 ? dx : 0,
 // leaves with the rows instead of taking a launch of its own
 int fc_dx(Ctx &c, const FcDev &f, const float *dy, int64_t lddy, int64_t rows,
           float *dx, const float *gate = nullptr, int64_t ld_gate = 0) {
-  if (c.dry || rows == 0) return 0;
-  pgnn_fc_layer L;
-  L.packed = f.packed_t;
-  L.k_in = f.ref.n_out;
-  L.n_out = f.ref.k_in;
-  L.relu_from = f.ref.k_in;  // linear
+  if (rows == 0) return 0;
+  // (the transposed image as a linear layer)
+  const pgnn_fc_layer L = {f.packed_t, f.ref.n_out, f.ref.k_in, f.ref.k_in};
   if (gate) {
     // (every caller's gate has the padded rows of the layer's input; a
     // narrower one would need an ld-aware mask)
@@ -521,57 +515,46 @@ int fc_dx(Ctx &c, const FcDev &f, const float *dy, int64_t lddy, int64_t rows,
 
 // record dW/db = (x^T dy, column sums) for the end of the backward; x and dy
 // must stay untouched until then
-void defer_wgrad(Ctx &c, const float *x, int64_t ldx, int k_in, const float *dy,
-                 int64_t lddy, int n_out, int64_t rows, float *gw, float *gb,
-                 bool accumulate) {
-  pgnn_wgrad_job j = {};
-  j.X = x;
-  j.ld_x = ldx;
-  j.dZ = dy;
-  j.ld_dz = lddy;
-  j.n_rows = rows;
-  j.dW = gw;
-  j.db = gb;
-  j.k_in = k_in;
-  j.n_out = n_out;
-  j.accumulate = accumulate ? 1 : 0;
-  c.wjobs.push_back(j);
+void defer_wgrad(std::vector<pgnn_wgrad_job> &jobs, const float *x, int64_t ldx,
+                 int k_in, const float *dy, int64_t lddy, int n_out, int64_t rows,
+                 float *gw, float *gb, bool accumulate) {
+  jobs.push_back(
+      {x, ldx, dy, lddy, rows, gw, gb, k_in, n_out, accumulate ? 1 : 0, 0});
+}
+// rows cc..cc+2 of the dW of a GNN stage's first edge layer w1 += x^T dz over
+// `rows` coordinate rows x [rows, 3].  It adds into the dW that w1's own job
+// writes, and jobs of one batch must not share outputs: the second batch.
+void defer_coord_wgrad(Ctx &c, const FcDev &w1, const float *x, const float *dz,
+                       int64_t lddz, int64_t rows) {
+  defer_wgrad(c.wjobs2, x, 3, 3, dz, lddz, w1.ref.n_out, rows,
+              w1.gw + (int64_t)(w1.ref.k_in - 3) * w1.ref.n_out, nullptr, true);
 }
 
-int fc_wgrad(Ctx &c, Saved &sv, const FcDev &f, const float *x, int64_t ldx,
-             const float *dy, int64_t lddy, int64_t rows, bool accumulate = true,
+int fc_wgrad(Ctx &c, const FcDev &f, const float *x, int64_t ldx, const float *dy,
+             int64_t lddy, int64_t rows, bool accumulate = true,
              bool defer = false) {
   if (rows == 0) return 0;
   if (defer && f.ref.n_out <= 320) {
-    defer_wgrad(c, x, ldx, f.ref.k_in, dy, lddy, f.ref.n_out, rows, f.gw, f.gb,
-                accumulate);
+    defer_wgrad(c.wjobs, x, ldx, f.ref.k_in, dy, lddy, f.ref.n_out, rows, f.gw,
+                f.gb, accumulate);
     return 0;
   }
-  if (c.dry) return 0;
   return pgnn_weight_grad_f32(x, ldx, f.ref.k_in, dy, lddy, f.ref.n_out, rows,
-                              f.gw, f.gb, accumulate ? 1 : 0, sv.scratch,
-                              sv.scratch_bytes, c.stream);
+                              f.gw, f.gb, accumulate ? 1 : 0, c.sv.scratch,
+                              c.sv.scratch_bytes, c.stream);
 }
 
-// fc_bwd of the Python mirror: optional ReluGrad (in place on dy), dW/db, dX.
+// fc_bwd of the Python mirror for a dy that is ReLU-masked already: dW/db, dX.
 // defer: the weight gradient is recorded for the end of the backward -- the
 // caller guarantees that x and dy are not written again before that.
 // gate_dx: x is the output of a ReLU layer whose backward comes next: dx leaves
-// already masked (the next fc_bwd is then called with relu = false).
-int fc_bwd(Ctx &c, Saved &sv, const FcDev &f, const float *x, int64_t ldx,
-           const float *y, float *dy, int64_t rows, bool relu, float *dx,
-           bool accumulate = true, bool defer = false, bool gate_dx = false) {
-  if (rows == 0) return 0;
+// masked by its ReluGrad.
+int fc_bwd(Ctx &c, const FcDev &f, const float *x, int64_t ldx, const float *dy,
+           int64_t rows, float *dx, bool accumulate = true, bool defer = false,
+           bool gate_dx = false) {
   const int ldy = pad16(f.ref.n_out);
-  int rc = 0;
-  if (relu && !c.dry) {
-    rc = pgnn_relu_mask_mul(dy, y, rows * ldy, c.stream);
-    if (rc) return rc;
-  }
-  rc = fc_wgrad(c, sv, f, x, ldx, dy, ldy, rows, accumulate, defer);
-  if (rc) return rc;
-  if (dx && !c.dry)
-    rc = fc_dx(c, f, dy, ldy, rows, dx, gate_dx ? x : nullptr, ldx);
+  int rc = fc_wgrad(c, f, x, ldx, dy, ldy, rows, accumulate, defer);
+  if (rc == 0 && dx) rc = fc_dx(c, f, dy, ldy, rows, dx, gate_dx ? x : nullptr, ldx);
   return rc;
 }
 
@@ -591,18 +574,14 @@ struct PreDx {
   int64_t ldx;
 };
 int pre_dx(Ctx &c, const PreDx &p, int64_t rows, float *dy_top) {
-  pgnn_fc_layer L;
-  L.packed = (const float *)p.packed;
-  L.k_in = p.k_in;
-  L.n_out = p.n_out;
-  L.relu_from = p.n_out;
+  const pgnn_fc_layer L = {(const float *)p.packed, p.k_in, p.n_out, p.n_out};
   return pgnn_mlp_fwd(p.x, p.ldx, p.k_in, nullptr, 0, 0, rows, &L, 1, nullptr, 0,
                       dy_top, pad16(p.n_out), c.stream);
 }
-int fc_chain_bwd(Ctx &c, Saved &sv, const FcDev *const *f, int n,
-                 const float *const *xin, const int64_t *ldx, float *dy_top,
-                 int64_t rows, float *const *dxs, const bool *gate,
-                 bool accumulate = true, const PreDx *pre = nullptr) {
+int fc_chain_bwd(Ctx &c, const FcDev *const *f, int n, const float *const *xin,
+                 const int64_t *ldx, float *dy_top, int64_t rows,
+                 float *const *dxs, const bool *gate, bool accumulate = true,
+                 const PreDx *pre = nullptr) {
   if (rows == 0 || n == 0) return 0;
   const int np = pre ? 1 : 0;
   bool chain = n + np >= 2 && n + np <= PGNN_MAX_LAYERS;
@@ -611,33 +590,24 @@ int fc_chain_bwd(Ctx &c, Saved &sv, const FcDev *const *f, int n,
             (!gate[i] || ldx[i] == pad16(f[i]->ref.k_in));
   int rc = 0;
   if (chain) {
-    // (recorded in the sizing run too; a job only holds pointers)
+    // (n_out <= 320: fc_wgrad records every one of these, it launches none)
     const float *dy = dy_top;
     for (int i = n - 1; i >= 0; --i) {
-      rc = fc_wgrad(c, sv, *f[i], xin[i], ldx[i], dy, pad16(f[i]->ref.n_out), rows,
+      rc = fc_wgrad(c, *f[i], xin[i], ldx[i], dy, pad16(f[i]->ref.n_out), rows,
                     accumulate, true);
       if (rc) return rc;
       dy = dxs[i];
     }
-    if (c.dry) return 0;
     pgnn_fc_layer L[PGNN_MAX_LAYERS];
     RowsTap taps[PGNN_MAX_LAYERS];
     if (pre) {
-      L[0].packed = (const float *)pre->packed;
-      L[0].k_in = pre->k_in;
-      L[0].n_out = pre->n_out;
-      L[0].relu_from = pre->n_out;
-      taps[0].mid = dy_top;
-      taps[0].gate = nullptr;
+      L[0] = {(const float *)pre->packed, pre->k_in, pre->n_out, pre->n_out};
+      taps[0] = {dy_top, nullptr};
     }
     for (int j = 0; j < n; ++j) {
       const FcDev &g = *f[n - 1 - j];
-      L[np + j].packed = g.packed_t;
-      L[np + j].k_in = g.ref.n_out;
-      L[np + j].n_out = g.ref.k_in;
-      L[np + j].relu_from = g.ref.k_in;  // linear
-      taps[np + j].mid = dxs[n - 1 - j];
-      taps[np + j].gate = gate[n - 1 - j] ? xin[n - 1 - j] : nullptr;
+      L[np + j] = {g.packed_t, g.ref.n_out, g.ref.k_in, g.ref.k_in};  // linear
+      taps[np + j] = {dxs[n - 1 - j], gate[n - 1 - j] ? xin[n - 1 - j] : nullptr};
     }
     rc = mlp_rows_chain(pre ? pre->x : dy_top,
                         pre ? pre->ldx : (int64_t)pad16(f[n - 1]->ref.n_out),
@@ -645,47 +615,40 @@ int fc_chain_bwd(Ctx &c, Saved &sv, const FcDev *const *f, int n,
                         gate[0] ? xin[0] : nullptr, ldx[0], gate[0] ? 1 : 0,
                         dxs[0], pad16(f[0]->ref.k_in), c.stream);
     if (rc != PGNN_E_UNSUPPORTED) return rc;
-    // the dX launches one by one (the weight gradients are already recorded)
-    if (pre) {
-      rc = pre_dx(c, *pre, rows, dy_top);
-      if (rc) return rc;
-    }
-    float *d = dy_top;
-    for (int i = n - 1; i >= 0; --i) {
-      rc = fc_dx(c, *f[i], d, pad16(f[i]->ref.n_out), rows, dxs[i],
-                 gate[i] ? xin[i] : nullptr, ldx[i]);
-      if (rc) return rc;
-      d = dxs[i];
-    }
-    return 0;
   }
-  if (pre && !c.dry) {
+  // layer by layer (after a chain that did not apply: the dX launches only,
+  // its weight gradients are recorded)
+  if (pre) {
     rc = pre_dx(c, *pre, rows, dy_top);
     if (rc) return rc;
   }
   float *d = dy_top;
   for (int i = n - 1; i >= 0; --i) {
-    rc = fc_bwd(c, sv, *f[i], xin[i], ldx[i], nullptr, d, rows, false, dxs[i],
-                accumulate, true, gate[i]);
+    const int ldy = pad16(f[i]->ref.n_out);
+    if (!chain) {
+      rc = fc_wgrad(c, *f[i], xin[i], ldx[i], d, ldy, rows, accumulate, true);
+      if (rc) return rc;
+    }
+    rc = fc_dx(c, *f[i], d, ldy, rows, dxs[i], gate[i] ? xin[i] : nullptr, ldx[i]);
     if (rc) return rc;
     d = dxs[i];
   }
   return 0;
 }
 
-// run the recorded weight gradients (one launch pair).  Their partial sums
-// take a fixed slice of the workspace (the sizing run records no jobs: it
-// does not walk the launch code): pgnn_weight_grad_many_f32 aims for 4
+// Run the recorded weight gradients (one launch pair per batch).  Only a
+// backward that launches records jobs, so the sizing run cannot know their
+// partial sums' size: they take a slice of fixed size, which the layout
+// reserves (Grads::wgrad_part).  pgnn_weight_grad_many_f32 aims for 4
 // workgroups per CU over all jobs, each writing a [64 x <= 320] block.
 size_t wgrad_many_bound() {
   return ((size_t)4 * device_cu_count() + 8 * 64) * 64 * 320 * 4 + 256;
 }
-int flush_wgrads(Ctx &c, Saved &sv) {
+int flush_wgrads(Ctx &c, void *part) {
   const size_t bound = wgrad_many_bound();
-  void *part = c.ws.raw(bound);
   int rc = 0;
   for (std::vector<pgnn_wgrad_job> *jobs : {&c.wjobs, &c.wjobs2}) {
-    if (!c.dry && !jobs->empty() && rc == 0) {
+    if (!jobs->empty() && rc == 0) {
       PGNN_REQUIRE(part != nullptr, PGNN_E_WORKSPACE,
                    "trainer: workspace too small");
       const size_t bytes =
@@ -696,8 +659,8 @@ int flush_wgrads(Ctx &c, Saved &sv) {
       } else {  // (more jobs than the bound foresees: one by one)
         for (const pgnn_wgrad_job &j : *jobs) {
           rc = pgnn_weight_grad_f32(j.X, j.ld_x, j.k_in, j.dZ, j.ld_dz, j.n_out,
-                                    j.n_rows, j.dW, j.db, j.accumulate, sv.scratch,
-                                    sv.scratch_bytes, c.stream);
+                                    j.n_rows, j.dW, j.db, j.accumulate,
+                                    c.sv.scratch, c.sv.scratch_bytes, c.stream);
           if (rc) break;
         }
       }
@@ -709,9 +672,11 @@ int flush_wgrads(Ctx &c, Saved &sv) {
 
 size_t scratch_need(const Trainer &t, const pgnn_train_batch &b) {
   size_t need = 256;
-  auto wg = [&](const FcDev &f, int64_t rows) {
-    const size_t n = pgnn_weight_grad_workspace_bytes(f.ref.k_in, f.ref.n_out, rows);
+  auto at_least = [&](size_t n) {
     if (n > need) need = n;
+  };
+  auto wg = [&](const FcDev &f, int64_t rows) {
+    at_least(pgnn_weight_grad_workspace_bytes(f.ref.k_in, f.ref.n_out, rows));
   };
   for (const StageDev &s : t.stages) {
     const int64_t E = b.n_edges[s.level], K = b.n_vertices[s.level + 1];
@@ -719,18 +684,13 @@ size_t scratch_need(const Trainer &t, const pgnn_train_batch &b) {
     for (const FcDev &f : s.b) wg(f, K);
     for (const FcDev &f : s.c) wg(f, K);
     const FcDev &last = s.a.back();
-    if (last.want_wt) {
-      const size_t n = pgnn_segmax_fc_bwd_workspace_bytes(E, last.ref.n_out,
-                                                          (int32_t)K, last.ref.k_in);
-      if (n > need) need = n;
-    }
-    if (s.kind == 1) {  // the coordinate rows: k_in = 3, rows [x; x']
-      const size_t n = pgnn_weight_grad_workspace_bytes(3, s.a[0].ref.n_out, 2 * K);
-      if (n > need) need = n;
-    } else {  // the fused backward of the narrow pooling layers
-      const size_t n = pgnn_pool_narrow_bwd_workspace_bytes(E);
-      if (n > need) need = n;
-    }
+    if (last.want_wt)
+      at_least(pgnn_segmax_fc_bwd_workspace_bytes(E, last.ref.n_out, (int32_t)K,
+                                                  last.ref.k_in));
+    if (s.kind == 1)  // the coordinate rows: k_in = 3, rows [x; x']
+      at_least(pgnn_weight_grad_workspace_bytes(3, s.a[0].ref.n_out, 2 * K));
+    else  // the fused backward of the narrow pooling layers
+      at_least(pgnn_pool_narrow_bwd_workspace_bytes(E));
   }
   const int64_t K = b.n_vertices[b.n_levels];
   for (const FcDev &f : t.cls) wg(f, K);
@@ -741,303 +701,207 @@ size_t scratch_need(const Trainer &t, const pgnn_train_batch &b) {
 }
 
 // ---- forward ---------------------------------------------------------------------------
-// Allocation sequence of the forward (shared by the sizing run, the forward
-// and the backward, which re-derives the same pointers).
-int forward_impl(Ctx &c, Saved &sv) {
-  Trainer &t = c.t;
+// The destination column of a level's edge list, extracted by the stage that
+// first uses the level (the three GNN stages of the shipped models share
+// level 1's).  fill / fill_count: a buffer the same launch sets to lowest();
+// returns whether that happened -- not when the level's column existed already.
+bool level_dst(Ctx &c, int lvl, int32_t *dst, float *fill = nullptr,
+               int64_t fill_count = 0) {
+  const int64_t E = c.b.n_edges[lvl];
+  if (c.dst_done[lvl]) return false;
+  c.dst_done[lvl] = true;
+  if (E == 0 || !dst) return false;
+  hipLaunchKernelGGL(edge_dst_kernel, dim3(blocks_for(E)), dim3(256), 0, c.stream,
+                     c.b.edges[lvl], E, dst, fill, fill ? fill_count : (int64_t)0);
+  return fill != nullptr;
+}
+
+// The unfused form of a stage's per-edge layers a[first..] on the rows x (their
+// outputs go to acts[first..]) and the max over each destination's rows.
+int edge_layers_fwd(Ctx &c, const StageDev &s, size_t first, const float *x,
+                    int64_t ldx, float *const *acts, const int32_t *dst,
+                    float *agg) {
+  const int64_t E = c.b.n_edges[s.level], K = c.b.n_vertices[s.level + 1];
+  for (size_t i = first; i < s.a.size(); ++i) {
+    const int rc = fc_fwd(c, s.a[i], x, ldx, E, true, nullptr, 0, acts[i]);
+    if (rc) return rc;
+    x = acts[i];
+    ldx = pad16(s.a[i].ref.n_out);
+  }
+  return pgnn_scatter_max_f32(x, ldx, dst, E, (int32_t)ldx, (int32_t)K, agg, ldx,
+                              c.b.edges_sorted[s.level] ? 1 : 0, c.stream);
+}
+
+// PointSetPooling (gnn.py:269-290)
+int pool_stage_fwd(Ctx &c, const StageDev &s, const PoolSaved &p) {
   const pgnn_train_batch &b = c.b;
+  const int lvl = s.level;
+  const int64_t E = b.n_edges[lvl], K = b.n_vertices[lvl + 1];
+  const int wa = pad16(s.a.back().ref.n_out);
+  PGNN_REQUIRE(s.a[0].ref.k_in == b.n_feat + 3, PGNN_E_INVALID,
+               "trainer: point MLP input width != n_feat + 3");
+  // (the launch that extracts the level's dst column also sets the
+  // aggregation buffer to lowest(): no fill launch of its own)
+  const bool agg_filled = level_dst(c, lvl, p.dst, p.agg, (int64_t)K * wa);
+  int rc = pgnn_pool_features_fwd(b.input_v, b.n_feat, b.coords[lvl],
+                                  b.keypoints[lvl], b.edges[lvl], E, p.feat,
+                                  c.stream);
+  if (rc) return rc;
+  bool fused = false;
+  if (s.a.size() == 4 && s.a.back().want_wt && pad16(s.a[0].ref.n_out) == 32 &&
+      pad16(s.a[1].ref.n_out) == 64 && pad16(s.a[2].ref.n_out) == 128) {
+    // gather + the whole point MLP + scatter-max in ONE kernel that also
+    // writes the four layers' activations
+    pgnn_fc_layer Ls[4];
+    for (int i = 0; i < 4; ++i)
+      Ls[i] = {s.a[i].packed, s.a[i].ref.k_in, s.a[i].ref.n_out, 0};
+    rc = pgnn_point_set_pooling_rows_fwd(
+        b.input_v, b.n_feat, b.coords[lvl], b.keypoints[lvl], b.edges[lvl], E,
+        (int32_t)K, Ls, 4, (b.edges_sorted[lvl] ? 1 : 0) | (agg_filled ? 2 : 0),
+        p.agg, wa, p.act, wa, c.stream);
+    if (rc == 0) fused = true;
+    else if (rc != PGNN_E_UNSUPPORTED) return rc;
+  }
+  if (!fused) {
+    rc = edge_layers_fwd(c, s, 0, p.feat, 16, p.act, p.dst, p.agg);
+    if (rc) return rc;
+  }
+  // output MLP, every layer a ReLU layer: one launch
+  const Chain ch = chain_of(s.b, false);
+  return fc_chain_fwd(c, ch.fs, ch.rf, ch.n, p.agg, wa, K, nullptr, 0, p.oact);
+}
+
+// GraphNetAutoCenter (gnn.py:337-372) on the k_h rows of features the stages
+// before it left
+int gnn_stage_fwd(Ctx &c, const StageDev &s, const GnnSaved &g, int64_t k_h) {
+  const pgnn_train_batch &b = c.b;
+  const int lvl = s.level;
+  const int64_t E = b.n_edges[lvl], K = b.n_vertices[lvl + 1];
+  const float *h = g.h_in;
+  const int ld_h = c.sv.ld_h_final;  // (one feature width from stage to stage)
+  const FcDev &w1 = s.a[0];
+  const int cc = w1.ref.k_in - 3;
+  const int wq = pad16(w1.ref.n_out), wa = pad16(s.a.back().ref.n_out);
+  const int ldhx = pad16(cc + 3);
+  PGNN_REQUIRE(h != nullptr, PGNN_E_INVALID,
+               "trainer: a GNN stage needs vertex features from a pooling stage");
+  PGNN_REQUIRE(k_h == K, PGNN_E_INVALID,
+               "trainer: GNN stage vertex count != feature rows");
+  PGNN_REQUIRE(ld_h >= cc, PGNN_E_INVALID,
+               "trainer: vertex features narrower than the edge MLP input");
+  PGNN_REQUIRE(s.b.back().ref.n_out == cc && ld_h >= pad16(cc), PGNN_E_INVALID,
+               "trainer: update MLP must preserve the feature width");
+  PGNN_REQUIRE(s.c.empty() || s.c.back().ref.n_out == 3, PGNN_E_INVALID,
+               "trainer: the offset MLP must end in 3 outputs");
+  level_dst(c, lvl, g.dst);
   int rc = 0;
-  sv.scratch_bytes = scratch_need(t, b);
-  sv.scratch = (float *)c.ws.raw(sv.scratch_bytes);
-  const float *h = nullptr;
-  int ld_h = 0;
-  int64_t k_h = 0;
-  // the destination column of a level's edge list, extracted once per level
-  // (the three GNN stages of the shipped models share level 1's)
-  int32_t *dst_of[PGNN_TRAIN_MAX_LEVELS] = {nullptr};
-  // (fill / fill_count: a buffer the same launch sets to lowest(); *filled
-  // says whether that happened -- not when the level's column existed already)
-  auto level_dst = [&](int lvl, int64_t E, float *fill = nullptr,
-                       int64_t fill_count = 0,
-                       bool *filled = nullptr) -> int32_t * {
-    if (filled) *filled = false;
-    if (dst_of[lvl]) return dst_of[lvl];
-    int32_t *d = c.ws.i32(E > 0 ? E : 1);
-    if (!c.dry && E > 0 && d) {
-      hipLaunchKernelGGL(edge_dst_kernel, dim3(blocks_for(E)), dim3(256), 0,
-                         c.stream, b.edges[lvl], E, d, fill,
-                         fill ? fill_count : (int64_t)0);
-      if (filled && fill) *filled = true;
-    }
-    dst_of[lvl] = d;
-    return d;
-  };
-  for (size_t si = 0; si < t.stages.size(); ++si) {
-    StageDev &s = t.stages[si];
-    const int lvl = s.level;
-    const int64_t E = b.n_edges[lvl], K = b.n_vertices[lvl + 1];
-    if (s.kind == 0) {
-      PoolSaved &p = sv.pool[si];
-      p.feat = c.ws.f(E, 16);
-      for (size_t i = 0; i < s.a.size(); ++i) p.act[i] = c.ws.f(E, pad16(s.a[i].ref.n_out));
-      const int wa = pad16(s.a.back().ref.n_out);
-      p.agg = c.ws.f(K, wa);
-      // (the launch that extracts the level's dst column also sets the
-      // aggregation buffer to lowest(): no fill launch of its own)
-      bool agg_filled = false;
-      p.dst = level_dst(lvl, E, p.agg, (int64_t)K * wa, &agg_filled);
-      for (size_t i = 0; i < s.b.size(); ++i) p.oact[i] = c.ws.f(K, pad16(s.b[i].ref.n_out));
-      if (!c.dry) {
-        PGNN_REQUIRE(s.a[0].ref.k_in == b.n_feat + 3, PGNN_E_INVALID,
-                     "trainer: point MLP input width != n_feat + 3");
-        rc = pgnn_pool_features_fwd(b.input_v, b.n_feat, b.coords[lvl],
-                                    b.keypoints[lvl], b.edges[lvl], E, p.feat,
-                                    c.stream);
-        if (rc) return rc;
-        const float *x = p.feat;
-        int64_t ldx = 16;
-        bool fused = false;
-        if (s.a.size() == 4 && s.a.back().want_wt &&
-            pad16(s.a[0].ref.n_out) == 32 && pad16(s.a[1].ref.n_out) == 64 &&
-            pad16(s.a[2].ref.n_out) == 128) {
-          // gather + the whole point MLP + scatter-max in ONE kernel that
-          // also writes the four layers' activations
-          pgnn_fc_layer Ls[4];
-          for (int i = 0; i < 4; ++i) {
-            Ls[i].packed = s.a[i].packed;
-            Ls[i].k_in = s.a[i].ref.k_in;
-            Ls[i].n_out = s.a[i].ref.n_out;
-            Ls[i].relu_from = 0;
-          }
-          float *acts[4] = {p.act[0], p.act[1], p.act[2], p.act[3]};
-          rc = pgnn_point_set_pooling_rows_fwd(
-              b.input_v, b.n_feat, b.coords[lvl], b.keypoints[lvl], b.edges[lvl],
-              E, (int32_t)K, Ls, 4,
-              (b.edges_sorted[lvl] ? 1 : 0) | (agg_filled ? 2 : 0), p.agg, wa,
-              acts, wa, c.stream);
-          if (rc == 0) fused = true;
-          else if (rc != PGNN_E_UNSUPPORTED) return rc;
-        }
-        if (!fused) {
-          for (size_t i = 0; i < s.a.size(); ++i) {
-            rc = fc_fwd(c, s.a[i], x, ldx, E, true, nullptr, 0, p.act[i]);
-            if (rc) return rc;
-            x = p.act[i];
-            ldx = pad16(s.a[i].ref.n_out);
-          }
-          rc = pgnn_scatter_max_f32(x, ldx, p.dst, E, (int32_t)ldx, (int32_t)K,
-                                    p.agg, wa, b.edges_sorted[lvl] ? 1 : 0,
-                                    c.stream);
-          if (rc) return rc;
-        }
-        {  // output MLP, every layer a ReLU layer: one launch
-          const FcDev *fs[PGNN_TRAIN_MAX_FC];
-          int rf[PGNN_TRAIN_MAX_FC];
-          for (size_t i = 0; i < s.b.size(); ++i) {
-            fs[i] = &s.b[i];
-            rf[i] = 0;
-          }
-          rc = fc_chain_fwd(c, fs, rf, (int)s.b.size(), p.agg, wa, K, nullptr, 0,
-                            p.oact);
-          if (rc) return rc;
-        }
-      }
-      h = p.oact[s.b.size() - 1];
-      ld_h = pad16(s.b.back().ref.n_out);
-      k_h = K;
-    } else {
-      GnnSaved &g = sv.gnn[si];
-      PGNN_REQUIRE(h != nullptr || c.dry, PGNN_E_INVALID,
-                   "trainer: a GNN stage needs vertex features from a pooling stage");
-      PGNN_REQUIRE(c.dry || k_h == K, PGNN_E_INVALID,
-                   "trainer: GNN stage vertex count != feature rows");
-      const FcDev &w1 = s.a[0];
-      const int cc = w1.ref.k_in - 3;
-      const int wq = pad16(w1.ref.n_out);
-      g.h_in = h;
-      for (size_t i = 0; i < s.c.size(); ++i) g.off_act[i] = c.ws.f(K, pad16(s.c[i].ref.n_out));
-      g.xx = c.ws.f(2 * K, 3);
-      g.xo = g.xx + 3 * K;
-      g.q = c.ws.f(K, wq);
-      g.hx = c.ws.f(K, pad16(cc + 3));
-      g.p = c.ws.f(K, wq);
-      g.eact[0] = c.ws.f(E, wq);
-      for (size_t i = 1; i < s.a.size(); ++i) g.eact[i] = c.ws.f(E, pad16(s.a[i].ref.n_out));
-      g.dst = level_dst(lvl, E);
-      const int wa = pad16(s.a.back().ref.n_out);
-      g.agg = c.ws.f(K, wa);
-      for (size_t i = 0; i < s.b.size(); ++i) g.uact[i] = c.ws.f(K, pad16(s.b[i].ref.n_out));
-      if (!c.dry) {
-        PGNN_REQUIRE(ld_h >= cc, PGNN_E_INVALID,
-                     "trainer: vertex features narrower than the edge MLP input");
-        PGNN_REQUIRE(s.b.back().ref.n_out == cc && ld_h >= pad16(cc), PGNN_E_INVALID,
-                     "trainer: update MLP must preserve the feature width");
-        const float *delta = nullptr;
-        int64_t ld_delta = 0;
-        if (!s.c.empty()) {  // offset MLP, last layer linear: one launch
-          PGNN_REQUIRE(s.c.back().ref.n_out == 3, PGNN_E_INVALID,
-                       "trainer: the offset MLP must end in 3 outputs");
-          const FcDev *fs[PGNN_TRAIN_MAX_FC];
-          int rf[PGNN_TRAIN_MAX_FC];
-          for (size_t i = 0; i < s.c.size(); ++i) {
-            fs[i] = &s.c[i];
-            rf[i] = i + 1 < s.c.size() ? 0 : s.c[i].ref.n_out;
-          }
-          rc = fc_chain_fwd(c, fs, rf, (int)s.c.size(), h, ld_h, K, nullptr, 0,
-                            g.off_act);
-          if (rc) return rc;
-          delta = g.off_act[s.c.size() - 1];
-          ld_delta = pad16(s.c.back().ref.n_out);
-        }
-        if (K > 0) {
-          const int ldhx = pad16(cc + 3);
-          hipLaunchKernelGGL(pre_edge_prep_kernel,
-                             dim3(blocks_for(K * (ldhx > wq ? ldhx : wq), 8192)),
-                             dim3(256), 0, c.stream, h, (int64_t)ld_h, cc,
-                             b.coords[lvl], delta, ld_delta, K, s.wx, g.hx, ldhx,
-                             g.xx, g.xo, g.q, wq, g.agg, (int64_t)K * wa);
-        }
-        rc = fc_fwd(c, w1, g.hx, pad16(cc + 3), K, false, nullptr, 0, g.p);
-        if (rc) return rc;
-        bool fused = false;
-        if (s.a.size() == 2 && s.a[1].want_wt) {
-          // gather + last edge layer + scatter-max in ONE kernel that also
-          // writes the layer's rows and the gathered hidden rows H1
-          pgnn_fc_layer L2;
-          L2.packed = s.a[1].packed;
-          L2.k_in = s.a[1].ref.k_in;
-          L2.n_out = s.a[1].ref.n_out;
-          L2.relu_from = 0;
-          rc = pgnn_edge_mlp_scatter_max_rows_fwd(
-              g.p, g.q, wq, s.a[1].ref.k_in, b.edges[lvl], E, (int32_t)K, &L2,
-              (b.edges_sorted[lvl] ? 1 : 0) | (K > 0 ? 2 : 0), g.agg, wa,
-              g.eact[1], wa, c.t.h1 ? g.eact[0] : nullptr, c.stream);
-          if (rc == 0) fused = true;
-          else if (rc != PGNN_E_UNSUPPORTED) return rc;
-        }
-        if (!fused) {
-          rc = pgnn_edge_hidden_fwd(g.p, g.q, wq, b.edges[lvl], E, g.eact[0],
-                                    c.stream);
-          if (rc) return rc;
-          for (size_t i = 1; i < s.a.size(); ++i) {
-            rc = fc_fwd(c, s.a[i], g.eact[i - 1], pad16(s.a[i - 1].ref.n_out), E,
-                        true, nullptr, 0, g.eact[i]);
-            if (rc) return rc;
-          }
-          rc = pgnn_scatter_max_f32(g.eact[s.a.size() - 1], wa, g.dst, E, wa,
-                                    (int32_t)K, g.agg, wa,
-                                    b.edges_sorted[lvl] ? 1 : 0, c.stream);
-          if (rc) return rc;
-        }
-        {  // update MLP, last layer linear, + h (gnn.py:372): one launch
-          const FcDev *fs[PGNN_TRAIN_MAX_FC];
-          int rf[PGNN_TRAIN_MAX_FC];
-          for (size_t i = 0; i < s.b.size(); ++i) {
-            fs[i] = &s.b[i];
-            rf[i] = i + 1 < s.b.size() ? 0 : s.b[i].ref.n_out;
-          }
-          rc = fc_chain_fwd(c, fs, rf, (int)s.b.size(), g.agg, wa, K, h, ld_h,
-                            g.uact);
-          if (rc) return rc;
-        }
-      }
-      h = g.uact[s.b.size() - 1];
-      ld_h = pad16(s.b.back().ref.n_out);
-      k_h = K;
-    }
+  const float *delta = nullptr;
+  int64_t ld_delta = 0;
+  if (!s.c.empty()) {  // offset MLP, last layer linear: one launch
+    const Chain ch = chain_of(s.c, true);
+    rc = fc_chain_fwd(c, ch.fs, ch.rf, ch.n, h, ld_h, K, nullptr, 0, g.off_act);
+    if (rc) return rc;
+    delta = g.off_act[s.c.size() - 1];
+    ld_delta = pad16(s.c.back().ref.n_out);
   }
-  // prediction heads (gnn.py:133-163)
-  const int64_t K = b.n_vertices[b.n_levels];
-  const int nc = t.m.num_classes, L = t.m.box_len;
-  HeadsSaved &hs = sv.heads;
-  sv.h_final = h;
-  sv.ld_h_final = ld_h;
-  sv.k_final = K;
-  PGNN_REQUIRE(c.dry || (h != nullptr && k_h == K), PGNN_E_INVALID,
-               "trainer: heads need the last level's vertex features");
-  if (!t.groups.empty()) {
-    PGNN_REQUIRE(t.groups.size() <= 4, PGNN_E_UNSUPPORTED,
-                 "trainer: too many head groups");
-    for (size_t gi = 0; gi < t.groups.size(); ++gi) {
-      HeadGroup &g = t.groups[gi];
-      hs.y1[gi] = c.ws.f(K, pad16(g.f[0].ref.n_out));
-      hs.y2[gi] = c.ws.f(K, pad16(g.f[1].ref.n_out));
-      hs.y3[gi] = c.ws.f(K, pad16(g.f[2].ref.n_out));
-    }
-    hs.logits = c.ws.f(K, pad16(nc));
-    hs.pred = c.ws.f(K, (int64_t)nc * L);
-    if (!c.dry) {
-      for (size_t gi = 0; gi < t.groups.size(); ++gi) {
-        HeadGroup &g = t.groups[gi];
-        {  // the group's three layers (ReLU | ReLU from `base` | linear)
-          const FcDev *fs[3] = {&g.f[0], &g.f[1], &g.f[2]};
-          const int rf[3] = {0, g.base, g.f[2].ref.n_out};
-          float *outs[3] = {hs.y1[gi], hs.y2[gi], hs.y3[gi]};
-          rc = fc_chain_fwd(c, fs, rf, 3, h, ld_h, K, nullptr, 0, outs);
-          if (rc) return rc;
-        }
-        if (K > 0) {
-          const int ld3 = pad16(g.f[2].ref.n_out);
-          bool run = true;  // lids of a group are consecutive
-          for (size_t i = 1; i < g.lids.size(); ++i)
-            run = run && g.lids[i] == g.lids[0] + (int)i;
-          if (run) {
-            const int ncp = pad16(nc);
-            hipLaunchKernelGGL(
-                pred_slices_kernel,
-                dim3(blocks_for(K * (L * (int64_t)g.lids.size() + ncp))),
-                dim3(256), 0, c.stream, hs.y3[gi], (int64_t)ld3, K, L, nc,
-                g.lids.empty() ? 0 : g.lids[0], (int)g.lids.size(), g.base,
-                hs.pred, g.has_cls ? hs.logits : nullptr, ncp);
-          } else {
-            if (g.has_cls)
-              hipLaunchKernelGGL(block_copy_kernel<false>,
-                                 dim3(blocks_for(K * pad16(nc))), dim3(256), 0,
-                                 c.stream, hs.logits, (int64_t)pad16(nc), 0,
-                                 hs.y3[gi], (int64_t)ld3, 0, K, pad16(nc));
-            for (size_t i = 0; i < g.lids.size(); ++i)
-              hipLaunchKernelGGL(pred_slice_kernel, dim3(blocks_for(K * L)),
-                                 dim3(256), 0, c.stream,
-                                 hs.y3[gi] + g.base + 8 * (int)i, (int64_t)ld3, K,
-                                 L, nc, g.lids[i], hs.pred);
-          }
-        }
-      }
-      PGNN_HIP(hipGetLastError());
-    }
-    return 0;
+  if (K > 0)
+    hipLaunchKernelGGL(pre_edge_prep_kernel,
+                       dim3(blocks_for(K * (ldhx > wq ? ldhx : wq), 8192)),
+                       dim3(256), 0, c.stream, h, (int64_t)ld_h, cc, b.coords[lvl],
+                       delta, ld_delta, K, s.wx, g.hx, ldhx, g.xx, g.xo, g.q, wq,
+                       g.agg, (int64_t)K * wa);
+  rc = fc_fwd(c, w1, g.hx, ldhx, K, false, nullptr, 0, g.p);
+  if (rc) return rc;
+  bool fused = false;
+  if (s.a.size() == 2 && s.a[1].want_wt) {
+    // gather + last edge layer + scatter-max in ONE kernel that also
+    // writes the layer's rows and the gathered hidden rows H1
+    const pgnn_fc_layer L2 = {s.a[1].packed, s.a[1].ref.k_in, s.a[1].ref.n_out, 0};
+    rc = pgnn_edge_mlp_scatter_max_rows_fwd(
+        g.p, g.q, wq, s.a[1].ref.k_in, b.edges[lvl], E, (int32_t)K, &L2,
+        (b.edges_sorted[lvl] ? 1 : 0) | (K > 0 ? 2 : 0), g.agg, wa, g.eact[1], wa,
+        c.t.h1 ? g.eact[0] : nullptr, c.stream);
+    if (rc == 0) fused = true;
+    else if (rc != PGNN_E_UNSUPPORTED) return rc;
   }
-  hs.c1 = c.ws.f(K, pad16(t.cls[0].ref.n_out));
-  hs.logits = c.ws.f(K, pad16(nc));
+  if (!fused) {
+    rc = pgnn_edge_hidden_fwd(g.p, g.q, wq, b.edges[lvl], E, g.eact[0], c.stream);
+    if (rc) return rc;
+    rc = edge_layers_fwd(c, s, 1, g.eact[0], wq, g.eact, g.dst, g.agg);
+    if (rc) return rc;
+  }
+  // update MLP, last layer linear, + h (gnn.py:372): one launch
+  const Chain ch = chain_of(s.b, true);
+  return fc_chain_fwd(c, ch.fs, ch.rf, ch.n, g.agg, wa, K, h, ld_h, g.uact);
+}
+
+// prediction heads (gnn.py:133-163): as fused groups of three layers each, or
+// one by one (shapes plan_head_groups does not take)
+int heads_fwd(Ctx &c) {
+  Trainer &t = c.t;
+  const HeadsSaved &hs = c.sv.heads;
+  const int64_t K = c.sv.k_final;
+  const float *h = c.sv.h_final;
+  const int ld_h = c.sv.ld_h_final;
+  const int nc = t.m.num_classes, L = t.m.box_len, ncp = pad16(nc);
+  int rc = 0;
+  for (size_t gi = 0; gi < t.groups.size(); ++gi) {
+    HeadGroup &g = t.groups[gi];
+    // the group's three layers (ReLU | ReLU from `base` | linear)
+    const FcDev *fs[3] = {&g.f[0], &g.f[1], &g.f[2]};
+    const int rf[3] = {0, g.base, g.f[2].ref.n_out};
+    float *outs[3] = {hs.y1[gi], hs.y2[gi], hs.y3[gi]};
+    rc = fc_chain_fwd(c, fs, rf, 3, h, ld_h, K, nullptr, 0, outs);
+    if (rc) return rc;
+    if (K == 0) continue;
+    const int ld3 = pad16(g.f[2].ref.n_out);
+    // (the box heads of a group are consecutive: plan_head_groups, and
+    // fused_dy3_kernel in the backward relies on it too)
+    hipLaunchKernelGGL(pred_slices_kernel,
+                       dim3(blocks_for(K * (L * (int64_t)g.lids.size() + ncp))),
+                       dim3(256), 0, c.stream, hs.y3[gi], (int64_t)ld3, K, L, nc,
+                       g.lids.empty() ? 0 : g.lids[0], (int)g.lids.size(), g.base,
+                       hs.pred, g.has_cls ? hs.logits : nullptr, ncp);
+  }
+  if (!t.groups.empty()) return 0;
+  rc = fc_fwd(c, t.cls[0], h, ld_h, K, true, nullptr, 0, hs.c1);
+  if (rc) return rc;
+  rc = fc_fwd(c, t.cls[1], hs.c1, pad16(t.cls[0].ref.n_out), K, false, nullptr, 0,
+              hs.logits);
+  if (rc) return rc;
   for (int j = 0; j < nc; ++j) {
-    hs.l1[j] = c.ws.f(K, pad16(t.loc[3 * j].ref.n_out));
-    hs.l2[j] = c.ws.f(K, pad16(t.loc[3 * j + 1].ref.n_out));
-    hs.l3[j] = c.ws.f(K, pad16(L));
-  }
-  hs.pred = c.ws.f(K, (int64_t)nc * L);
-  if (!c.dry) {
-    rc = fc_fwd(c, t.cls[0], h, ld_h, K, true, nullptr, 0, hs.c1);
+    const FcDev *f = &t.loc[3 * (size_t)j];
+    rc = fc_fwd(c, f[0], h, ld_h, K, true, nullptr, 0, hs.l1[j]);
     if (rc) return rc;
-    rc = fc_fwd(c, t.cls[1], hs.c1, pad16(t.cls[0].ref.n_out), K, false, nullptr,
-                0, hs.logits);
+    rc = fc_fwd(c, f[1], hs.l1[j], pad16(f[0].ref.n_out), K, true, nullptr, 0,
+                hs.l2[j]);
     if (rc) return rc;
-    for (int j = 0; j < nc; ++j) {
-      rc = fc_fwd(c, t.loc[3 * j], h, ld_h, K, true, nullptr, 0, hs.l1[j]);
-      if (rc) return rc;
-      rc = fc_fwd(c, t.loc[3 * j + 1], hs.l1[j], pad16(t.loc[3 * j].ref.n_out), K,
-                  true, nullptr, 0, hs.l2[j]);
-      if (rc) return rc;
-      rc = fc_fwd(c, t.loc[3 * j + 2], hs.l2[j],
-                  pad16(t.loc[3 * j + 1].ref.n_out), K, false, nullptr, 0,
-                  hs.l3[j]);
-      if (rc) return rc;
-      if (K > 0)
-        hipLaunchKernelGGL(pred_slice_kernel, dim3(blocks_for(K * L)), dim3(256), 0,
-                           c.stream, hs.l3[j], (int64_t)pad16(L), K, L, nc, j,
-                           hs.pred);
-    }
-    PGNN_HIP(hipGetLastError());
+    rc = fc_fwd(c, f[2], hs.l2[j], pad16(f[1].ref.n_out), K, false, nullptr, 0,
+                hs.l3[j]);
+    if (rc) return rc;
+    if (K > 0)
+      hipLaunchKernelGGL(pred_slice_kernel, dim3(blocks_for(K * L)), dim3(256), 0,
+                         c.stream, hs.l3[j], (int64_t)pad16(L), K, L, nc, j,
+                         hs.pred);
   }
+  return 0;
+}
+
+int forward_impl(Ctx &c) {
+  Trainer &t = c.t;
+  int64_t k_h = 0;  // rows of vertex features the stages so far left
+  for (size_t si = 0; si < t.stages.size(); ++si) {
+    const StageDev &s = t.stages[si];
+    const int rc = s.kind == 0 ? pool_stage_fwd(c, s, c.sv.pool[si])
+                               : gnn_stage_fwd(c, s, c.sv.gnn[si], k_h);
+    if (rc) return rc;
+    k_h = c.b.n_vertices[s.level + 1];
+  }
+  PGNN_REQUIRE(c.sv.h_final != nullptr && k_h == c.sv.k_final, PGNN_E_INVALID,
+               "trainer: heads need the last level's vertex features");
+  const int rc = heads_fwd(c);
+  if (rc) return rc;
+  PGNN_HIP(hipGetLastError());
   return 0;
 }
 
@@ -1077,392 +941,258 @@ __global__ void relu_mask_cols_kernel(float *__restrict__ dy,
 }
 
 // ---- backward --------------------------------------------------------------------------
-int backward_impl(Ctx &c, Saved &sv, const float *dlogits, const float *dpred) {
+// dh = gradient w.r.t. the heads' input.  Fused groups (three layers each): the
+// first writes it, the others add theirs through dxh.  One by one: into a zeroed dh.
+int heads_bwd(Ctx &c, const Grads &gr, const float *dlogits, const float *dpred,
+              float *dh) {
   Trainer &t = c.t;
-  const pgnn_train_batch &b = c.b;
-  const int64_t K = sv.k_final;
+  const HeadsSaved &hs = c.sv.heads;
+  const int64_t K = c.sv.k_final;
+  const float *h = c.sv.h_final;
   const int nc = t.m.num_classes, L = t.m.box_len;
-  const int hw = sv.ld_h_final;
-  const HeadsSaved &hs = sv.heads;
-  int rc = 0;
-  // gradient w.r.t. the output of stage i: dhs[i + 1] (dhs[n] = w.r.t. the
-  // input of the heads).  One buffer per boundary: each is also the dY of a
-  // deferred weight gradient and must survive until the end of the backward.
-  const int n_stages = (int)t.stages.size();
-  std::vector<float *> dhs((size_t)n_stages + 1);
-  for (int i = 0; i <= n_stages; ++i) dhs[(size_t)i] = c.ws.f(K, hw);
-  float *dh = dhs[(size_t)n_stages];
-  float *dxh = c.ws.f(K, hw);
-  const int cw = t.cls[0].ref.k_in;
-  if (!t.groups.empty()) {
-    // fused heads: three layers per group
-    int w1 = 16, w2 = 16, w3 = 16;
-    for (const HeadGroup &g : t.groups) {
-      w1 = pad16(g.f[0].ref.n_out) > w1 ? pad16(g.f[0].ref.n_out) : w1;
-      w2 = pad16(g.f[1].ref.n_out) > w2 ? pad16(g.f[1].ref.n_out) : w2;
-      w3 = pad16(g.f[2].ref.n_out) > w3 ? pad16(g.f[2].ref.n_out) : w3;
-    }
-    // (one set per group: the buffers are the dY of deferred weight gradients)
-    std::vector<float *> dy3s, dy2s, dy1s;
-    for (size_t gi = 0; gi < t.groups.size(); ++gi) {
-      dy3s.push_back(c.ws.f(K, w3));
-      dy2s.push_back(c.ws.f(K, w2));
-      dy1s.push_back(c.ws.f(K, w1));
-    }
-    if (!c.dry && K > 0) {
-      for (size_t gi = 0; gi < t.groups.size(); ++gi) {
-        HeadGroup &g = t.groups[gi];
-        float *dy3 = dy3s[gi], *dy2 = dy2s[gi], *dy1 = dy1s[gi];
-        const int ld1 = pad16(g.f[0].ref.n_out), ld2 = pad16(g.f[1].ref.n_out),
-                  ld3 = pad16(g.f[2].ref.n_out);
-        hipLaunchKernelGGL(fused_dy3_kernel, dim3(blocks_for(K * ld3)), dim3(256),
-                           0, c.stream, dlogits, dpred, K, nc, L,
-                           g.has_cls ? 1 : 0, g.base, (int)g.lids.size(),
-                           g.lids.empty() ? 0 : g.lids[0], dy3, ld3);
-        // the fused gradients are overwritten (accumulate = false) and handed
-        // to the flat buffer by the unpack jobs at the end
-        rc = fc_bwd(c, sv, g.f[2], sv.heads.y2[gi], ld2, nullptr, dy3, K, false,
-                    dy2, false, true);
-        if (rc) return rc;
-        // second layer: ReLU on the box-head columns only (logits are linear)
-        if (g.f[1].ref.n_out > g.base)
-          hipLaunchKernelGGL(relu_mask_cols_kernel,
-                             dim3(blocks_for(K * (g.f[1].ref.n_out - g.base))),
-                             dim3(256), 0, c.stream, dy2, sv.heads.y2[gi], K, ld2,
-                             g.base, g.f[1].ref.n_out);
-        {  // layers 2 and 1 in one launch (dy1 leaves masked by y1 > 0: the
-           // first layer's ReluGrad)
-          const FcDev *fs[2] = {&g.f[0], &g.f[1]};
-          const float *xin[2] = {sv.h_final, sv.heads.y1[gi]};
-          const int64_t ldx[2] = {hw, ld1};
-          float *dxs[2] = {gi == 0 ? dh : dxh, dy1};
-          const bool gate[2] = {false, true};
-          rc = fc_chain_bwd(c, sv, fs, 2, xin, ldx, dy2, K, dxs, gate, false);
-          if (rc) return rc;
-        }
-        if (gi > 0)
-          hipLaunchKernelGGL(block_copy_kernel<true>, dim3(blocks_for(K * cw)),
-                             dim3(256), 0, c.stream, dh, (int64_t)hw, 0, dxh,
-                             (int64_t)pad16(cw), 0, K, cw);
-      }
-      // (the unpack of the fused gradients follows the deferred weight
-      // gradients at the end of the backward)
-    }
-  } else {
-  const int w64 = pad16(t.cls[0].ref.n_out);
-  int wh = w64;  // widest hidden layer of the heads
-  for (const FcDev &f : t.loc)
-    if (pad16(f.ref.n_out) > wh) wh = pad16(f.ref.n_out);
-  float *dy = c.ws.f(K, pad16(nc > L ? nc : L));
-  float *d1 = c.ws.f(K, wh), *d2 = c.ws.f(K, wh);
-  if (!c.dry && K > 0) {
-    PGNN_HIP(hipMemsetAsync(dh, 0, (size_t)K * hw * 4, c.stream));
-    // class head
-    PGNN_HIP(hipMemsetAsync(dy, 0, (size_t)K * pad16(nc) * 4, c.stream));
-    hipLaunchKernelGGL(block_copy_kernel<false>, dim3(blocks_for(K * nc)),
-                       dim3(256), 0, c.stream, dy, (int64_t)pad16(nc), 0, dlogits,
-                       (int64_t)nc, 0, K, nc);
-    rc = fc_bwd(c, sv, t.cls[1], hs.c1, w64, hs.logits, dy, K, false, d1, true,
-                false, true);
-    if (rc) return rc;
-    rc = fc_bwd(c, sv, t.cls[0], sv.h_final, hw, hs.c1, d1, K, false, dxh);
-    if (rc) return rc;
+  const int hw = c.sv.ld_h_final, cw = t.cls[0].ref.k_in;
+  float *dy = gr.dy, *d1 = gr.d1, *d2 = gr.d2, *dxh = gr.dxh;
+  auto add_dxh = [&] {
     hipLaunchKernelGGL(block_copy_kernel<true>, dim3(blocks_for(K * cw)),
                        dim3(256), 0, c.stream, dh, (int64_t)hw, 0, dxh,
                        (int64_t)pad16(cw), 0, K, cw);
-    for (int j = 0; j < nc; ++j) {
-      hipLaunchKernelGGL(dpred_slice_kernel, dim3(blocks_for(K * pad16(L))),
-                         dim3(256), 0, c.stream, dpred, K, L, nc, j, dy,
-                         pad16(L));
-      rc = fc_bwd(c, sv, t.loc[3 * j + 2], hs.l2[j],
-                  pad16(t.loc[3 * j + 1].ref.n_out), hs.l3[j], dy, K, false, d2,
-                  true, false, true);
+  };
+  int rc = 0;
+  for (size_t gi = 0; gi < t.groups.size(); ++gi) {
+    HeadGroup &g = t.groups[gi];
+    float *dy3 = gr.dy3[gi], *dy2 = gr.dy2[gi], *dy1 = gr.dy1[gi];
+    const int ld1 = pad16(g.f[0].ref.n_out), ld2 = pad16(g.f[1].ref.n_out),
+              ld3 = pad16(g.f[2].ref.n_out);
+    hipLaunchKernelGGL(fused_dy3_kernel, dim3(blocks_for(K * ld3)), dim3(256), 0,
+                       c.stream, dlogits, dpred, K, nc, L, g.has_cls ? 1 : 0,
+                       g.base, (int)g.lids.size(), g.lids.empty() ? 0 : g.lids[0],
+                       dy3, ld3);
+    // the fused gradients are overwritten (accumulate = false) and handed
+    // to the flat buffer by the unpack jobs at the end of the backward
+    rc = fc_bwd(c, g.f[2], hs.y2[gi], ld2, dy3, K, dy2, false, true);
+    if (rc) return rc;
+    // second layer: ReLU on the box-head columns only (logits are linear)
+    if (g.f[1].ref.n_out > g.base)
+      hipLaunchKernelGGL(relu_mask_cols_kernel,
+                         dim3(blocks_for(K * (g.f[1].ref.n_out - g.base))),
+                         dim3(256), 0, c.stream, dy2, hs.y2[gi], K, ld2, g.base,
+                         g.f[1].ref.n_out);
+    {  // layers 2 and 1 in one launch (dy1 leaves masked by y1 > 0: the
+       // first layer's ReluGrad)
+      const FcDev *fs[2] = {&g.f[0], &g.f[1]};
+      const float *xin[2] = {h, hs.y1[gi]};
+      const int64_t ldx[2] = {hw, ld1};
+      float *dxs[2] = {gi == 0 ? dh : dxh, dy1};
+      const bool gate[2] = {false, true};
+      rc = fc_chain_bwd(c, fs, 2, xin, ldx, dy2, K, dxs, gate, false);
       if (rc) return rc;
-      rc = fc_bwd(c, sv, t.loc[3 * j + 1], hs.l1[j],
-                  pad16(t.loc[3 * j].ref.n_out), hs.l2[j], d2, K, false, d1, true,
-                  false, true);
-      if (rc) return rc;
-      rc = fc_bwd(c, sv, t.loc[3 * j], sv.h_final, hw, hs.l1[j], d1, K, false, dxh);
-      if (rc) return rc;
-      hipLaunchKernelGGL(block_copy_kernel<true>, dim3(blocks_for(K * cw)),
-                         dim3(256), 0, c.stream, dh, (int64_t)hw, 0, dxh,
-                         (int64_t)pad16(cw), 0, K, cw);
     }
+    if (gi > 0) add_dxh();
   }
+  if (!t.groups.empty()) return 0;
+  PGNN_HIP(hipMemsetAsync(dh, 0, (size_t)K * hw * 4, c.stream));
+  // class head
+  PGNN_HIP(hipMemsetAsync(dy, 0, (size_t)K * pad16(nc) * 4, c.stream));
+  hipLaunchKernelGGL(block_copy_kernel<false>, dim3(blocks_for(K * nc)), dim3(256),
+                     0, c.stream, dy, (int64_t)pad16(nc), 0, dlogits, (int64_t)nc,
+                     0, K, nc);
+  rc = fc_bwd(c, t.cls[1], hs.c1, pad16(t.cls[0].ref.n_out), dy, K, d1, true, false,
+              true);
+  if (rc) return rc;
+  rc = fc_bwd(c, t.cls[0], h, hw, d1, K, dxh);
+  if (rc) return rc;
+  add_dxh();
+  for (int j = 0; j < nc; ++j) {
+    const FcDev *f = &t.loc[3 * (size_t)j];
+    hipLaunchKernelGGL(dpred_slice_kernel, dim3(blocks_for(K * pad16(L))),
+                       dim3(256), 0, c.stream, dpred, K, L, nc, j, dy, pad16(L));
+    rc = fc_bwd(c, f[2], hs.l2[j], pad16(f[1].ref.n_out), dy, K, d2, true, false,
+                true);
+    if (rc) return rc;
+    rc = fc_bwd(c, f[1], hs.l1[j], pad16(f[0].ref.n_out), d2, K, d1, true, false,
+                true);
+    if (rc) return rc;
+    rc = fc_bwd(c, f[0], h, hw, d1, K, dxh);
+    if (rc) return rc;
+    add_dxh();
   }
-  // stages in reverse
-  for (int si = (int)t.stages.size() - 1; si >= 0; --si) {
-    StageDev &s = t.stages[si];
-    const int lvl = s.level;
-    const int64_t E = b.n_edges[lvl], Ks = b.n_vertices[lvl + 1];
-    // gradient w.r.t. this stage's output / input
-    float *dh = dhs[(size_t)si + 1], *dh2 = dhs[(size_t)si];
-    if (s.kind == 1) {
-      GnnSaved &g = sv.gnn[si];
-      const FcDev &w1 = s.a[0];
-      const int cc = w1.ref.k_in - 3;
-      const int wq = pad16(w1.ref.n_out);
-      const int wa = pad16(s.a.back().ref.n_out);
-      const int ld_h = hw;
-      // K-row buffers first: they are the dY of deferred weight gradients and
-      // stay until the end of the backward; the E-row temporaries behind the
-      // mark are released with the stage
-      float *du[PGNN_TRAIN_MAX_FC + 1];
-      for (size_t i = 0; i < s.b.size(); ++i)
-        du[i] = c.ws.f(Ks, pad16(s.b[i].ref.k_in));
-      float *dp = c.ws.f(2 * Ks, wq);  // dP | dQ back to back: one fill
-      float *dq = dp ? dp + Ks * wq : nullptr;
-      float *dhx = c.ws.f(Ks, pad16(cc + 3));
-      float *dxo = c.ws.f(Ks, 16);
-      float *doff[PGNN_TRAIN_MAX_FC];
-      for (size_t i = 0; i < s.c.size(); ++i)
-        doff[i] = c.ws.f(Ks, pad16(s.c[i].ref.k_in));
-      const size_t mark = c.ws.off;
-      float *ge[PGNN_TRAIN_MAX_FC] = {nullptr};
-      if (!(s.a.back().want_wt && s.a.size() == 2))
-        for (size_t i = 0; i + 1 < s.a.size(); ++i)
-          ge[i] = c.ws.f(E, pad16(s.a[i + 1].ref.k_in));  // grad w.r.t. eact[i]
-      float *gz = nullptr;  // dense fallback: grad w.r.t. the last edge layer
-      if (!s.a.back().want_wt) gz = c.ws.f(E, wa);
-      int32_t *ties = nullptr;
-      if (!s.a.back().want_wt) ties = c.ws.i32(Ks * wa > 0 ? Ks * wa : 1);
-      if (!c.dry && Ks > 0) {
-        // (residual branch, gnn.py:372: dh_in = dh + what the edge input and
-        // the offset MLP send back -- summed in one pass at the stage's end)
-        // update MLP, last layer linear
-        // (one launch; the ReluGrad of layer i - 1 leaves with du[i])
-        {
-          const FcDev *fs[PGNN_TRAIN_MAX_FC];
-          const float *xin[PGNN_TRAIN_MAX_FC];
-          int64_t ldx[PGNN_TRAIN_MAX_FC];
-          bool gate[PGNN_TRAIN_MAX_FC];
-          for (size_t i = 0; i < s.b.size(); ++i) {
-            fs[i] = &s.b[i];
-            xin[i] = i == 0 ? g.agg : g.uact[i - 1];
-            ldx[i] = i == 0 ? wa : pad16(s.b[i - 1].ref.n_out);
-            gate[i] = i > 0;
-          }
-          rc = fc_chain_bwd(c, sv, fs, (int)s.b.size(), xin, ldx, dh, Ks, du, gate);
-          if (rc) return rc;
-        }
-        const float *dagg = du[0];  // [Ks, pad(k_in of b[0])] = [Ks, wa]
-        const int na = (int)s.a.size();
-        float *gcur = nullptr;  // grad w.r.t. eact[i], ReLU-masked
-        int from;
-        bool scattered = false;
-        if (s.a.back().want_wt && na == 2) {
-          // last edge layer + scatter-max + the gather's adjoint in one
-          // routing pass: dP / dQ directly, dH1 is never written
-          rc = pgnn_edge_segmax_fc_bwd_f32(
-              g.eact[1], wa, b.edges[lvl], g.dst, E, s.a[1].ref.n_out,
-              (int32_t)Ks, g.agg, wa, dagg, wa, c.t.h1 ? g.eact[0] : nullptr,
-              wq, g.p, g.q,
-              s.a[1].ref.k_in, s.a[1].wt, pad16(s.a[1].ref.k_in), dp, dq, wq,
-              s.a[1].gw, s.a[1].gb, sv.scratch, sv.scratch_bytes, c.stream);
-          if (rc) return rc;
-          scattered = true;
-          from = 0;
-        } else if (s.a.back().want_wt) {
-          rc = pgnn_segmax_fc_bwd_f32(
-              g.eact[na - 1], wa, g.dst, E, s.a.back().ref.n_out, (int32_t)Ks,
-              g.agg, wa, dagg, wa, g.eact[na - 2], pad16(s.a.back().ref.k_in),
-              s.a.back().ref.k_in, s.a.back().wt, pad16(s.a.back().ref.k_in),
-              ge[na - 2], pad16(s.a.back().ref.k_in), pad16(s.a.back().ref.k_in),
-              1, s.a.back().gw, s.a.back().gb, sv.scratch, sv.scratch_bytes,
-              c.stream);
-          if (rc) return rc;
-          gcur = ge[na - 2];
-          from = na - 2;
-        } else {
-          rc = pgnn_scatter_max_bwd_f32(g.eact[na - 1], wa, g.dst, E, wa,
-                                        (int32_t)Ks, g.agg, wa, dagg, wa, ties,
-                                        gz, wa, 1, c.stream);
-          if (rc) return rc;
-          gcur = gz;
-          from = na - 1;
-        }
-        for (int i = from; i >= 1; --i) {  // dense middle edge layers
-          rc = fc_bwd(c, sv, s.a[i], g.eact[i - 1], pad16(s.a[i].ref.k_in),
-                      g.eact[i], gcur, E, false, ge[i - 1], true, false, true);
-          if (rc) return rc;
-          gcur = ge[i - 1];
-        }
-        if (!scattered) {
-          rc = pgnn_edge_hidden_bwd(gcur, wq, b.edges[lvl], E, Ks, dp, dq,
-                                    c.stream);
-          if (rc) return rc;
-        }
-        // P = [h, x] W1 + b1 and Q = x' Wx, Wx = rows cc..cc+2 of W1 (the
-        // minus sign is in dq).  Those three rows of dW are
-        //   sum_v x_v dP_v + sum_v x'_v dQ_v = sum_e (x_src - x'_dst) dH1_e:
-        // two sums of coordinate-sized terms (tens of metres) that cancel
-        // down to offset-sized ones.  They are ONE job over the stacked rows
-        // [x; x'] (g.xx) and [dP; dQ] (back to back) in the second batch,
-        // whose few narrow jobs get short row slices: as a part of w1's job
-        // in the first batch (long slices) their float32 rounding reached
-        // 1e-5 of the gradient's scale at the benchmarked batch size.
-        if (w1.ref.n_out <= 320) {  // (fc_wgrad defers exactly these)
-          defer_wgrad(c, g.hx, pad16(cc + 3), cc, dp, wq, w1.ref.n_out, Ks,
-                      w1.gw, w1.gb, true);
-          rc = fc_dx(c, w1, dp, wq, Ks, dhx);
-          if (rc) return rc;
-          pgnn_wgrad_job j = {};
-          j.X = g.xx;
-          j.ld_x = 3;
-          j.dZ = dp;
-          j.ld_dz = wq;
-          j.n_rows = 2 * Ks;
-          j.dW = w1.gw + (int64_t)cc * w1.ref.n_out;
-          j.db = nullptr;
-          j.k_in = 3;
-          j.n_out = w1.ref.n_out;
-          j.accumulate = 1;
-          c.wjobs2.push_back(j);
-        } else {
-          rc = fc_bwd(c, sv, w1, g.hx, pad16(cc + 3), nullptr, dp, Ks, false,
-                      dhx, true, true);
-          if (rc) return rc;
-          // (it adds into rows of the same dW as w1's job above, and jobs of
-          // one batch must not share outputs: the second batch)
-          pgnn_wgrad_job j = {};
-          j.X = g.xo;
-          j.ld_x = 3;
-          j.dZ = dq;
-          j.ld_dz = wq;
-          j.n_rows = Ks;
-          j.dW = w1.gw + (int64_t)cc * w1.ref.n_out;
-          j.db = nullptr;
-          j.k_in = 3;
-          j.n_out = w1.ref.n_out;
-          j.accumulate = 1;
-          c.wjobs2.push_back(j);
-        }
-        const float *d_off = nullptr;  // grad w.r.t. h through the offset MLP
-        if (!s.c.empty()) {
-          // dx' = dQ Wx^T, then the offset MLP's backward: one launch
-          const PreDx pre = {s.wx_packed_t, w1.ref.n_out, 3, dq, wq};
-          {
-            const FcDev *fs[PGNN_TRAIN_MAX_FC];
-            const float *xin[PGNN_TRAIN_MAX_FC];
-            int64_t ldx[PGNN_TRAIN_MAX_FC];
-            bool gate[PGNN_TRAIN_MAX_FC];
-            for (size_t i = 0; i < s.c.size(); ++i) {
-              fs[i] = &s.c[i];
-              xin[i] = i == 0 ? g.h_in : g.off_act[i - 1];
-              ldx[i] = i == 0 ? ld_h : pad16(s.c[i - 1].ref.n_out);
-              gate[i] = i > 0;
-            }
-            rc = fc_chain_bwd(c, sv, fs, (int)s.c.size(), xin, ldx, dxo, Ks, doff,
-                              gate, true, &pre);
-            if (rc) return rc;
-          }
-          d_off = doff[0];
-        }
-        hipLaunchKernelGGL(stage_input_grad_kernel, dim3(blocks_for(Ks * ld_h)),
-                           dim3(256), 0, c.stream, dh, ld_h, dhx, pad16(cc + 3),
-                           d_off, s.c.empty() ? 0 : pad16(s.c[0].ref.k_in), Ks, cc,
-                           dh2);
-      }
-      c.ws.off = mark;
-    } else {
-      PoolSaved &p = sv.pool[si];
-      const int wa = pad16(s.a.back().ref.n_out);
-      float *dob[PGNN_TRAIN_MAX_FC];  // K-row: kept (deferred weight gradients)
-      for (size_t i = 0; i < s.b.size(); ++i)
-        dob[i] = c.ws.f(Ks, pad16(s.b[i].ref.k_in));
-      const size_t mark = c.ws.off;
-      float *ga[PGNN_TRAIN_MAX_FC];  // grad w.r.t. act[i] (input of layer i+1)
-      for (size_t i = 0; i + 1 < s.a.size(); ++i)
-        ga[i] = c.ws.f(E, pad16(s.a[i + 1].ref.k_in));
-      float *gz = nullptr;
-      int32_t *ties = nullptr;
-      if (!s.a.back().want_wt) {
-        gz = c.ws.f(E, wa);
-        ties = c.ws.i32(Ks * wa > 0 ? Ks * wa : 1);
-      }
-      if (!c.dry && Ks > 0) {
-        // every layer is a ReLU layer: the last one's mask is applied to dh
-        // here, the others' leave with the dX of the layer above (one launch)
-        rc = pgnn_relu_mask_mul(dh, p.oact[s.b.size() - 1],
-                                Ks * pad16(s.b.back().ref.n_out), c.stream);
-        if (rc) return rc;
-        {
-          const FcDev *fs[PGNN_TRAIN_MAX_FC];
-          const float *xin[PGNN_TRAIN_MAX_FC];
-          int64_t ldx[PGNN_TRAIN_MAX_FC];
-          bool gate[PGNN_TRAIN_MAX_FC];
-          for (size_t i = 0; i < s.b.size(); ++i) {
-            fs[i] = &s.b[i];
-            xin[i] = i == 0 ? p.agg : p.oact[i - 1];
-            ldx[i] = i == 0 ? wa : pad16(s.b[i - 1].ref.n_out);
-            gate[i] = i > 0;
-          }
-          rc = fc_chain_bwd(c, sv, fs, (int)s.b.size(), xin, ldx, dh, Ks, dob, gate);
-          if (rc) return rc;
-        }
-        float *d = dob[0];
-        const int na = (int)s.a.size();
-        float *gcur;
-        int from;
-        if (s.a.back().want_wt) {
-          rc = pgnn_segmax_fc_bwd_f32(
-              p.act[na - 1], wa, p.dst, E, s.a.back().ref.n_out, (int32_t)Ks,
-              p.agg, wa, d, wa, p.act[na - 2], pad16(s.a.back().ref.k_in),
-              s.a.back().ref.k_in, s.a.back().wt, pad16(s.a.back().ref.k_in),
-              ga[na - 2], pad16(s.a.back().ref.k_in), pad16(s.a.back().ref.k_in),
-              1, s.a.back().gw, s.a.back().gb, sv.scratch, sv.scratch_bytes,
-              c.stream);
-          if (rc) return rc;
-          gcur = ga[na - 2];
-          from = na - 2;
-        } else {
-          rc = pgnn_scatter_max_bwd_f32(p.act[na - 1], wa, p.dst, E, wa,
-                                        (int32_t)Ks, p.agg, wa, d, wa, ties, gz,
-                                        wa, 1, c.stream);
-          if (rc) return rc;
-          gcur = gz;
-          from = na - 1;
-        }
-        // the shipped car chain's three narrow layers (feat -> 32 -> 64 -> 128
-        // below the sparse 128 -> 300 layer): one fused pass over the E rows
-        const bool narrow =
-            s.a.back().want_wt && na == 4 && from == 2 &&
-            s.a[0].ref.k_in <= 15 && s.a[0].ref.n_out == 32 &&
-            s.a[1].ref.k_in == 32 && s.a[1].ref.n_out == 64 &&
-            s.a[2].ref.k_in == 64 && s.a[2].ref.n_out == 128 &&
-            s.a[1].packed_t && s.a[2].packed_t &&
-            sv.scratch_bytes >= pgnn_pool_narrow_bwd_workspace_bytes(E);
-        if (narrow) {
-          rc = pgnn_pool_narrow_bwd_f32(
-              p.feat, p.act[0], p.act[1], gcur, E, s.a[2].packed_t,
-              s.a[1].packed_t, s.a[0].ref.k_in, s.a[0].gw, s.a[0].gb, s.a[1].gw,
-              s.a[1].gb, s.a[2].gw, s.a[2].gb, 1, sv.scratch, sv.scratch_bytes,
-              c.stream);
-          if (rc) return rc;
-          from = -1;  // done
-        }
-        for (int i = from; i >= 0; --i) {
-          const float *xin = i == 0 ? p.feat : p.act[i - 1];
-          const int64_t ldx = i == 0 ? 16 : pad16(s.a[i - 1].ref.n_out);
-          rc = fc_bwd(c, sv, s.a[i], xin, ldx, p.act[i], gcur, E, false,
-                      i > 0 ? ga[i - 1] : nullptr, true, false, i > 0);
-          if (rc) return rc;
-          if (i > 0) gcur = ga[i - 1];
-        }
-      }
-      c.ws.off = mark;
+  return 0;
+}
+
+// Adjoint of "last per-edge layer + max over each destination's rows" given
+// dagg [Ks, wa]: the sparse form through the layer (pgnn_segmax_fc_bwd_f32)
+// when it has the image for it, else the dense scatter-max adjoint.  acts[i]
+// = the output rows of a[i], ge[i] the gradient w.r.t. them: *gcur = ge[*from]
+// (or gz) is ReLU-masked, and a[*from] is the next layer to go through.
+int segmax_tail_bwd(Ctx &c, const StageDev &s, float *const *acts,
+                    const int32_t *dst, const float *agg, const float *dagg,
+                    const StageGrads &sg, float **gcur, int *from) {
+  const int64_t E = c.b.n_edges[s.level], Ks = c.b.n_vertices[s.level + 1];
+  const FcDev &last = s.a.back();
+  const int na = (int)s.a.size(), wa = pad16(last.ref.n_out);
+  if (last.want_wt) {
+    const int wk = pad16(last.ref.k_in);
+    *gcur = sg.ge[na - 2];
+    *from = na - 2;
+    return pgnn_segmax_fc_bwd_f32(acts[na - 1], wa, dst, E, last.ref.n_out,
+                                  (int32_t)Ks, agg, wa, dagg, wa, acts[na - 2], wk,
+                                  last.ref.k_in, last.wt, wk, *gcur, wk, wk, 1,
+                                  last.gw, last.gb, c.sv.scratch,
+                                  c.sv.scratch_bytes, c.stream);
+  }
+  *gcur = sg.gz;
+  *from = na - 1;
+  return pgnn_scatter_max_bwd_f32(acts[na - 1], wa, dst, E, wa, (int32_t)Ks, agg,
+                                  wa, dagg, wa, sg.ties, sg.gz, wa, 1, c.stream);
+}
+
+// dh: gradient w.r.t. the stage's output, dh2: w.r.t. its input features
+// (residual branch, gnn.py:372: dh2 = dh + what the edge input and the offset
+// MLP send back -- summed in one pass at the stage's end)
+int gnn_stage_bwd(Ctx &c, const StageDev &s, const GnnSaved &g,
+                  const StageGrads &sg, float *dh, float *dh2) {
+  const pgnn_train_batch &b = c.b;
+  const int lvl = s.level;
+  const int64_t E = b.n_edges[lvl], Ks = b.n_vertices[lvl + 1];
+  const FcDev &w1 = s.a[0];
+  const int cc = w1.ref.k_in - 3, ldhx = pad16(cc + 3);
+  const int wq = pad16(w1.ref.n_out), wa = pad16(s.a.back().ref.n_out);
+  const int ld_h = c.sv.ld_h_final;
+  float *dp = sg.dp, *dq = sg.dq;
+  // update MLP, last layer linear
+  // (one launch; the ReluGrad of layer i - 1 leaves with du[i])
+  const Chain ub = chain_of(s.b, true, g.agg, wa, g.uact);
+  int rc = fc_chain_bwd(c, ub.fs, ub.n, ub.xin, ub.ldx, dh, Ks, sg.du, ub.gate);
+  if (rc) return rc;
+  const float *dagg = sg.du[0];  // [Ks, pad(k_in of b[0])] = [Ks, wa]
+  if (s.a.back().want_wt && s.a.size() == 2) {
+    // last edge layer + scatter-max + the gather's adjoint in one
+    // routing pass: dP / dQ directly, dH1 is never written
+    rc = pgnn_edge_segmax_fc_bwd_f32(
+        g.eact[1], wa, b.edges[lvl], g.dst, E, s.a[1].ref.n_out, (int32_t)Ks,
+        g.agg, wa, dagg, wa, c.t.h1 ? g.eact[0] : nullptr, wq, g.p, g.q,
+        s.a[1].ref.k_in, s.a[1].wt, pad16(s.a[1].ref.k_in), dp, dq, wq, s.a[1].gw,
+        s.a[1].gb, c.sv.scratch, c.sv.scratch_bytes, c.stream);
+    if (rc) return rc;
+  } else {
+    float *gcur;  // grad w.r.t. eact[i], ReLU-masked
+    int from;
+    rc = segmax_tail_bwd(c, s, g.eact, g.dst, g.agg, dagg, sg, &gcur, &from);
+    if (rc) return rc;
+    for (int i = from; i >= 1; --i) {  // dense middle edge layers
+      rc = fc_bwd(c, s.a[i], g.eact[i - 1], pad16(s.a[i].ref.k_in), gcur, E,
+                  sg.ge[i - 1], true, false, true);
+      if (rc) return rc;
+      gcur = sg.ge[i - 1];
     }
+    rc = pgnn_edge_hidden_bwd(gcur, wq, b.edges[lvl], E, Ks, dp, dq, c.stream);
+    if (rc) return rc;
+  }
+  // P = [h, x] W1 + b1 and Q = x' Wx, Wx = rows cc..cc+2 of W1 (the
+  // minus sign is in dq).  Those three rows of dW are
+  //   sum_v x_v dP_v + sum_v x'_v dQ_v = sum_e (x_src - x'_dst) dH1_e:
+  // two sums of coordinate-sized terms (tens of metres) that cancel
+  // down to offset-sized ones.  They are ONE job over the stacked rows
+  // [x; x'] (g.xx) and [dP; dQ] (back to back) in the second batch,
+  // whose few narrow jobs get short row slices: as a part of w1's job
+  // in the first batch (long slices) their float32 rounding reached
+  // 1e-5 of the gradient's scale at the benchmarked batch size.
+  if (w1.ref.n_out <= 320) {  // (fc_wgrad defers exactly these)
+    defer_wgrad(c.wjobs, g.hx, ldhx, cc, dp, wq, w1.ref.n_out, Ks, w1.gw, w1.gb,
+                true);
+    rc = fc_dx(c, w1, dp, wq, Ks, sg.dhx);
+    if (rc) return rc;
+    defer_coord_wgrad(c, w1, g.xx, dp, wq, 2 * Ks);
+  } else {
+    rc = fc_bwd(c, w1, g.hx, ldhx, dp, Ks, sg.dhx, true, true);
+    if (rc) return rc;
+    defer_coord_wgrad(c, w1, g.xo, dq, wq, Ks);
+  }
+  const float *d_off = nullptr;  // grad w.r.t. h through the offset MLP
+  if (!s.c.empty()) {
+    // dx' = dQ Wx^T, then the offset MLP's backward: one launch
+    const PreDx pre = {s.wx_packed_t, w1.ref.n_out, 3, dq, wq};
+    const Chain ob = chain_of(s.c, true, g.h_in, ld_h, g.off_act);
+    rc = fc_chain_bwd(c, ob.fs, ob.n, ob.xin, ob.ldx, sg.dxo, Ks, sg.doff, ob.gate,
+                      true, &pre);
+    if (rc) return rc;
+    d_off = sg.doff[0];
+  }
+  hipLaunchKernelGGL(stage_input_grad_kernel, dim3(blocks_for(Ks * ld_h)),
+                     dim3(256), 0, c.stream, dh, ld_h, sg.dhx, ldhx, d_off,
+                     s.c.empty() ? 0 : pad16(s.c[0].ref.k_in), Ks, cc, dh2);
+  return 0;
+}
+
+int pool_stage_bwd(Ctx &c, const StageDev &s, const PoolSaved &p,
+                   const StageGrads &sg, float *dh) {
+  const int64_t E = c.b.n_edges[s.level], Ks = c.b.n_vertices[s.level + 1];
+  const int wa = pad16(s.a.back().ref.n_out), na = (int)s.a.size();
+  // every layer is a ReLU layer: the last one's mask is applied to dh
+  // here, the others' leave with the dX of the layer above (one launch)
+  int rc = pgnn_relu_mask_mul(dh, p.oact[s.b.size() - 1],
+                              Ks * pad16(s.b.back().ref.n_out), c.stream);
+  if (rc) return rc;
+  const Chain ob = chain_of(s.b, false, p.agg, wa, p.oact);
+  rc = fc_chain_bwd(c, ob.fs, ob.n, ob.xin, ob.ldx, dh, Ks, sg.du, ob.gate);
+  if (rc) return rc;
+  float *gcur;  // grad w.r.t. act[i], ReLU-masked
+  int from;
+  rc = segmax_tail_bwd(c, s, p.act, p.dst, p.agg, sg.du[0], sg, &gcur, &from);
+  if (rc) return rc;
+  // the shipped car chain's three narrow layers (feat -> 32 -> 64 -> 128
+  // below the sparse 128 -> 300 layer): one fused pass over the E rows
+  const bool narrow =
+      s.a.back().want_wt && na == 4 && from == 2 && s.a[0].ref.k_in <= 15 &&
+      s.a[0].ref.n_out == 32 && s.a[1].ref.k_in == 32 && s.a[1].ref.n_out == 64 &&
+      s.a[2].ref.k_in == 64 && s.a[2].ref.n_out == 128 && s.a[1].packed_t &&
+      s.a[2].packed_t &&
+      c.sv.scratch_bytes >= pgnn_pool_narrow_bwd_workspace_bytes(E);
+  if (narrow)
+    return pgnn_pool_narrow_bwd_f32(
+        p.feat, p.act[0], p.act[1], gcur, E, s.a[2].packed_t, s.a[1].packed_t,
+        s.a[0].ref.k_in, s.a[0].gw, s.a[0].gb, s.a[1].gw, s.a[1].gb, s.a[2].gw,
+        s.a[2].gb, 1, c.sv.scratch, c.sv.scratch_bytes, c.stream);
+  for (int i = from; i >= 0; --i) {
+    const float *xin = i == 0 ? p.feat : p.act[i - 1];
+    const int64_t ldx = i == 0 ? 16 : pad16(s.a[i - 1].ref.n_out);
+    rc = fc_bwd(c, s.a[i], xin, ldx, gcur, E, i > 0 ? sg.ge[i - 1] : nullptr,
+                true, false, i > 0);
+    if (rc) return rc;
+    if (i > 0) gcur = sg.ge[i - 1];
+  }
+  return 0;
+}
+
+int backward_impl(Ctx &c, const Grads &gr, const float *dlogits,
+                  const float *dpred) {
+  Trainer &t = c.t;
+  const int n_stages = (int)t.stages.size();
+  const int64_t K = c.sv.k_final;
+  int rc = 0;
+  if (K > 0) {
+    rc = heads_bwd(c, gr, dlogits, dpred, gr.dhs[n_stages]);
+    if (rc) return rc;
+  }
+  for (int si = n_stages - 1; si >= 0; --si) {  // stages in reverse
+    const StageDev &s = t.stages[(size_t)si];
+    if (c.b.n_vertices[s.level + 1] == 0) continue;
+    rc = s.kind == 1 ? gnn_stage_bwd(c, s, c.sv.gnn[si], gr.stage[si],
+                                     gr.dhs[si + 1], gr.dhs[si])
+                     : pool_stage_bwd(c, s, c.sv.pool[si], gr.stage[si],
+                                      gr.dhs[si + 1]);
+    if (rc) return rc;
   }
   // every K-row weight gradient of the step, in one launch pair; then the
   // fused heads' gradients go to the flat buffer
-  rc = flush_wgrads(c, sv);
+  rc = flush_wgrads(c, gr.wgrad_part);
   if (rc) return rc;
-  if (!c.dry && K > 0 && !t.groups.empty()) {
+  if (K > 0 && !t.groups.empty()) {
     rc = pgnn_pack_fc_many(t.images + t.off_jobs_u, t.n_jobs_u, t.total_blocks_u,
                            c.stream);
     if (rc) return rc;
   }
-  if (!c.dry) PGNN_HIP(hipGetLastError());
+  PGNN_HIP(hipGetLastError());
   return 0;
 }
 
@@ -1546,6 +1276,7 @@ extern "C" int pgnn_trainer_create(const pgnn_train_model *m, void **handle) {
   }
   if (!plan_head_groups(*t)) t->groups.clear();  // heads one by one
   t->images_bytes = layout_images(*t);
+  t->shape = shape_of(*t);
   *handle = t;
   return 0;
   PGNN_GUARD_END
@@ -1740,17 +1471,37 @@ extern "C" int pgnn_trainer_repack(void *handle, void *stream_) {
   PGNN_GUARD_END
 }
 
+namespace {
+// Both layouts of a step over `workspace`, which must hold them (need: sizing
+// only, *need = the bytes).  The forward lays the backward's buffers out too:
+// the size check covers the whole step, as the sizing query's answer does.
+int lay_out(const Trainer *t, const pgnn_train_batch *batch, void *workspace,
+            size_t workspace_bytes, Saved &sv, Grads &gr, const char *who,
+            size_t *need = nullptr) {
+  PGNN_REQUIRE(t && (need || (t->images && workspace)), PGNN_E_INVALID,
+               (std::string(who) + ": null argument / not bound").c_str());
+  const int rc = check_batch(*t, batch);
+  if (rc) return rc;
+  Bump ws(workspace, workspace_bytes);
+  memset(&sv, 0, sizeof sv);
+  memset(&gr, 0, sizeof gr);
+  PGNN_REQUIRE(layout_forward(t->shape, *batch, scratch_need(*t, *batch), ws, sv),
+               PGNN_E_UNSUPPORTED, "trainer: too many head groups");
+  layout_backward(t->shape, *batch, wgrad_many_bound(), ws, sv, gr);
+  if (need) *need = ws.high + 4096;
+  PGNN_REQUIRE(need || workspace_bytes >= ws.high + 4096, PGNN_E_WORKSPACE,
+               (std::string(who) + ": workspace too small").c_str());
+  return 0;
+}
+}  // namespace
+
 extern "C" size_t pgnn_trainer_workspace_bytes(void *handle,
                                                const pgnn_train_batch *batch) {
-  Trainer *t = (Trainer *)handle;
-  if (!t || !batch || check_batch(*t, batch)) return 0;
-  Bump ws(nullptr, 0);
   Saved sv;
-  memset(&sv, 0, sizeof sv);
-  Ctx c{*t, *batch, ws, nullptr, true};
-  if (forward_impl(c, sv)) return 0;
-  if (backward_impl(c, sv, nullptr, nullptr)) return 0;
-  return ws.high + 4096;
+  Grads gr;
+  size_t need = 0;
+  if (!handle || !batch) return 0;  // (without a last-error text)
+  return lay_out((Trainer *)handle, batch, nullptr, 0, sv, gr, "", &need) ? 0 : need;
 }
 
 extern "C" int pgnn_trainer_forward(void *handle, const pgnn_train_batch *batch,
@@ -1759,18 +1510,15 @@ extern "C" int pgnn_trainer_forward(void *handle, const pgnn_train_batch *batch,
                                     const float **pred_box, void *stream_) {
   PGNN_GUARD_BEGIN
   Trainer *t = (Trainer *)handle;
-  PGNN_REQUIRE(t && t->images && workspace && logits && ld_logits && pred_box,
-               PGNN_E_INVALID, "trainer_forward: null argument / not bound");
-  int rc = check_batch(*t, batch);
-  if (rc) return rc;
-  PGNN_REQUIRE(workspace_bytes >= pgnn_trainer_workspace_bytes(handle, batch),
-               PGNN_E_WORKSPACE, "trainer_forward: workspace too small");
-  Bump ws(workspace, workspace_bytes);
+  PGNN_REQUIRE(logits && ld_logits && pred_box, PGNN_E_INVALID,
+               "trainer_forward: null argument / not bound");
   Saved sv;
-  memset(&sv, 0, sizeof sv);
+  Grads gr;
+  int rc = lay_out(t, batch, workspace, workspace_bytes, sv, gr, "trainer_forward");
+  if (rc) return rc;
   t->h1 = g_train_h1 ? 1 : 0;
-  Ctx c{*t, *batch, ws, (hipStream_t)stream_, false};
-  rc = forward_impl(c, sv);
+  Ctx c{*t, *batch, (hipStream_t)stream_, sv};
+  rc = forward_impl(c);
   if (rc) return rc;
   *logits = sv.heads.logits;
   *ld_logits = pad16(t->m.num_classes);
@@ -1785,21 +1533,15 @@ extern "C" int pgnn_trainer_backward(void *handle, const pgnn_train_batch *batch
                                      void *stream_) {
   PGNN_GUARD_BEGIN
   Trainer *t = (Trainer *)handle;
-  PGNN_REQUIRE(t && t->images && workspace && dlogits && dpred_box,
-               PGNN_E_INVALID, "trainer_backward: null argument / not bound");
-  int rc = check_batch(*t, batch);
-  if (rc) return rc;
-  PGNN_REQUIRE(workspace_bytes >= pgnn_trainer_workspace_bytes(handle, batch),
-               PGNN_E_WORKSPACE, "trainer_backward: workspace too small");
-  // re-derive the forward's pointers by replaying its allocation sequence
-  Bump ws(workspace, workspace_bytes);
+  PGNN_REQUIRE(dlogits && dpred_box, PGNN_E_INVALID,
+               "trainer_backward: null argument / not bound");
   Saved sv;
-  memset(&sv, 0, sizeof sv);
-  Ctx dryc{*t, *batch, ws, nullptr, true};
-  rc = forward_impl(dryc, sv);
+  Grads gr;
+  const int rc =
+      lay_out(t, batch, workspace, workspace_bytes, sv, gr, "trainer_backward");
   if (rc) return rc;
-  Ctx c{*t, *batch, ws, (hipStream_t)stream_, false};
-  return backward_impl(c, sv, dlogits, dpred_box);
+  Ctx c{*t, *batch, (hipStream_t)stream_, sv};
+  return backward_impl(c, gr, dlogits, dpred_box);
   PGNN_GUARD_END
 }
 

@@ -1359,6 +1359,48 @@ def test_native_sparse_and_dense_steps_give_the_same_gradient(dev, name,
                 mode, n, np.abs(a - b).max(), scale)
 
 
+def test_native_step_above_the_row_chain_limit(dev):
+    """More vertex rows than the one-launch chain kernel of the per-vertex
+    MLPs takes (mlp_rows_chain: 32 rows per CU): the native step then runs
+    those layers, forward and backward, one launch each.  24 merged frames of
+    graph_tiny.npz (K = 8 448 on 256 CUs) through the native and the
+    Python-driven step: same forward arithmetic, so the losses are equal, and
+    the gradients agree to float32 summation order -- the bar of
+    test_native_sparse_and_dense_steps_give_the_same_gradient, 2e-5 of a
+    variable's scale, which leaves room for the 24 times longer sums (random
+    rounding grows with the square root of their length: about 5 times the
+    ~1e-6 seen at one frame)."""
+    import torch
+    from pointgnn_amd import train
+    cfg = configs.car_auto_config(3)
+    params = weights.init_params(cfg, seed=5, bias_scale=0.1)
+    frames = []
+    for seed in range(24):
+        b = _tiny_batch(seed=seed)
+        f = lambda a: T(a, dev)
+        frames.append((f(b[0]), [f(c) for c in b[1]], [f(k) for k in b[2]],
+                       [f(e) for e in b[3]], f(b[4]), f(b[5]), f(b[6])))
+    batch = train.batch_data(frames)
+    k = int(batch[1][-1].shape[0])
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    assert k > 32 * cus, (k, cus)
+    grads, losses = {}, {}
+    for mode, native in (("native", True), ("python", False)):
+        tr = train.Trainer(cfg, params=params, device=dev)
+        tr.native = native
+        out = tr.train_step(batch, apply=False)
+        assert (tr._native is not None) == native
+        grads[mode] = tr.grad_dict()
+        losses[mode] = (out['cls_loss'], out['loc_loss'])
+    assert losses["native"] == losses["python"]
+    for n in grads["python"]:
+        a = grads["native"][n].astype(np.float64)
+        b = grads["python"][n].astype(np.float64)
+        scale = max(np.abs(b).max(), 1e-12)
+        assert np.abs(a - b).max() <= 2e-5 * scale + 1e-9, (
+            n, np.abs(a - b).max(), scale)
+
+
 def test_native_step_updates_like_the_python_step(dev):
     """Three SGD steps (apply=True: repack after every update) native vs
     Python-driven: the weights stay within float32 summation order of each

@@ -773,3 +773,220 @@ def test_ws_partition_header_on_every_geometry(tmp_path):
     cost = (ctypes.c_double * 4)(*[models[2](s) for s in (5, 5, 5, 4)])
     lib.t_balance(ctypes.byref(g), 256, cost, 0)
     assert g.balanced == 1 and list(g.n_wg) == [66, 66, 66, 58]
+
+
+# ---- the native trainer's workspace layout (csrc/trainer_layout.h), host only ---
+_LAYOUT_WRAPPERS = r"""
+#include <string.h>
+#include "trainer_layout.h"
+using namespace pgnn;
+extern "C" {
+int t_sizeof_shape() { return (int)sizeof(TrainerShape); }
+// Both layouts of a two-level batch (N, K, E0, E1) over `base` (null: sizing).
+// Returns the number of spans (all of them in out[] when <= cap), -1 when
+// layout_forward refuses.  info: spans and high-water mark of the forward, the
+// final high-water mark, then the offsets of scratch, logits, pred, dhs[0], dq
+// of the last stage and the weight-gradient partial slice.
+int t_layout(const TrainerShape *sh, const int64_t *nkee, size_t scratch,
+             size_t wgrad, char *base, BumpSpan *out, int cap, size_t *info) {
+  pgnn_train_batch b;
+  memset(&b, 0, sizeof b);
+  b.n_levels = 2;
+  b.n_feat = 1;
+  b.n_vertices[0] = nkee[0];
+  b.n_vertices[1] = b.n_vertices[2] = nkee[1];
+  b.n_edges[0] = nkee[2];
+  b.n_edges[1] = nkee[3];
+  std::vector<BumpSpan> log;
+  Bump ws(base, (size_t)1 << 40, &log);
+  Saved sv;
+  Grads gr;
+  memset(&sv, 0, sizeof sv);
+  memset(&gr, 0, sizeof gr);
+  if (!layout_forward(*sh, b, scratch, ws, sv)) return -1;
+  info[0] = log.size();
+  info[1] = ws.high;
+  layout_backward(*sh, b, wgrad, ws, sv, gr);
+  info[2] = ws.high;
+  const char *zero = base ? base : (const char *)256;  // (sizing: offset + 256)
+  const void *named[6] = {sv.scratch, sv.heads.logits, sv.heads.pred, gr.dhs[0],
+                          gr.stage[sh->n_stages - 1].dq, gr.wgrad_part};
+  for (int i = 0; i < 6; ++i) info[3 + i] = (size_t)((const char *)named[i] - zero);
+  for (size_t i = 0; i < log.size() && (int)i < cap; ++i) out[i] = log[i];
+  return (int)log.size();
+}
+}
+"""
+
+
+class _FcShape(ctypes.Structure):
+    _fields_ = [("k_in", ctypes.c_int), ("n_out", ctypes.c_int)]
+
+
+class _StageShape(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("level", ctypes.c_int),
+                ("n_a", ctypes.c_int), ("n_b", ctypes.c_int),
+                ("n_c", ctypes.c_int), ("a", _FcShape * 8), ("b", _FcShape * 8),
+                ("c", _FcShape * 8), ("want_wt", ctypes.c_bool)]
+
+
+class _TrainerShape(ctypes.Structure):
+    _fields_ = [("n_stages", ctypes.c_int), ("stages", _StageShape * 8),
+                ("n_groups", ctypes.c_int), ("group_w", (ctypes.c_int * 3) * 4),
+                ("cls_w", ctypes.c_int), ("loc_w", (ctypes.c_int * 3) * 16),
+                ("num_classes", ctypes.c_int), ("box_len", ctypes.c_int)]
+
+
+class _BumpSpan(ctypes.Structure):
+    _fields_ = [("off", ctypes.c_size_t), ("bytes", ctypes.c_size_t),
+                ("released", ctypes.c_int)]
+
+
+@pytest.fixture(scope="module")
+def trainer_layout_lib(tmp_path_factory):
+    """csrc/trainer_layout.h alone through the host C++ compiler, as
+    _ws_partition_lib builds its header: it must not need HIP."""
+    import shutil
+    import subprocess
+    tmp = tmp_path_factory.mktemp("trainer_layout")
+    cands = [shutil.which("g++")]
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(hipcc)))
+    cands += [os.path.join(rocm, "lib", "llvm", "bin", "clang++"),
+              os.path.join(rocm, "llvm", "bin", "clang++")]
+    cxx = next((c for c in cands if c and os.path.exists(c)), None)
+    assert cxx, "no host C++ compiler (g++ or ROCm's clang++) found"
+    src = tmp / "trainer_layout_test.cpp"
+    src.write_text(_LAYOUT_WRAPPERS)
+    so = tmp / "libtrainer_layout_test.so"
+    subprocess.check_call([cxx, "-O1", "-std=c++17", "-Wall", "-shared", "-fPIC",
+                           "-I", os.path.join(ROOT, "point-gnn_amd", "csrc"),
+                           "-I", os.path.join(ROOT, "include"),
+                           "-o", str(so), str(src)])
+    lib = ctypes.CDLL(str(so))
+    assert lib.t_sizeof_shape() == ctypes.sizeof(_TrainerShape)
+    lib.t_layout.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                             ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                             ctypes.c_int, ctypes.c_void_p]
+    return lib
+
+
+def _trainer_shape(point_mlp, out_mlp, width, offset_mlp, T, num_classes,
+                   fused, sparse):
+    """The shape of a shipped model as pgnn_trainer_create derives it: n_feat =
+    1, box_len = 7, heads C -> 64 -> nc and C -> 64 -> 64 -> 7, fused into
+    groups of at most 320 columns the way plan_head_groups does."""
+    def chain(dst, k_in, widths):
+        for i, n_out in enumerate(widths):
+            dst[i].k_in, dst[i].n_out = k_in, n_out
+            k_in = n_out
+        return len(widths)
+    sh = _TrainerShape()
+    sh.n_stages = 1 + T
+    s = sh.stages[0]
+    s.kind, s.level = 0, 0
+    s.n_a = chain(s.a, 1 + 3, point_mlp)
+    s.n_b = chain(s.b, point_mlp[-1], out_mlp)
+    s.want_wt = sparse
+    for i in range(T):
+        s = sh.stages[1 + i]
+        s.kind, s.level = 1, 1
+        s.n_a = chain(s.a, width + 3, [width, width])
+        s.n_b = chain(s.b, width, [width, width])
+        s.n_c = chain(s.c, width, offset_mlp)
+        s.want_wt = sparse
+    sh.num_classes, sh.box_len = num_classes, 7
+    hw = 64
+    if fused:
+        lids, first = num_classes, True
+        while first or lids:
+            take = min(lids, 320 // hw - (1 if first else 0))
+            base = 16 if first else 0
+            g = sh.group_w[sh.n_groups]
+            g[0] = hw * (take + (1 if first else 0))
+            g[1] = base + hw * take
+            g[2] = base + 8 * take
+            sh.n_groups += 1
+            lids -= take
+            first = False
+    else:
+        sh.cls_w = hw
+        for j in range(num_classes):
+            sh.loc_w[j][0], sh.loc_w[j][1], sh.loc_w[j][2] = hw, hw, 7
+    return sh
+
+
+_LAYOUT_MODELS = {
+    "car_auto_T3": ([32, 64, 128, 300], [300, 300], 300, [64, 3], 3, 4),
+    "car_auto_T1": ([32, 64, 128, 300], [300, 300], 300, [64, 3], 1, 4),
+    "car_fixed_T3": ([32, 64, 128, 300], [300, 300], 300, [], 3, 4),
+    "ped_cyl_auto_T3": ([32, 64, 128, 256, 512], [256, 256], 256, [64, 3], 3, 6),
+}
+_LAYOUT_BATCHES = [(0, 0, 0, 0), (5, 1, 5, 0), (40, 7, 33, 12),
+                   (1000, 300, 4000, 9000), (20000, 3352, 347456, 674852)]
+
+
+@pytest.mark.parametrize("sparse", [True, False], ids=["sparse", "dense"])
+@pytest.mark.parametrize("fused", [True, False], ids=["fused", "separate"])
+@pytest.mark.parametrize("model", sorted(_LAYOUT_MODELS))
+def test_trainer_layout_buffers_are_aligned_disjoint_and_repeatable(
+        trainer_layout_lib, model, fused, sparse):
+    """csrc/trainer_layout.h is the one statement of where the native training
+    step keeps its buffers (the sizing query, the forward and the backward all
+    call it).  For the shipped models, fused and separate heads, the sparse
+    and the dense last per-edge layer, from an empty batch to a full-size car
+    frame: every buffer starts on a 256-byte boundary and ends below the
+    high-water mark; buffers that are live together do not overlap (only a
+    backward stage's E-row temporaries are ever released, with their stage);
+    the backward's buffers lie behind everything the forward keeps; and a
+    second layout, over a base address instead of the sizing run's null,
+    gives the same offsets."""
+    lib = trainer_layout_lib
+    sh = _trainer_shape(*_LAYOUT_MODELS[model], fused, sparse)
+    assert sh.n_groups == (0 if not fused else 1 if sh.num_classes == 4 else 2)
+    scratch, wgrad = 1 << 20, 64 << 20
+    # E-row temporaries: ge / ga per layer below the last (not for a two-layer
+    # GNN stage's sparse adjoint, which writes dP / dQ), gz and ties when dense
+    n_temp = sum((0 if s.kind == 1 and sparse and s.n_a == 2 else s.n_a - 1) +
+                 (0 if sparse else 2)
+                 for s in list(sh.stages)[:sh.n_stages])
+    for sizes in _LAYOUT_BATCHES:
+        nkee = (ctypes.c_int64 * 4)(*sizes)
+        runs = []
+        for base in (None, 1 << 32):
+            spans = (_BumpSpan * 512)()
+            info = (ctypes.c_size_t * 9)()
+            n = lib.t_layout(ctypes.byref(sh), nkee, scratch, wgrad, base, spans,
+                             512, info)
+            assert 0 < n <= 512
+            runs.append(([(s.off, s.bytes, s.released) for s in spans[:n]],
+                         list(info)))
+        assert runs[0] == runs[1], sizes
+        spans, (n_fwd, fwd_high, high, *named) = runs[0]
+        assert 0 < n_fwd < len(spans) and fwd_high <= high
+        for i, (off, nbytes, released) in enumerate(spans):
+            assert off % 256 == 0 and off + nbytes <= high, (sizes, i)
+            if i >= n_fwd:
+                assert off >= fwd_high, (sizes, i)
+            if released >= 0:      # given back once span `released` is made
+                assert n_fwd <= i < released <= len(spans), (sizes, i)
+            for j in range(i + 1, len(spans)):
+                if released < 0 or j < released:      # i is live when j is made
+                    o2, b2, _ = spans[j]
+                    assert off + nbytes <= o2 or o2 + b2 <= off, (sizes, i, j)
+        assert sum(1 for s in spans if s[2] >= 0) == n_temp, sizes
+        # the records point at the spans: the first and the last buffer of
+        # either direction and two in between
+        N, K, E0, E1 = sizes
+        at = {off: nbytes for off, nbytes, _ in spans if nbytes}
+        assert named[0] == 0 and spans[0] == (0, scratch, -1)
+        assert spans[-1] == (named[5], wgrad, -1)
+        assert spans[n_fwd - 1][0] == named[2]
+        assert spans[n_fwd][0] == named[3] >= fwd_high
+        if K:
+            assert at[named[1]] == K * 16 * 4               # logits [K, pad(nc)]
+            assert at[named[2]] == K * sh.num_classes * 7 * 4
+            width = _LAYOUT_MODELS[model][2]
+            wq = (width + 15) // 16 * 16
+            assert at[named[3]] == K * wq * 4               # dhs[0] [K, hw]
+            assert at[named[4] - K * wq * 4] == 2 * K * wq * 4   # dP | dQ
