@@ -1384,6 +1384,41 @@ int pgnn_points_in_box_f64(const double *xyz, int64_t n_points,
                            const double *box_record_24, const int32_t *exclude,
                            int32_t *inside, int32_t *count, void *stream);
 
+/* The union mask of remove_background / dilute_background
+ * (models/preprocess.py:420-421, :359-360: `mask += sel_xyz_in_box3d(...)` over
+ * the selected labels).  box_records is a DEVICE array of n_boxes records of 24
+ * doubles (layout and strict predicate of pgnn_points_in_box_f64; `action` is
+ * not looked at).  inside[i] (nullable) = 1 when point i is strictly inside any
+ * of the boxes and exclude[i] == 0 (exclude nullable; with one record it gives
+ * the `new_mask & ~mask` of random_box_global_rotation, :211-213), else 0;
+ * *count (nullable, device) = the number of such points.  n_boxes == 0: all
+ * zeros.  n_points == 0: *count = 0, nothing else.  No host synchronisation. */
+int pgnn_points_in_boxes_f64(const double *xyz, int64_t n_points,
+                             const double *box_records, int32_t n_boxes,
+                             const int32_t *exclude, int32_t *inside,
+                             int32_t *count, void *stream);
+
+/* Order-preserving compaction of the float64 cloud and its attributes: the
+ * `xyz[mask]` / `attr[mask]` of random_drop (models/preprocess.py:27),
+ * random_box_global_rotation (:220-221), remove_background (:427-428) and
+ * dilute_background (:367-371).  Point i is kept when
+ *   (keep == NULL || keep[i] != 0) && (drop == NULL || drop[i] == 0)
+ * (int32 device masks).  attr is float32 [n_points, attr_dim] with attr_dim in
+ * 0..4, or NULL (then out_attr is not touched).  The kept rows go, in their
+ * original order, to out_xyz [capacity,3] / out_attr [capacity,attr_dim];
+ * *out_count (device) = the number of kept points also when that exceeds
+ * `capacity`, and nothing is written past `capacity` rows.  n_points == 0:
+ * *out_count = 0.  n_points < 2^31.  Two launches around an exclusive scan of
+ * the per-block counts (the shape of pgnn_kitti_cam_points_in_image); no host
+ * synchronisation.  Workspace: pgnn_points_compact_workspace_bytes(n_points). */
+size_t pgnn_points_compact_workspace_bytes(int64_t n_points);
+int pgnn_points_compact_f64(const double *xyz, const float *attr,
+                            int32_t attr_dim, int64_t n_points,
+                            const int32_t *keep, const int32_t *drop,
+                            void *workspace, size_t workspace_bytes,
+                            double *out_xyz, float *out_attr, int64_t capacity,
+                            int32_t *out_count, void *stream);
+
 /* Streaming classification metrics of the training / evaluation loops
  * (train.py:301-368, eval.py:176-245): per class tf.metrics.recall and
  * tf.metrics.precision of argmax(probs) against the labels, and

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include "pgnn_common.h"
+#include "sort.h"
 
 namespace pgnn {
 namespace {
@@ -167,10 +168,191 @@ __global__ void points_in_box_f64_kernel(const double *__restrict__ xyz,
   }
 }
 
+// inside[i] = point i lies strictly inside ANY of the n_rec box records and
+// exclude[i] == 0 (the union masks of remove_background / dilute_background,
+// preprocess.py:359-360, :420-421; with one record and `exclude` the
+// `new_mask & ~mask` of random_box_global_rotation, :211-213); *count += the
+// number of such points.  Same predicate, in the same operation order, as
+// points_in_box_f64_kernel.
+__global__ void points_in_boxes_f64_kernel(const double *__restrict__ xyz,
+                                           int64_t n,
+                                           const LabelRecord *__restrict__ rec,
+                                           int n_rec,
+                                           const int32_t *__restrict__ exclude,
+                                           int32_t *__restrict__ inside,
+                                           int32_t *__restrict__ count) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool any = false;
+  if (i < n) {
+    const double x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+    for (int r = 0; r < n_rec && !any; ++r) {
+      const LabelRecord &b = rec[r];
+      bool in = true;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double p = (x * b.normals[3 * k] + y * b.normals[3 * k + 1]) +
+                         z * b.normals[3 * k + 2];
+        in = in && p > b.lower[k] && p < b.upper[k];
+      }
+      any = in;
+    }
+    if (exclude && exclude[i] != 0) any = false;
+    if (inside) inside[i] = any ? 1 : 0;
+  }
+  if (count) {
+    const unsigned long long bal = __ballot(any);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(count, (int)__popcll(bal));
+  }
+}
+
+// ---- order-preserving compaction of the cloud ------------------------------
+// xyz[mask] / attr[mask] of random_drop (:27), random_box_global_rotation
+// (:220-221), remove_background (:427-428) and dilute_background (:367-371):
+// count per block, exclusive scan of the block counts, write -- the shape of
+// ingest.hip.  Within a block the rank of a kept point is the popcount of the
+// wave's ballot below its lane plus the totals of the waves before it.
+constexpr int kCompactBlock = 256;
+
+__device__ __forceinline__ bool compact_kept(const int32_t *__restrict__ keep,
+                                             const int32_t *__restrict__ drop,
+                                             int64_t i, int64_t n) {
+  return i < n && (!keep || keep[i] != 0) && !(drop && drop[i] != 0);
+}
+
+__global__ __launch_bounds__(kCompactBlock) void compact_count_kernel(
+    const int32_t *__restrict__ keep, const int32_t *__restrict__ drop,
+    int64_t n, int32_t *__restrict__ block_count) {
+  const int64_t i = (int64_t)blockIdx.x * kCompactBlock + threadIdx.x;
+  const bool kept = compact_kept(keep, drop, i, n);
+  __shared__ int wave_tot[kCompactBlock / 64];
+  const unsigned long long bal = __ballot(kept);
+  if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = __popcll(bal);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t = 0;
+    for (int w = 0; w < kCompactBlock / 64; ++w) t += wave_tot[w];
+    block_count[blockIdx.x] = t;
+  }
+}
+
+__global__ __launch_bounds__(kCompactBlock) void compact_write_kernel(
+    const double *__restrict__ xyz, const float *__restrict__ attr,
+    int attr_dim, const int32_t *__restrict__ keep,
+    const int32_t *__restrict__ drop, int64_t n,
+    const int32_t *__restrict__ block_offset, double *__restrict__ out_xyz,
+    float *__restrict__ out_attr, int64_t capacity,
+    int32_t *__restrict__ out_count, int n_blocks) {
+  const int64_t i = (int64_t)blockIdx.x * kCompactBlock + threadIdx.x;
+  const bool kept = compact_kept(keep, drop, i, n);
+  __shared__ int wave_tot[kCompactBlock / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long bal = __ballot(kept);
+  if (lane == 0) wave_tot[wave] = __popcll(bal);
+  __syncthreads();
+  int64_t slot = block_offset[blockIdx.x];
+  for (int w = 0; w < wave; ++w) slot += wave_tot[w];
+  slot += __popcll(bal & ((1ull << lane) - 1ull));
+  if (kept && slot < capacity) {
+    out_xyz[3 * slot] = xyz[3 * i];
+    out_xyz[3 * slot + 1] = xyz[3 * i + 1];
+    out_xyz[3 * slot + 2] = xyz[3 * i + 2];
+    for (int k = 0; k < attr_dim; ++k)
+      out_attr[slot * attr_dim + k] = attr[i * attr_dim + k];
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) *out_count = block_offset[n_blocks];
+}
+
+// workspace: [block counts | block offsets (+ total) | scan scratch]
+struct CompactLayout {
+  int32_t *counts, *offsets;
+  void *scan_ws;
+  size_t scan_bytes;
+};
+
+bool carve_compact(Arena &ar, int64_t n_points, CompactLayout *L) {
+  const size_t nb =
+      (size_t)((n_points + kCompactBlock - 1) / kCompactBlock) + 2;
+  L->scan_bytes = scan_scratch_bytes((int64_t)nb);
+  L->counts = ar.take<int32_t>(nb);
+  L->offsets = ar.take<int32_t>(nb + 1);
+  L->scan_ws = ar.take<char>(L->scan_bytes > 0 ? L->scan_bytes : 1);
+  return L->counts && L->offsets && L->scan_ws;
+}
+
 }  // namespace
 }  // namespace pgnn
 
 using namespace pgnn;
+
+extern "C" size_t pgnn_points_compact_workspace_bytes(int64_t n_points) {
+  if (n_points < 0) return 0;
+  Arena ar(nullptr, 0);
+  CompactLayout L;
+  carve_compact(ar, n_points, &L);
+  return align_up(ar.used, 256);
+}
+
+extern "C" int pgnn_points_compact_f64(
+    const double *xyz, const float *attr, int32_t attr_dim, int64_t n_points,
+    const int32_t *keep, const int32_t *drop, void *workspace,
+    size_t workspace_bytes, double *out_xyz, float *out_attr, int64_t capacity,
+    int32_t *out_count, void *stream_) {
+  PGNN_GUARD_BEGIN
+  hipStream_t stream = (hipStream_t)stream_;
+  PGNN_REQUIRE(n_points >= 0 && n_points <= 0x7fffffffll && capacity >= 0 &&
+                   out_count && attr_dim >= 0 && attr_dim <= 4,
+               PGNN_E_INVALID, "points_compact: bad argument");
+  if (n_points == 0) {
+    PGNN_HIP(hipMemsetAsync(out_count, 0, 4, stream));
+    return 0;
+  }
+  if (!attr) attr_dim = 0;
+  PGNN_REQUIRE(xyz && (capacity == 0 || (out_xyz && (attr_dim == 0 || out_attr))),
+               PGNN_E_INVALID, "points_compact: null pointer");
+  const int64_t nb = (n_points + kCompactBlock - 1) / kCompactBlock;
+  Arena ar(workspace, workspace_bytes);
+  CompactLayout L;
+  PGNN_REQUIRE(carve_compact(ar, n_points, &L), PGNN_E_WORKSPACE,
+               "points_compact: workspace too small "
+               "(see pgnn_points_compact_workspace_bytes)");
+  hipLaunchKernelGGL(compact_count_kernel, dim3((unsigned)nb),
+                     dim3(kCompactBlock), 0, stream, keep, drop, n_points,
+                     L.counts);
+  PGNN_HIP(hipGetLastError());
+  int rc = exclusive_scan_i32(L.counts, L.offsets, nb, L.scan_ws, L.scan_bytes,
+                              stream);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(compact_write_kernel, dim3((unsigned)nb),
+                     dim3(kCompactBlock), 0, stream, xyz, attr, (int)attr_dim,
+                     keep, drop, n_points, L.offsets, out_xyz, out_attr,
+                     capacity, out_count, (int)nb);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_points_in_boxes_f64(const double *xyz, int64_t n_points,
+                                        const double *box_records,
+                                        int32_t n_boxes, const int32_t *exclude,
+                                        int32_t *inside, int32_t *count,
+                                        void *stream_) {
+  PGNN_GUARD_BEGIN
+  hipStream_t stream = (hipStream_t)stream_;
+  PGNN_REQUIRE(n_points >= 0 && n_boxes >= 0, PGNN_E_INVALID,
+               "points_in_boxes: bad size");
+  if (count) PGNN_HIP(hipMemsetAsync(count, 0, 4, stream));
+  if (n_points == 0) return 0;
+  PGNN_REQUIRE(xyz && (box_records || n_boxes == 0), PGNN_E_INVALID,
+               "points_in_boxes: null pointer");
+  hipLaunchKernelGGL(points_in_boxes_f64_kernel,
+                     dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0,
+                     stream, xyz, n_points,
+                     reinterpret_cast<const LabelRecord *>(box_records),
+                     (int)n_boxes, exclude, inside, count);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+  PGNN_GUARD_END
+}
 
 extern "C" int pgnn_points_affine_f64(double *xyz, int64_t n_points,
                                       const double *rot_3x3,

@@ -290,6 +290,11 @@ def fetch_data(dataset, frame_idx, config, train_config, aug_fn=None,
         aug_fn = preprocess.get_data_aug(
             train_config.get('data_aug_configs', []))
     points, labels = aug_fn(points, labels)
+    if points.attr is not None and \
+            int(points.attr.shape[0]) != int(points.xyz.shape[0]):
+        # augmentations that remove points take the attributes along
+        raise ValueError("augmented cloud has %d points but %d attribute rows"
+                         % (points.xyz.shape[0], points.attr.shape[0]))
     if graph_hints is not None and isinstance(points.xyz, torch.Tensor) and \
             config['graph_gen_method'] == 'multi_level_local_graph_v3':
         coords, kps, edges = graph_gen.gen_multi_level_local_graph_v3_one_read(
