@@ -1110,6 +1110,25 @@ int pgnn_optimizer_step(int32_t kind, float *params, const float *grads,
 /* *out (device double) = sum |params| over is_weight entries (reg_loss/scale). */
 int pgnn_l1_norm(const float *params, const float *is_weight, int64_t n,
                  double *out, void *stream);
+/* The other weight regularizers of models.py:11-15 (tf.contrib.layers):
+ * l2_regularizer(scale) = scale * sum(w^2) / 2 (tf.nn.l2_loss),
+ * l1_l2_regularizer(scale_l1, scale_l2) = the sum of the two; FC weights only
+ * (models.py:114-115).  The two entries above with the gradient
+ *   grad_scale*grads + (l1_scale*sign(params) + l2_scale*params)*is_weight;
+ * l2_scale = 0 is exactly pgnn_sgd_step / pgnn_optimizer_step (they forward
+ * here).                                                                      */
+int pgnn_sgd_step_l1l2(float *params, const float *grads, const float *is_weight,
+                       int64_t n, float lr, float grad_scale, float l1_scale,
+                       float l2_scale, void *stream);
+int pgnn_optimizer_step_l1l2(int32_t kind, float *params, const float *grads,
+                             const float *is_weight, float *slot0, float *slot1,
+                             int64_t n, float lr, float grad_scale,
+                             float l1_scale, float l2_scale, float h0, float h1,
+                             float h2, void *stream);
+/* out2 (device double[2]) = {sum |params|, sum params^2} over is_weight entries:
+ * reg_loss = l1_scale * out2[0] + l2_scale * out2[1] / 2.                     */
+int pgnn_weight_norms(const float *params, const float *is_weight, int64_t n,
+                      double *out2, void *stream);
 
 /* ---- native training step (config 4) ----------------------------------------
  * What train.py builds with TF towers -- model.predict with saved
@@ -1146,8 +1165,14 @@ typedef struct pgnn_train_model {
   int32_t n_stages, num_classes, box_len, reserved;
   int64_t n_params;
   pgnn_train_stage stages[PGNN_TRAIN_MAX_STAGES];
-  pgnn_train_fc cls[2];                          /* C -> 64 -> nc (gnn.py:145-152)  */
-  pgnn_train_fc loc[PGNN_TRAIN_MAX_CLASSES][3];  /* per class C -> 64 -> 64 -> L   */
+  pgnn_train_fc cls[2];                          /* C -> hw -> nc (gnn.py:145-152)  */
+  pgnn_train_fc loc[PGNN_TRAIN_MAX_CLASSES][3];  /* per class C -> hw -> hw -> L   */
+  /* which columns of the C-wide features box head j reads: 0 = all of them
+   * (ClassAwarePredictor, gnn.py:133-163; what a zero-initialised model
+   * means), 1 = its own slice [j*s, (j+1)*s), s = C / num_classes, so that
+   * loc[j][0].k_in = s (ClassAwareSeparatedPredictor, gnn.py:178-213: tf.split).
+   * The class head reads all C columns either way.                            */
+  int32_t loc_split, reserved2;
 } pgnn_train_model;
 typedef struct pgnn_train_batch { /* device pointers; what train.py's batch_data
                                      returns for this rank (train.py:135-171) */

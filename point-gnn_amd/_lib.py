@@ -87,7 +87,10 @@ class TrainModel(ctypes.Structure):
                 ("box_len", c_i32), ("reserved", c_i32), ("n_params", c_i64),
                 ("stages", TrainStage * TRAIN_MAX_STAGES),
                 ("cls", TrainFc * 2),
-                ("loc", (TrainFc * 3) * TRAIN_MAX_CLASSES)]
+                ("loc", (TrainFc * 3) * TRAIN_MAX_CLASSES),
+                # 0: every box head reads all feature columns; 1: head j reads
+                # its slice [j*s, (j+1)*s), s = C / num_classes
+                ("loc_split", c_i32), ("reserved2", c_i32)]
 
 
 class TrainBatch(ctypes.Structure):
@@ -415,6 +418,11 @@ _SIGNATURES = {
     "pgnn_optimizer_step": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64] +
                             [ctypes.c_float] * 6 + [c_vp]),
     "pgnn_l1_norm": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "pgnn_sgd_step_l1l2": (c_i32, [c_vp, c_vp, c_vp, c_i64] +
+                           [ctypes.c_float] * 4 + [c_vp]),
+    "pgnn_optimizer_step_l1l2": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                         c_i64] + [ctypes.c_float] * 7 + [c_vp]),
+    "pgnn_weight_norms": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     # detection post-processing
     "pgnn_box_decode_f32": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64,
                                     c_i32, c_vp, c_vp]),

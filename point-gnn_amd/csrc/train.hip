@@ -1249,13 +1249,17 @@ __global__ void loss_kernel(const float *__restrict__ logits, int64_t ldl,
 
 __global__ void sgd_kernel(float *__restrict__ w, const float *__restrict__ g,
                            const float *__restrict__ is_weight, int64_t n,
-                           float lr, float grad_scale, float l1) {
+                           float lr, float grad_scale, float l1, float l2) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     const float wi = w[i];
     float gi = g[i] * grad_scale;
-    if (is_weight[i] != 0.0f)  // l1_regularizer: d|w| = sign(w) (0 at 0)
+    if (is_weight[i] != 0.0f) {  // l1_regularizer: d|w| = sign(w) (0 at 0)
       gi += l1 * (wi > 0.0f ? 1.0f : (wi < 0.0f ? -1.0f : 0.0f));
+      // l2_regularizer: d(w^2 / 2) = w (tf.nn.l2_loss); skipped, not added
+      // as 0 * w, when there is none: the l1 step keeps its bits
+      if (l2 != 0.0f) gi += l2 * wi;
+    }
     w[i] = wi - lr * gi;
   }
 }
@@ -1263,7 +1267,7 @@ __global__ void sgd_kernel(float *__restrict__ w, const float *__restrict__ g,
 // The other optimizers of train.py:380-391 on the flat parameter buffer, with
 // TF 1.x's update rules (training_ops.cc: ApplyMomentum without Nesterov,
 // ApplyRMSProp (not centered), ApplyAdam): the gradient is the one sgd_kernel
-// applies (scaled batch gradient + the L1 regulariser's sign term), the slot
+// applies (scaled batch gradient + the regulariser's l1 sign(w) + l2 w), the slot
 // buffers have the parameters' layout.
 //   kind 1 momentum: a = h0 a + g;                  w -= lr a
 //   kind 2 rmsprop : ms = h1 ms + (1 - h1) g^2;
@@ -1275,13 +1279,15 @@ __global__ void optimizer_kernel(int kind, float *__restrict__ w,
                                  const float *__restrict__ is_weight,
                                  float *__restrict__ s0, float *__restrict__ s1,
                                  int64_t n, float lr, float grad_scale, float l1,
-                                 float h0, float h1, float h2) {
+                                 float l2, float h0, float h1, float h2) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     const float wi = w[i];
     float gi = g[i] * grad_scale;
-    if (is_weight[i] != 0.0f)
+    if (is_weight[i] != 0.0f) {
       gi += l1 * (wi > 0.0f ? 1.0f : (wi < 0.0f ? -1.0f : 0.0f));
+      if (l2 != 0.0f) gi += l2 * wi;  // (as in sgd_kernel)
+    }
     if (kind == 1) {
       const float a = h0 * s0[i] + gi;
       s0[i] = a;
@@ -1321,6 +1327,37 @@ __global__ __launch_bounds__(1024) void l1_norm_kernel(
     double t = 0.0;
     for (int q = 0; q < (int)(blockDim.x >> 6); ++q) t += part[q];
     atomicAdd(out, t);
+  }
+}
+
+// out[0] += sum |w|, out[1] += sum w^2 over the weights (l1_norm_kernel's
+// reduction with a second accumulator: one atomic pair per workgroup)
+__global__ __launch_bounds__(1024) void weight_norms_kernel(
+    const float *__restrict__ w, const float *__restrict__ is_weight, int64_t n,
+    double *__restrict__ out) {
+  double s1 = 0.0, s2 = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    if (is_weight[i] != 0.0f) {
+      const double wi = (double)w[i];
+      s1 += fabs(wi);
+      s2 += wi * wi;
+    }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    s1 += __shfl_xor(s1, d);
+    s2 += __shfl_xor(s2, d);
+  }
+  __shared__ double part[2][16];
+  if ((threadIdx.x & 63) == 0) {
+    part[0][threadIdx.x >> 6] = s1;
+    part[1][threadIdx.x >> 6] = s2;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    double t = 0.0;
+    for (int q = 0; q < (int)(blockDim.x >> 6); ++q) t += part[threadIdx.x][q];
+    atomicAdd(out + threadIdx.x, t);
   }
 }
 
@@ -2668,16 +2705,45 @@ extern "C" int pgnn_topk_mask_f32(const float *values, int64_t n, int64_t k,
   PGNN_GUARD_END
 }
 
-extern "C" int pgnn_sgd_step(float *params, const float *grads,
-                             const float *is_weight, int64_t n, float lr,
-                             float grad_scale, float l1_scale, void *stream_) {
+extern "C" int pgnn_sgd_step_l1l2(float *params, const float *grads,
+                                  const float *is_weight, int64_t n, float lr,
+                                  float grad_scale, float l1_scale,
+                                  float l2_scale, void *stream_) {
   PGNN_GUARD_BEGIN
   if (n <= 0) return 0;
   PGNN_REQUIRE(params && grads && is_weight, PGNN_E_INVALID,
                "sgd_step: null pointer");
   hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n)), dim3(256), 0,
                      (hipStream_t)stream_, params, grads, is_weight, n, lr,
-                     grad_scale, l1_scale);
+                     grad_scale, l1_scale, l2_scale);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_sgd_step(float *params, const float *grads,
+                             const float *is_weight, int64_t n, float lr,
+                             float grad_scale, float l1_scale, void *stream_) {
+  return pgnn_sgd_step_l1l2(params, grads, is_weight, n, lr, grad_scale, l1_scale,
+                            0.0f, stream_);
+}
+
+extern "C" int pgnn_optimizer_step_l1l2(int32_t kind, float *params,
+                                        const float *grads,
+                                        const float *is_weight, float *slot0,
+                                        float *slot1, int64_t n, float lr,
+                                        float grad_scale, float l1_scale,
+                                        float l2_scale, float h0, float h1,
+                                        float h2, void *stream_) {
+  PGNN_GUARD_BEGIN
+  PGNN_REQUIRE(kind >= 1 && kind <= 3, PGNN_E_INVALID,
+               "optimizer_step: kind must be 1 (momentum), 2 (rmsprop) or 3 (adam)");
+  if (n <= 0) return 0;
+  PGNN_REQUIRE(params && grads && is_weight && slot0 && (kind == 1 || slot1),
+               PGNN_E_INVALID, "optimizer_step: null pointer");
+  hipLaunchKernelGGL(optimizer_kernel, dim3(grid_for(n)), dim3(256), 0,
+                     (hipStream_t)stream_, kind, params, grads, is_weight, slot0,
+                     slot1, n, lr, grad_scale, l1_scale, l2_scale, h0, h1, h2);
   PGNN_HIP(hipGetLastError());
   return 0;
   PGNN_GUARD_END
@@ -2688,18 +2754,9 @@ extern "C" int pgnn_optimizer_step(int32_t kind, float *params,
                                    float *slot0, float *slot1, int64_t n,
                                    float lr, float grad_scale, float l1_scale,
                                    float h0, float h1, float h2, void *stream_) {
-  PGNN_GUARD_BEGIN
-  PGNN_REQUIRE(kind >= 1 && kind <= 3, PGNN_E_INVALID,
-               "optimizer_step: kind must be 1 (momentum), 2 (rmsprop) or 3 (adam)");
-  if (n <= 0) return 0;
-  PGNN_REQUIRE(params && grads && is_weight && slot0 && (kind == 1 || slot1),
-               PGNN_E_INVALID, "optimizer_step: null pointer");
-  hipLaunchKernelGGL(optimizer_kernel, dim3(grid_for(n)), dim3(256), 0,
-                     (hipStream_t)stream_, kind, params, grads, is_weight, slot0,
-                     slot1, n, lr, grad_scale, l1_scale, h0, h1, h2);
-  PGNN_HIP(hipGetLastError());
-  return 0;
-  PGNN_GUARD_END
+  return pgnn_optimizer_step_l1l2(kind, params, grads, is_weight, slot0, slot1, n,
+                                  lr, grad_scale, l1_scale, 0.0f, h0, h1, h2,
+                                  stream_);
 }
 
 extern "C" int pgnn_l1_norm(const float *params, const float *is_weight,
@@ -2712,6 +2769,21 @@ extern "C" int pgnn_l1_norm(const float *params, const float *is_weight,
   PGNN_REQUIRE(params && is_weight, PGNN_E_INVALID, "l1_norm: null pointer");
   hipLaunchKernelGGL(l1_norm_kernel, dim3(grid_for((n + 3) / 4, 128)), dim3(1024),
                      0, stream, params, is_weight, n, out);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_weight_norms(const float *params, const float *is_weight,
+                                 int64_t n, double *out2, void *stream_) {
+  PGNN_GUARD_BEGIN
+  hipStream_t stream = (hipStream_t)stream_;
+  PGNN_REQUIRE(out2, PGNN_E_INVALID, "weight_norms: null out");
+  PGNN_HIP(hipMemsetAsync(out2, 0, 2 * sizeof(double), stream));
+  if (n <= 0) return 0;
+  PGNN_REQUIRE(params && is_weight, PGNN_E_INVALID, "weight_norms: null pointer");
+  hipLaunchKernelGGL(weight_norms_kernel, dim3(grid_for((n + 3) / 4, 128)),
+                     dim3(1024), 0, stream, params, is_weight, n, out2);
   PGNN_HIP(hipGetLastError());
   return 0;
   PGNN_GUARD_END

@@ -252,15 +252,21 @@ size_t packed_floats(int k_in, int n_out) {
 
 // groups of heads as the inference path forms them (gnn.py of the package,
 // ClassAwarePredictor): returns false when the heads do not have the shipped
-// shape (C -> hw -> nc and C -> hw -> hw -> L with one hw, L <= 8)
+// shape (C -> hw -> nc and C -> hw -> hw -> L with one hw, L <= 8).  With
+// loc_split the box heads' first layers are s = C / nc rows high instead of C:
+// in the fused first layer, still C rows high, head j's block sits in rows
+// [j s, (j + 1) s) and the rows around it stay zero (pgnn_trainer_bind), which
+// is the column split written as a matrix -- x W1 with zero rows reads none of
+// the other columns, and dX = dY W1^T gives them none of head j's gradient.
 bool plan_head_groups(Trainer &t) {
   const int nc = t.m.num_classes, L = t.m.box_len;
   const int C = t.cls[0].ref.k_in, hw = t.cls[0].ref.n_out;
+  const int c_loc = t.m.loc_split ? C / nc : C;
   if (L > 8 || nc > 16 || t.cls[1].ref.k_in != hw || t.cls[1].ref.n_out != nc)
     return false;
   for (int j = 0; j < nc; ++j) {
     const FcDev *f = &t.loc[3 * j];
-    if (f[0].ref.k_in != C || f[0].ref.n_out != hw || f[1].ref.k_in != hw ||
+    if (f[0].ref.k_in != c_loc || f[0].ref.n_out != hw || f[1].ref.k_in != hw ||
         f[1].ref.n_out != hw || f[2].ref.k_in != hw || f[2].ref.n_out != L)
       return false;
   }
@@ -1214,7 +1220,8 @@ extern "C" int pgnn_trainer_create(const pgnn_train_model *m, void **handle) {
   PGNN_REQUIRE(m->n_stages >= 1 && m->n_stages <= PGNN_TRAIN_MAX_STAGES &&
                    m->num_classes >= 1 &&
                    m->num_classes <= PGNN_TRAIN_MAX_CLASSES && m->box_len >= 1 &&
-                   m->box_len <= 16 && m->n_params > 0,
+                   m->box_len <= 16 && m->n_params > 0 &&
+                   (m->loc_split == 0 || m->loc_split == 1),
                PGNN_E_INVALID, "trainer_create: bad model header");
   Trainer *t = new Trainer();
   t->m = *m;
@@ -1262,9 +1269,14 @@ extern "C" int pgnn_trainer_create(const pgnn_train_model *m, void **handle) {
       if (d.b.back().ref.n_out != hw) ok = false;        // stage output width
       if (d.kind == 1 && d.a[0].ref.k_in != hw + 3) ok = false;
     }
+    if (m->loc_split && hw % m->num_classes != 0)
+      rc = fail(PGNN_E_INVALID,
+                "trainer_create: loc_split needs a feature width that "
+                "num_classes divides");
+    const int c_loc = m->loc_split ? hw / m->num_classes : hw;
     for (int j = 0; j < m->num_classes; ++j)
-      if (t->loc[3 * (size_t)j].ref.k_in != hw) ok = false;
-    if (!ok)
+      if (t->loc[3 * (size_t)j].ref.k_in != c_loc) ok = false;
+    if (!ok && !rc)
       rc = fail(PGNN_E_UNSUPPORTED,
                 "trainer_create: the native step needs a pooling stage only "
                 "in front and one feature width from the first stage to the "
@@ -1274,7 +1286,16 @@ extern "C" int pgnn_trainer_create(const pgnn_train_model *m, void **handle) {
     delete t;
     return rc;
   }
-  if (!plan_head_groups(*t)) t->groups.clear();  // heads one by one
+  if (!plan_head_groups(*t)) {
+    t->groups.clear();  // heads one by one
+    if (m->loc_split) {
+      // (the one-by-one path hands every head the full-width rows)
+      delete t;
+      return fail(PGNN_E_UNSUPPORTED,
+                  "trainer_create: split box heads run as fused groups only "
+                  "(C -> hw -> hw -> L with one hw <= 160, L <= 8)");
+    }
+  }
   t->images_bytes = layout_images(*t);
   t->shape = shape_of(*t);
   *handle = t;
@@ -1410,9 +1431,13 @@ extern "C" int pgnn_trainer_bind(void *handle, float *params, float *grads,
         add_to(once, first_o, nullptr, nullptr, g.f[2].w, nc, nc, 6, (size_t)nc, n3);
         slot = 1;
       }
+      // loc_split: head j's first layer is the row range [j s, (j + 1) s) of
+      // its fused block -- assembled there, its gradient read back from
+      // there; the rows around it were zeroed above and nothing writes them
+      const int s_rows = t->m.loc_split ? t->loc[0].ref.k_in : 0;
       for (size_t i = 0; i < g.lids.size(); ++i) {
         const int j = g.lids[i], sl = slot + (int)i;
-        block(t->loc[3 * j], 0, 0, hw * sl);
+        block(t->loc[3 * j], 0, j * s_rows, hw * sl);
         block(t->loc[3 * j + 1], 1, hw * sl, g.base + hw * (int)i);
         block(t->loc[3 * j + 2], 2, g.base + hw * (int)i, g.base + 8 * (int)i);
       }

@@ -346,6 +346,14 @@ class MultiLayerFastLocalGraphModelV2(object):
             reg = scale * float(sum(np.abs(v).sum() for name, v in
                                     self._store.params.items()
                                     if name.endswith('/weights')))
+        elif self._regularizer_type is not None and self._store is not None:
+            # 'l2' / 'l1_l2' (models.py:11-15): l1 sum|w| + l2 sum(w^2) / 2
+            l1, l2 = regularizer_scales(self._regularizer_type,
+                                        self._regularizer_kwargs)
+            ws = [np.asarray(v, np.float64) for name, v in
+                  self._store.params.items() if name.endswith('/weights')]
+            reg = l1 * float(sum(np.abs(w).sum() for w in ws)) + \
+                0.5 * l2 * float(sum((w * w).sum() for w in ws))
         # per-class sums of the per-vertex Huber vectors (diagnostic only)
         sel = pb[torch.arange(k, device=dev), lab.long()]
         err = sel - gt
@@ -363,6 +371,31 @@ class MultiLayerFastLocalGraphModelV2(object):
             'reg_loss': reg, 'num_endpoint': int(n), 'num_valid_endpoint': nv,
             'classwise_loc_loss': classwise,
         }
+
+
+def regularizer_scales(regularizer_type, regularizer_kwargs):
+    """(l1, l2) of models.py:11-15's regularizer_dict, tf.contrib.layers'
+    keyword names: l1_regularizer(scale) = scale * sum|w|, l2_regularizer(scale)
+    = scale * sum(w^2) / 2 (tf.nn.l2_loss), l1_l2_regularizer(scale_l1=1.0,
+    scale_l2=1.0) = the sum of the two.  FC weights only (models.py:114-115)."""
+    kw = dict(regularizer_kwargs or {})
+    if regularizer_type is None:
+        return 0.0, 0.0
+    if regularizer_type not in ('l1', 'l2', 'l1_l2'):
+        raise KeyError(regularizer_type)
+    known = ('scale_l1', 'scale_l2') if regularizer_type == 'l1_l2' \
+        else ('scale',)
+    unknown = sorted(set(kw) - set(known) - {'scope'})
+    if unknown:
+        raise ValueError("regularizer_kwargs %s of %r (it takes %s)"
+                         % (unknown, regularizer_type, list(known)))
+    if regularizer_type == 'l1_l2':
+        return float(kw.get('scale_l1', 1.0)), float(kw.get('scale_l2', 1.0))
+    if 'scale' not in kw:
+        raise ValueError("regularizer %r needs regularizer_kwargs['scale']"
+                         % (regularizer_type,))
+    scale = float(kw['scale'])
+    return (scale, 0.0) if regularizer_type == 'l1' else (0.0, scale)
 
 
 def get_model(model_name):

@@ -520,14 +520,15 @@ class BatchPrefetcher(object):
 
 
 class StepResult(object):
-    """The numbers of one training step ([sum CE, sum loc, -, -, L1 of the
-    weights, (global n, n_valid)] float64), on their way to pinned host memory
+    """The numbers of one training step ([sum CE, sum loc, -, -, sum |w| and
+    sum w^2 of the weights, (global n, n_valid)] float64), on their way to
+    pinned host memory
     on the step's stream.  get() waits for that copy -- not for anything queued
     after it -- and returns the loss dict of models.py:308-311."""
 
     def __init__(self, trainer, dev_values, counts, lr):
         self.cls_w, self.loc_w = trainer.cls_w, trainer.loc_w
-        self.l1_scale = trainer.l1_scale
+        self.l1_scale, self.l2_scale = trainer.l1_scale, trainer.l2_scale
         self.counts, self.lr = counts, lr
         self.host = torch.empty(dev_values.shape, dtype=dev_values.dtype,
                                 pin_memory=True)
@@ -543,12 +544,15 @@ class StepResult(object):
             self._dev = None
             v = self.host.tolist()
             n_total, nv_total = self.counts if self.counts is not None \
-                else (v[5], v[6])
+                else (v[6], v[7])
             self._out = {
                 'cls_loss': self.cls_w * float(v[0]) / max(n_total, 1.0),
                 'loc_loss': (self.loc_w * float(v[1]) / nv_total)
                 if nv_total > 0 else 0.0,
-                'reg_loss': self.l1_scale * float(v[4]),
+                # (v[5] is written only when there is an l2 term)
+                'reg_loss': self.l1_scale * float(v[4]) + (
+                    0.5 * self.l2_scale * float(v[5]) if self.l2_scale
+                    else 0.0),
                 'num_endpoint': int(n_total), 'num_valid_endpoint': nv_total,
                 'learning_rate': self.lr,
             }
@@ -664,12 +668,11 @@ class Trainer(object):
         # as TF's beta1_power / beta2_power variables would)
         self.opt_step = 0
         mk = config['model_kwargs']
-        if mk.get('regularizer_type') not in (None, 'l1'):
-            raise NotImplementedError("regularizer %r" % mk['regularizer_type'])
-        self.l1_scale = float(mk['regularizer_kwargs']['scale']) \
-            if mk.get('regularizer_type') == 'l1' else 0.0
+        from .models import cls_loss_kind, loss_top_k, regularizer_scales
+        # models.py:11-15: 'l1' / 'l2' / 'l1_l2' by tf.contrib.layers' keywords
+        self.l1_scale, self.l2_scale = regularizer_scales(
+            mk.get('regularizer_type'), mk.get('regularizer_kwargs'))
         check_trainable_kinds(config)
-        from .models import cls_loss_kind, loss_top_k
         # models.py:198-208: the loss entries may be dicts keyed by mode
         lcfg = {key: (val['train'] if isinstance(val, dict) and 'train' in val
                       and key in ('cls_loss_type', 'cls_loss_kwargs',
@@ -693,6 +696,15 @@ class Trainer(object):
         self._class_loc_w = None
         # ---- flat parameter / gradient buffers --------------------------
         self.specs = variable_specs(config, box_encoding_len=box_encoding_len)
+        # gnn.py:178-213 (ClassAwareSeparatedPredictor): box head j reads the
+        # columns [j*s, (j+1)*s) of the last features (s = this width); None:
+        # every head reads all of them (the other two predictors, which
+        # differ in their hidden widths only -- carried by the specs)
+        head = mk['layer_configs'][-1]
+        self._head_slice = None
+        if head['type'] == 'classaware_separated_predictor':
+            self._head_slice = dict(self.specs)[mlp_names(
+                head['scope'] + '/predictor/loc/cls_0', 1)[0] + '/weights'][0]
         if params is None:
             params = init_params(config, seed=seed)
         total = int(sum(int(np.prod(s)) for _, s in self.specs))
@@ -788,16 +800,19 @@ class Trainer(object):
     def _apply_gradients(self, lr, l1_mult=1):
         """optimizer.apply_gradients (train.py:392-405) on the flat buffers;
         `lr` is the decayed learning rate of this step; `l1_mult`: how many
-        batches' regulariser gradients the buffer stands for."""
+        batches' regulariser gradients (l1 sign(w) + l2 w) the buffer stands
+        for."""
         kind = _OPTIMIZERS[self.optimizer][0]
         kw = self.opt_kwargs
         l1 = self.l1_scale * l1_mult
+        l2 = self.l2_scale * l1_mult
         if kind == 0:
-            _lib.check(self.lib.pgnn_sgd_step(
+            _lib.check(self.lib.pgnn_sgd_step_l1l2(
                 _lib.ptr(self.flat), _lib.ptr(self.grad),
                 _lib.ptr(self.is_weight), self.flat.numel(),
                 ctypes.c_float(lr), ctypes.c_float(1.0),
-                ctypes.c_float(l1), self._st()), "pgnn_sgd_step")
+                ctypes.c_float(l1), ctypes.c_float(l2), self._st()),
+                "pgnn_sgd_step_l1l2")
             return
         if kind == 1:
             h = (kw['momentum'], 0.0, 0.0)
@@ -810,14 +825,14 @@ class Trainer(object):
             t = self.opt_step + 1
             lr = lr * np.sqrt(1.0 - kw['beta2'] ** t) / (1.0 - kw['beta1'] ** t)
             h = (kw['beta1'], kw['beta2'], kw['epsilon'])
-        _lib.check(self.lib.pgnn_optimizer_step(
+        _lib.check(self.lib.pgnn_optimizer_step_l1l2(
             kind, _lib.ptr(self.flat), _lib.ptr(self.grad),
             _lib.ptr(self.is_weight), _lib.ptr(self.slots[0]),
             _lib.ptr(self.slots[1]) if len(self.slots) > 1 else None,
             self.flat.numel(), ctypes.c_float(lr), ctypes.c_float(1.0),
-            ctypes.c_float(l1), ctypes.c_float(h[0]),
+            ctypes.c_float(l1), ctypes.c_float(l2), ctypes.c_float(h[0]),
             ctypes.c_float(h[1]), ctypes.c_float(h[2]), self._st()),
-            "pgnn_optimizer_step")
+            "pgnn_optimizer_step_l1l2")
 
     def optimizer_state_dict(self):
         """The optimizer's slot variables under TF's names ('<variable>/<slot>',
@@ -1134,8 +1149,7 @@ class Trainer(object):
                 for i, n in enumerate(names):
                     self._fc_ref(arr[i], n)
         pc = lcs[-1]
-        if pc['type'] != 'classaware_predictor':
-            raise NotImplementedError(pc['type'])
+        m.loc_split = int(self._head_slice is not None)
         ps = pc['scope'] + '/predictor'
         for i, n in enumerate(mlp_names(ps + '/cls', 2)):
             self._fc_ref(m.cls[i], n)
@@ -1374,8 +1388,6 @@ class Trainer(object):
             else:
                 raise NotImplementedError(lc['type'])
         pc = self.config['model_kwargs']['layer_configs'][-1]
-        if pc['type'] != 'classaware_predictor':
-            raise NotImplementedError(pc['type'])
         ps = pc['scope'] + '/predictor'
         cls_names = mlp_names(ps + '/cls', 2)
         cacts = [h, self.fc_fwd(cls_names[0], h, True)]
@@ -1388,6 +1400,12 @@ class Trainer(object):
         for j in range(self.nc):
             names = mlp_names(ps + '/loc/cls_%d' % j, 3)
             a = [h]
+            if self._head_slice is not None:
+                # tf.split (gnn.py:196): this head's columns as rows of their own
+                s = self._head_slice
+                a = [torch.zeros((k, padded_width(s)), dtype=torch.float32,
+                                 device=dev)]
+                a[0][:, :s] = h[:, j * s:(j + 1) * s]
             for i, n in enumerate(names):
                 a.append(self.fc_fwd(n, a[-1], i < 2))
             pred[:, j, :] = a[-1][:, :self.box_len]
@@ -1520,12 +1538,25 @@ class Trainer(object):
             _lib.ptr(dpred), self._st()), "pgnn_loss_fwd_bwd_sel")
         return sums, dlog, dpred
 
+    def _weight_norms(self, out2):
+        """out2[0] = sum |w| over the weights and, when there is an l2 term,
+        out2[1] = sum w^2 (left alone otherwise: the l1 step keeps its
+        launch)."""
+        if self.l2_scale:
+            _lib.check(self.lib.pgnn_weight_norms(
+                _lib.ptr(self.flat), _lib.ptr(self.is_weight),
+                self.flat.numel(), _lib.ptr(out2), self._st()),
+                "pgnn_weight_norms")
+        else:                               # (the call zeroes out2[0] first)
+            _lib.check(self.lib.pgnn_l1_norm(
+                _lib.ptr(self.flat), _lib.ptr(self.is_weight),
+                self.flat.numel(), _lib.ptr(out2), self._st()), "pgnn_l1_norm")
+
     def reg_loss(self):
-        out = torch.zeros(1, dtype=torch.float64, device=self.device)
-        _lib.check(self.lib.pgnn_l1_norm(
-            _lib.ptr(self.flat), _lib.ptr(self.is_weight), self.flat.numel(),
-            _lib.ptr(out), self._st()), "pgnn_l1_norm")
-        return self.l1_scale * float(out.item())
+        out = torch.zeros(2, dtype=torch.float64, device=self.device)
+        self._weight_norms(out)
+        v = out.tolist()
+        return self.l1_scale * v[0] + 0.5 * self.l2_scale * v[1]
 
     # ---- backward -----------------------------------------------------------------
     def _multi(self):
@@ -1553,8 +1584,8 @@ class Trainer(object):
         hw = self._h_width
         dh = torch.zeros((k, hw), dtype=torch.float32, device=dev)
 
-        def add_dh(dx, width):
-            dh[:, :width] += dx[:, :width]
+        def add_dh(dx, width, col0=0):
+            dh[:, col0:col0 + width] += dx[:, :width]
 
         # heads
         dy = torch.zeros((k, padded_width(self.nc)), dtype=torch.float32,
@@ -1571,7 +1602,11 @@ class Trainer(object):
             d = self.fc_bwd(names[2], a[2], a[3], dy, False)
             d = self.fc_bwd(names[1], a[1], a[2], d, True)
             d = self.fc_bwd(names[0], a[0], a[1], d, True)
-            add_dh(d, cwidth)
+            if self._head_slice is not None:
+                # a split head's input gradient goes to its own columns
+                add_dh(d, self._head_slice, j * self._head_slice)
+            else:
+                add_dh(d, cwidth)
         # layers in reverse
         while saved:
             item = saved.pop()
@@ -1693,9 +1728,9 @@ class Trainer(object):
         (input_v, coords, kps, edges, labels, boxes, valid) = batch
         self.grad.zero_()
         # the step's numbers, written in place by their kernels: [sum CE, sum
-        # loc, n, n_valid | L1 of the weights | global n, n_valid] -- no
-        # concatenate at the end
-        rec = torch.empty(7, dtype=torch.float64, device=self.device)
+        # loc, n, n_valid | sum |w|, sum w^2 of the weights | global n,
+        # n_valid] -- no concatenate at the end
+        rec = torch.empty(8, dtype=torch.float64, device=self.device)
         va = torch.as_tensor(valid).to(self.device, torch.float32).reshape(-1)
         k = int(va.shape[0])
         multi = self._multi()
@@ -1713,7 +1748,7 @@ class Trainer(object):
             if num_valid is not None:
                 counts_dev = allreduce_endpoint_counts_device(
                     k, float(num_valid), self.device, self.pg,
-                    self.force_collective, self.comm, out=rec[5:7])
+                    self.force_collective, self.comm, out=rec[6:8])
         elif num_valid is not None:
             counts = (float(k), float(num_valid))
         logits, pred = self.forward(input_v, coords, kps, edges)
@@ -1727,11 +1762,11 @@ class Trainer(object):
             counts_dev = allreduce_endpoint_counts_device(
                 k, (va * sel[1]).sum(), self.device, self.pg,
                 self.force_collective and multi, self.comm if multi else None,
-                out=rec[5:7])
+                out=rec[6:8])
         elif multi and counts_dev is None:
             counts_dev = allreduce_endpoint_counts_device(
                 k, va.sum(), self.device, self.pg, self.force_collective,
-                self.comm, out=rec[5:7])
+                self.comm, out=rec[6:8])
         elif not multi and counts is None:
             counts = (float(k), float(va.sum().item()))
         # unify_copies: global endpoint counts (train.py:268-284)
@@ -1758,18 +1793,15 @@ class Trainer(object):
             ev.append((e0, e1))
         lr = learning_rate(self.train_config, self.global_step)
         # Everything the device still has to do is queued BEFORE the host reads
-        # anything: the L1 term of the weights this step used, SGD, the image
-        # refresh.  The step's numbers then come back in one copy.
-        l1 = rec[4:5]
-        _lib.check(self.lib.pgnn_l1_norm(         # (the call zeroes `l1` first)
-            _lib.ptr(self.flat), _lib.ptr(self.is_weight), self.flat.numel(),
-            _lib.ptr(l1), self._st()), "pgnn_l1_norm")
+        # anything: the regulariser's norms of the weights this step used, SGD,
+        # the image refresh.  The step's numbers then come back in one copy.
+        self._weight_norms(rec[4:6])
         if apply:
             self._apply_gradients(lr)
             self.repack()
             self.global_step += 1
             self.opt_step += 1
-        res = StepResult(self, rec[:5] if counts_dev is None else rec, counts,
+        res = StepResult(self, rec[:6] if counts_dev is None else rec, counts,
                          lr)
         if after_enqueue is not None:
             # (behind the collective and the update: the host reads of a graph

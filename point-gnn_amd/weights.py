@@ -13,13 +13,29 @@ Names and shapes are exactly those of the reference's TF variables (SURVEY.md
 """
 import numpy as np
 
-__all__ = ["variable_specs", "init_params", "count_params", "mlp_names"]
+__all__ = ["variable_specs", "init_params", "count_params", "mlp_names",
+           "separated_slice_width"]
 
 _PREDICTOR_SHAPES = {
     # models.py:60-69: (cls hidden widths, loc hidden widths)
     'classaware_predictor': ((64,), (64, 64)),
     'classaware_predictor_128': ((128,), (128, 128)),
+    # models.py:70-74: box head j reads its own slice of the features
+    'classaware_separated_predictor': ((64,), (64, 64)),
 }
+
+
+def separated_slice_width(predictor_type, dim, num_classes):
+    """Input width of one box head: `dim` for the shared-input heads,
+    `dim // num_classes` for the separated one (gnn.py:196, tf.split)."""
+    if predictor_type != 'classaware_separated_predictor':
+        return dim
+    if dim % num_classes != 0:
+        raise ValueError(
+            "classaware_separated_predictor splits the %d feature columns "
+            "into num_classes=%d equal slices; %d %% %d != 0"
+            % (dim, num_classes, dim, num_classes))
+    return dim // num_classes
 
 
 def mlp_names(scope, n_layers):
@@ -74,8 +90,9 @@ def variable_specs(config, input_feature_dim=1, box_encoding_len=7):
     s, _ = _mlp_specs(pc['scope'] + '/predictor/cls', dim,
                       list(cls_w) + [nc])
     specs += s
+    loc_in = separated_slice_width(pc['type'], dim, nc)
     for j in range(nc):
-        s, _ = _mlp_specs(pc['scope'] + '/predictor/loc/cls_%d' % j, dim,
+        s, _ = _mlp_specs(pc['scope'] + '/predictor/loc/cls_%d' % j, loc_in,
                           list(loc_w) + [box_encoding_len])
         specs += s
     return specs
