@@ -306,7 +306,9 @@ __global__ void sort_keys_kernel(const float *__restrict__ scores, int64_t n,
                                  uint32_t *keys, uint32_t *vals) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  uint32_t u = __float_as_uint(scores[i]);
+  // -0.0f + 0.0f = +0.0f: the two zeros are equal scores and share a key, so
+  // the stable sort leaves them in input order like any other tie
+  uint32_t u = __float_as_uint(scores[i] + 0.0f);
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending float order
   keys[i] = ~u;                                     // descending score
   vals[i] = (uint32_t)i;

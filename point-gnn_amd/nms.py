@@ -17,8 +17,8 @@ Differences a caller can observe:
     path: random_box_shift (preprocess.py:281-301).
   * inputs are not modified (the reference edits `bboxes`/`scores` in place on
     its sorted copies only, so neither does it in effect);
-  * boxes with EQUAL scores keep their input order (np.argsort(-scores),
-    nms.py:93, leaves it unspecified).
+  * boxes with EQUAL scores (+0.0 and -0.0 are equal) keep their input order
+    (np.argsort(-scores), nms.py:93, leaves it unspecified).
 NumPy in -> NumPy out; CUDA tensors in -> CUDA tensors out.
 """
 import ctypes
