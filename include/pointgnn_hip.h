@@ -1291,6 +1291,29 @@ int pgnn_box_encode_f32(const int32_t *cls_labels, const float *xyz,
                         const float *boxes, const float *class_table,
                         int32_t n_table, int64_t n_rows, int32_t boxes_per_row,
                         float *encoded, void *stream);
+/* Box codec `classaware_all_class_box_canonical_encoding`: the same arguments,
+ * class table and pass-through rules (columns >= 1 and inactive labels get the
+ * xyz offset only), with the vertex->centre offset expressed in the anchor's
+ * own frame.  a = the yaw relative to the anchor (yaw - yaw_offset when
+ * encoding, e6*pi/4 when decoding); (p, q) = (l, w) for a horizontal anchor
+ * and (w, l) for a vertical one, the reference's swap.  cos/sin/exp/log are
+ * evaluated in double on the float32 argument and rounded once; products, sums
+ * and quotients are float32 in the reference's order.
+ * Replaces box_encoding.py:345-395 (classaware_all_class_box_canonical_decoding):
+ *   out0 = e0*p*cos a + e2*q*sin a, out2 = -e0*p*sin a + e2*q*cos a, + xyz. */
+int pgnn_box_decode_canonical_f32(const int32_t *cls_labels, const float *xyz,
+                                  const float *encoded,
+                                  const float *class_table, int32_t n_table,
+                                  int64_t n_rows, int32_t boxes_per_row,
+                                  float *decoded, void *stream);
+/* Replaces box_encoding.py:301-343 (classaware_all_class_box_canonical_encoding):
+ *   d = box - xyz, out0 = (d0*cos a - d2*sin a)/p, out2 = (d0*sin a + d2*cos a)/q,
+ *   out6 = a/(pi/4). */
+int pgnn_box_encode_canonical_f32(const int32_t *cls_labels, const float *xyz,
+                                  const float *boxes, const float *class_table,
+                                  int32_t n_table, int64_t n_rows,
+                                  int32_t boxes_per_row, float *encoded,
+                                  void *stream);
 /* run.py:266-290: candidates of probs [n_vertices, num_classes] = flat indices
  * p = k*num_classes + c with 0 < c < num_classes-1 and prob > 1/num_classes,
  * ascending (np.nonzero order).  out_label holds the merged class of
@@ -1392,6 +1415,22 @@ int pgnn_box_encode_f64_xyz64(const int32_t *cls_labels, const double *xyz,
                               int32_t n_table, int64_t n_rows,
                               int32_t boxes_per_row, float *encoded,
                               void *stream);
+/* pgnn_box_encode_canonical_f32 the same way: box_encoding.py:301-343 in
+ * float64 on float64 boxes, rounded to float32 once (train.py:120-130 under
+ * box_encoding_method 'classaware_all_class_box_canonical_encoding'). */
+int pgnn_box_encode_canonical_f64(const int32_t *cls_labels, const float *xyz,
+                                  const double *boxes,
+                                  const double *class_table, int32_t n_table,
+                                  int64_t n_rows, int32_t boxes_per_row,
+                                  float *encoded, void *stream);
+/* ... with float64 vertices (box_encoding.py:301-343 on train.py:120-122's
+ * float64 vertex coordinates). */
+int pgnn_box_encode_canonical_f64_xyz64(const int32_t *cls_labels,
+                                        const double *xyz, const double *boxes,
+                                        const double *class_table,
+                                        int32_t n_table, int64_t n_rows,
+                                        int32_t boxes_per_row, float *encoded,
+                                        void *stream);
 
 /* Point-wise parts of the training augmentations (models/preprocess.py:44-78
  * random_rotation_all / random_flip_all, :239-326 random_box_shift) on a

@@ -428,6 +428,10 @@ _SIGNATURES = {
                                     c_i32, c_vp, c_vp]),
     "pgnn_box_encode_f32": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64,
                                     c_i32, c_vp, c_vp]),
+    "pgnn_box_decode_canonical_f32": (
+        c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp]),
+    "pgnn_box_encode_canonical_f32": (
+        c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp]),
     "pgnn_detection_candidates": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp,
                                           c_i64, c_vp, c_vp]),
     "pgnn_detection_candidates_dyn": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp,
@@ -450,6 +454,10 @@ _SIGNATURES = {
                                     c_i32, c_vp, c_vp]),
     "pgnn_box_encode_f64_xyz64": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64,
                                           c_i32, c_vp, c_vp]),
+    "pgnn_box_encode_canonical_f64": (
+        c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp]),
+    "pgnn_box_encode_canonical_f64_xyz64": (
+        c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp]),
     "pgnn_points_affine_f64": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "pgnn_points_in_box_f64": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                        c_vp]),

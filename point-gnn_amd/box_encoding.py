@@ -2,13 +2,30 @@
 
 Same registry (`get_box_encoding_fn` / `get_box_decoding_fn` /
 `get_encoding_len`, box_encoding.py:469-508) and the same call signature
-`fn(cls_labels [R,1], points_xyz [R,3], boxes [R,B,7], label_map)`.  Only
-`'classaware_all_class_box_encoding'` -- the method of every shipped config --
-is implemented; the other registry keys raise NotImplementedError.
+`fn(cls_labels [R,1], points_xyz [R,3], boxes [R,B,7], label_map)`.  Both keys
+a reference config can select are implemented:
 
-NumPy in -> NumPy out, CUDA tensors in -> CUDA tensors out; the arithmetic
-runs in libpointgnn_hip.so (`pgnn_box_{decode,encode}_f32`), float32 like the
-reference's NumPy code on its float32 network outputs.
+  'classaware_all_class_box_encoding'            box_encoding.py:231-299, the
+      method of every shipped config: offset / median size, log size ratio,
+      yaw relative to the anchor in units of pi/4;
+  'classaware_all_class_box_canonical_encoding'  box_encoding.py:301-395: the
+      same, with the (x, z) offset rotated into the anchor's own frame by the
+      relative yaw `a` and divided by (l, w) for a horizontal anchor, (w, l)
+      for a vertical one (the reference's swap, :331-337).
+
+The other four keys (`direct_encoding`, `center_box_encoding`,
+`voxelnet_box_encoding`, `classaware_voxelnet_box_encoding`) raise
+NotImplementedError: they take three arguments (box_encoding.py:5-208) while
+every caller of the reference passes four (train.py:123-124, eval.py:106-107,
+run.py:276-277), so no reference config can run with them either.
+
+NumPy in -> NumPy out, CUDA tensors in -> CUDA tensors out, inputs are never
+written; the arithmetic runs in libpointgnn_hip.so
+(`pgnn_box_{decode,encode}[_canonical]_f32`), float32 like the reference's
+NumPy code on its float32 network outputs: cos/sin/exp/log in double on the
+float32 argument and rounded once, everything else float32 in the reference's
+operation order.  float64 boxes (the training targets) select the float64
+encoders (`pgnn_box_encode[_canonical]_f64[_xyz64]`), rounded to float32 once.
 """
 import math
 
@@ -63,9 +80,27 @@ def _device_table(label_map, dtype, dev):
     return t
 
 
-def _run(entry, cls_labels, points_xyz, boxes, label_map):
+PLAIN = 'classaware_all_class_box_encoding'
+CANONICAL = 'classaware_all_class_box_canonical_encoding'
+
+# (method, direction) -> C entries for (float32 boxes, float64 boxes with
+# float32 vertices, float64 boxes with float64 vertices); decoding is float32
+# only (network outputs)
+_ENTRIES = {
+    (PLAIN, 'encode'): ("pgnn_box_encode_f32", "pgnn_box_encode_f64",
+                        "pgnn_box_encode_f64_xyz64"),
+    (PLAIN, 'decode'): ("pgnn_box_decode_f32", None, None),
+    (CANONICAL, 'encode'): ("pgnn_box_encode_canonical_f32",
+                            "pgnn_box_encode_canonical_f64",
+                            "pgnn_box_encode_canonical_f64_xyz64"),
+    (CANONICAL, 'decode'): ("pgnn_box_decode_canonical_f32", None, None),
+}
+
+
+def _run(method, direction, cls_labels, points_xyz, boxes, label_map):
     import torch
     lib = _lib.load()
+    entry32, entry64, entry64_xyz64 = _ENTRIES[method, direction]
     as_numpy = not isinstance(boxes, torch.Tensor)
     dev = boxes.device if not as_numpy else torch.device("cuda", 0)
     if dev.type != "cuda":
@@ -76,28 +111,29 @@ def _run(entry, cls_labels, points_xyz, boxes, label_map):
         return torch.as_tensor(np.asarray(x) if not isinstance(
             x, torch.Tensor) else x).to(device=dev, dtype=dtype).contiguous()
 
+    def is_f64(x):
+        return (x.dtype == torch.float64) if isinstance(x, torch.Tensor) \
+            else np.asarray(x).dtype == np.float64
+
     # float64 ground-truth boxes (kitti_dataset.py:1199 np.zeros default) are
     # encoded in float64 and rounded once, like train.py:120-130
-    wide = entry == "pgnn_box_encode_f32" and (
-        (as_numpy and np.asarray(boxes).dtype == np.float64) or
-        (not as_numpy and boxes.dtype == torch.float64))
+    wide = entry64 is not None and is_f64(boxes)
     if wide:
         b = to(boxes, torch.float64)
         rows, per_row = int(b.shape[0]), int(b.shape[1])
         lab = to(cls_labels, torch.int32).reshape(-1)
         # float64 vertices (the training path, train.py:120-122) are used
         # as they are; float32 ones are widened inside the kernel
-        xyz64 = (np.asarray(points_xyz).dtype == np.float64) if not isinstance(
-            points_xyz, torch.Tensor) else points_xyz.dtype == torch.float64
+        xyz64 = is_f64(points_xyz)
         xyz = to(points_xyz, torch.float64 if xyz64 else torch.float32)
         table = _device_table(label_map, np.float64, dev)
         out = torch.empty(tuple(b.shape), dtype=torch.float32, device=dev)
+        entry = entry64_xyz64 if xyz64 else entry64
         with torch.cuda.device(dev):
-            _lib.check((lib.pgnn_box_encode_f64_xyz64 if xyz64 else
-                        lib.pgnn_box_encode_f64)(
+            _lib.check(getattr(lib, entry)(
                 _lib.ptr(lab), _lib.ptr(xyz), _lib.ptr(b), _lib.ptr(table),
                 int(table.shape[0]), rows, per_row, _lib.ptr(out),
-                _lib.stream_ptr()), "pgnn_box_encode_f64")
+                _lib.stream_ptr()), entry)
         return out.cpu().numpy() if as_numpy else out
     b = to(boxes, torch.float32)
     if b.dim() != 3 or b.shape[2] != 7:
@@ -110,49 +146,70 @@ def _run(entry, cls_labels, points_xyz, boxes, label_map):
     table = _device_table(label_map, np.float32, dev)
     out = torch.empty_like(b)
     with torch.cuda.device(dev):
-        _lib.check(getattr(lib, entry)(
+        _lib.check(getattr(lib, entry32)(
             _lib.ptr(lab), _lib.ptr(xyz), _lib.ptr(b), _lib.ptr(table),
             int(table.shape[0]), rows, per_row, _lib.ptr(out),
-            _lib.stream_ptr()), entry)
+            _lib.stream_ptr()), entry32)
     return out.cpu().numpy() if as_numpy else out
 
 
 def classaware_all_class_box_encoding(cls_labels, points_xyz, boxes_3d,
                                       label_map):
     """box_encoding.py:231-263."""
-    return _run("pgnn_box_encode_f32", cls_labels, points_xyz, boxes_3d,
-                label_map)
+    return _run(PLAIN, 'encode', cls_labels, points_xyz, boxes_3d, label_map)
 
 
 def classaware_all_class_box_decoding(cls_labels, points_xyz, encoded_boxes,
                                       label_map):
     """box_encoding.py:265-299."""
-    return _run("pgnn_box_decode_f32", cls_labels, points_xyz, encoded_boxes,
+    return _run(PLAIN, 'decode', cls_labels, points_xyz, encoded_boxes,
+                label_map)
+
+
+def classaware_all_class_box_canonical_encoding(cls_labels, points_xyz,
+                                                boxes_3d, label_map):
+    """box_encoding.py:301-343: the offset box centre - vertex rotated into the
+    anchor's frame (by the yaw for a horizontal anchor, yaw - pi/2 for a
+    vertical one) and divided by (l, w) resp. (w, l)."""
+    return _run(CANONICAL, 'encode', cls_labels, points_xyz, boxes_3d,
+                label_map)
+
+
+def classaware_all_class_box_canonical_decoding(cls_labels, points_xyz,
+                                                encoded_boxes, label_map):
+    """box_encoding.py:345-395."""
+    return _run(CANONICAL, 'decode', cls_labels, points_xyz, encoded_boxes,
                 label_map)
 
 
 _METHODS = ('direct_encoding', 'center_box_encoding', 'voxelnet_box_encoding',
-            'classaware_voxelnet_box_encoding',
-            'classaware_all_class_box_encoding',
-            'classaware_all_class_box_canonical_encoding')
+            'classaware_voxelnet_box_encoding', PLAIN, CANONICAL)
+_ENCODERS = {PLAIN: classaware_all_class_box_encoding,
+             CANONICAL: classaware_all_class_box_canonical_encoding}
+_DECODERS = {PLAIN: classaware_all_class_box_decoding,
+             CANONICAL: classaware_all_class_box_canonical_decoding}
 
 
-def _lookup(name, fn):
+def _lookup(name, fns):
     if name not in _METHODS:
         raise KeyError(name)
-    if name != 'classaware_all_class_box_encoding':
+    if name not in fns:
         raise NotImplementedError(
-            "%s: only 'classaware_all_class_box_encoding' (the method of all "
-            "shipped configs) has a HIP implementation" % name)
-    return fn
+            "%s: the reference's callers pass (cls_labels, xyz, boxes, "
+            "label_map) to every codec (train.py:123-124, eval.py:106-107, "
+            "run.py:276-277) and this one takes three arguments "
+            "(box_encoding.py:5-208), so no config can select it there "
+            "either; only %r and %r have HIP implementations"
+            % (name, PLAIN, CANONICAL))
+    return fns[name]
 
 
 def get_box_encoding_fn(encoding_method_name):
-    return _lookup(encoding_method_name, classaware_all_class_box_encoding)
+    return _lookup(encoding_method_name, _ENCODERS)
 
 
 def get_box_decoding_fn(encoding_method_name):
-    return _lookup(encoding_method_name, classaware_all_class_box_decoding)
+    return _lookup(encoding_method_name, _DECODERS)
 
 
 def get_encoding_len(encoding_method_name):

@@ -254,6 +254,81 @@ __global__ void box_encode_kernel(const int32_t *__restrict__ labels,
   for (int i = 0; i < 7; ++i) out[idx * 7 + i] = d[i];
 }
 
+// Canonical codec (box_encoding.py:301-395): the vertex->centre offset lives in
+// the anchor's own frame.  a = the yaw relative to the anchor; (p, q) = (l, w)
+// for a horizontal anchor and (w, l) for a vertical one, the reference's swap
+// (:331-337, :373-381).  cos/sin in double on the float32 angle, rounded once;
+// products, sums and quotients in float32 in the reference's order.
+__global__ void box_decode_canonical_kernel(
+    const int32_t *__restrict__ labels, const float *__restrict__ xyz,
+    const float *__restrict__ enc, const float *__restrict__ table, int n_table,
+    int64_t rows, int per_row, float *__restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows * per_row) return;
+  const int64_t r = idx / per_row;
+  const int col = (int)(idx - r * per_row);
+  const float *e = enc + idx * 7;
+  float d[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) d[i] = e[i];
+  const int lab = labels[r];
+  if (col == 0 && lab >= 0 && lab < n_table && table[5 * lab + 4] != 0.0f) {
+    const float l = table[5 * lab], h = table[5 * lab + 1],
+                w = table[5 * lab + 2], yo = table[5 * lab + 3];
+    const float p = yo != 0.0f ? w : l, q = yo != 0.0f ? l : w;
+    const float a = e[6] * 0.78539816339744830962f;
+    const float c = (float)cos((double)a), s = (float)sin((double)a);
+    const float t0 = e[0] * p, t2 = e[2] * q;
+    d[0] = t0 * c + t2 * s;
+    d[1] = e[1] * h;
+    d[2] = -t0 * s + t2 * c;
+    d[3] = (float)exp((double)e[3]) * l;
+    d[4] = (float)exp((double)e[4]) * h;
+    d[5] = (float)exp((double)e[5]) * w;
+    d[6] = yo != 0.0f ? a + yo : a;
+  }
+  d[0] = d[0] + xyz[3 * r];
+  d[1] = d[1] + xyz[3 * r + 1];
+  d[2] = d[2] + xyz[3 * r + 2];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) out[idx * 7 + i] = d[i];
+}
+
+__global__ void box_encode_canonical_kernel(
+    const int32_t *__restrict__ labels, const float *__restrict__ xyz,
+    const float *__restrict__ boxes, const float *__restrict__ table,
+    int n_table, int64_t rows, int per_row, float *__restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows * per_row) return;
+  const int64_t r = idx / per_row;
+  const int col = (int)(idx - r * per_row);
+  const float *b = boxes + idx * 7;
+  float d[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) d[i] = b[i];
+  d[0] = b[0] - xyz[3 * r];
+  d[1] = b[1] - xyz[3 * r + 1];
+  d[2] = b[2] - xyz[3 * r + 2];
+  const int lab = labels[r];
+  if (col == 0 && lab >= 0 && lab < n_table && table[5 * lab + 4] != 0.0f) {
+    const float l = table[5 * lab], h = table[5 * lab + 1],
+                w = table[5 * lab + 2], yo = table[5 * lab + 3];
+    const float p = yo != 0.0f ? w : l, q = yo != 0.0f ? l : w;
+    const float a = yo != 0.0f ? b[6] - yo : b[6];
+    const float c = (float)cos((double)a), s = (float)sin((double)a);
+    const float dx = d[0], dz = d[2];
+    d[0] = (dx * c - dz * s) / p;
+    d[1] = d[1] / h;
+    d[2] = (dx * s + dz * c) / q;
+    d[3] = (float)log((double)(b[3] / l));
+    d[4] = (float)log((double)(b[4] / h));
+    d[5] = (float)log((double)(b[5] / w));
+    d[6] = a / 0.78539816339744830962f;
+  }
+#pragma unroll
+  for (int i = 0; i < 7; ++i) out[idx * 7 + i] = d[i];
+}
+
 // ---------------------------------------------------------------- candidates
 // run.py:266-290: flat index p = k*nc + c is a candidate when 0 < c < nc-1 and
 // prob > 1/nc; indices come out ascending like np.nonzero.  One workgroup,
@@ -730,6 +805,48 @@ extern "C" int pgnn_box_encode_f32(const int32_t *cls_labels, const float *xyz,
                      n_table, n_rows, boxes_per_row, encoded);
   PGNN_HIP(hipGetLastError());
   return 0;
+  PGNN_GUARD_END
+}
+
+// the canonical pair: same arguments and checks, `kernel` is the direction
+static int box_canonical_impl(
+    void (*kernel)(const int32_t *, const float *, const float *, const float *,
+                   int, int64_t, int, float *),
+    const int32_t *cls_labels, const float *xyz, const float *in,
+    const float *class_table, int32_t n_table, int64_t n_rows,
+    int32_t boxes_per_row, float *out, hipStream_t stream) {
+  PGNN_REQUIRE(n_rows >= 0 && boxes_per_row > 0 && n_table >= 0,
+               PGNN_E_INVALID, "box_codec_canonical: bad size");
+  if (n_rows == 0) return 0;
+  PGNN_REQUIRE(cls_labels && xyz && in && out && (class_table || n_table == 0),
+               PGNN_E_INVALID, "box_codec_canonical: null pointer");
+  const int64_t total = n_rows * boxes_per_row;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((total + 255) / 256)), dim3(256),
+                     0, stream, cls_labels, xyz, in, class_table, n_table,
+                     n_rows, boxes_per_row, out);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pgnn_box_decode_canonical_f32(
+    const int32_t *cls_labels, const float *xyz, const float *encoded,
+    const float *class_table, int32_t n_table, int64_t n_rows,
+    int32_t boxes_per_row, float *decoded, void *stream_) {
+  PGNN_GUARD_BEGIN
+  return box_canonical_impl(box_decode_canonical_kernel, cls_labels, xyz,
+                            encoded, class_table, n_table, n_rows,
+                            boxes_per_row, decoded, (hipStream_t)stream_);
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_box_encode_canonical_f32(
+    const int32_t *cls_labels, const float *xyz, const float *boxes,
+    const float *class_table, int32_t n_table, int64_t n_rows,
+    int32_t boxes_per_row, float *encoded, void *stream_) {
+  PGNN_GUARD_BEGIN
+  return box_canonical_impl(box_encode_canonical_kernel, cls_labels, xyz,
+                            boxes, class_table, n_table, n_rows, boxes_per_row,
+                            encoded, (hipStream_t)stream_);
   PGNN_GUARD_END
 }
 

@@ -109,6 +109,46 @@ __global__ void box_encode_f64_kernel(const int32_t *__restrict__ labels,
   for (int i = 0; i < 7; ++i) out[idx * 7 + i] = (float)d[i];
 }
 
+// box_encoding.py:301-343 (the canonical encoding) the same way: everything in
+// float64, one rounding at the store.  a = the yaw relative to the anchor;
+// the offset is rotated by it and divided by (l, w) for a horizontal anchor,
+// (w, l) for a vertical one (:331-337).
+template <typename T>
+__global__ void box_encode_canonical_f64_kernel(
+    const int32_t *__restrict__ labels, const T *__restrict__ xyz,
+    const double *__restrict__ boxes, const double *__restrict__ table64,
+    int n_table, int64_t rows, int per_row, float *__restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows * per_row) return;
+  const int64_t r = idx / per_row;
+  const int col = (int)(idx - r * per_row);
+  const double *b = boxes + idx * 7;
+  double d[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) d[i] = b[i];
+  d[0] = b[0] - (double)xyz[3 * r];
+  d[1] = b[1] - (double)xyz[3 * r + 1];
+  d[2] = b[2] - (double)xyz[3 * r + 2];
+  const int lab = labels[r];
+  if (col == 0 && lab >= 0 && lab < n_table && table64[5 * lab + 4] != 0.0) {
+    const double l = table64[5 * lab], h = table64[5 * lab + 1],
+                 w = table64[5 * lab + 2], yo = table64[5 * lab + 3];
+    const double p = yo != 0.0 ? w : l, q = yo != 0.0 ? l : w;
+    const double a = yo != 0.0 ? b[6] - yo : b[6];
+    const double c = cos(a), s = sin(a);
+    const double dx = d[0], dz = d[2];
+    d[0] = (dx * c - dz * s) / p;
+    d[1] = d[1] / h;
+    d[2] = (dx * s + dz * c) / q;
+    d[3] = log(b[3] / l);
+    d[4] = log(b[4] / h);
+    d[5] = log(b[5] / w);
+    d[6] = a / 0.78539816339744830962;
+  }
+#pragma unroll
+  for (int i = 0; i < 7; ++i) out[idx * 7 + i] = (float)d[i];
+}
+
 // ---- augmentation primitives (models/preprocess.py) on float64 points -------
 // The reference's augmentations turn the float32 cloud into float64 with the
 // first `xyz.dot(R.T)` and keep it there until train.py:124 casts back; the
@@ -421,7 +461,8 @@ int assign_impl(const T *xyz, int64_t n_points, const double *label_records,
 template <typename T>
 int encode64_impl(const int32_t *cls_labels, const T *xyz, const double *boxes,
                   const double *class_table, int32_t n_table, int64_t n_rows,
-                  int32_t boxes_per_row, float *encoded, hipStream_t stream) {
+                  int32_t boxes_per_row, float *encoded, hipStream_t stream,
+                  bool canonical = false) {
   PGNN_REQUIRE(n_rows >= 0 && boxes_per_row > 0 && n_table >= 0,
                PGNN_E_INVALID, "box_encode_f64: bad size");
   if (n_rows == 0) return 0;
@@ -429,7 +470,8 @@ int encode64_impl(const int32_t *cls_labels, const T *xyz, const double *boxes,
                    (class_table || n_table == 0),
                PGNN_E_INVALID, "box_encode_f64: null pointer");
   const int64_t total = n_rows * boxes_per_row;
-  hipLaunchKernelGGL(box_encode_f64_kernel<T>,
+  hipLaunchKernelGGL(canonical ? box_encode_canonical_f64_kernel<T>
+                               : box_encode_f64_kernel<T>,
                      dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                      stream, cls_labels, xyz, boxes, class_table, n_table,
                      n_rows, boxes_per_row, encoded);
@@ -481,5 +523,25 @@ extern "C" int pgnn_box_encode_f64_xyz64(const int32_t *cls_labels,
   PGNN_GUARD_BEGIN
   return encode64_impl(cls_labels, xyz, boxes, class_table, n_table, n_rows,
                        boxes_per_row, encoded, (hipStream_t)stream_);
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_box_encode_canonical_f64(
+    const int32_t *cls_labels, const float *xyz, const double *boxes,
+    const double *class_table, int32_t n_table, int64_t n_rows,
+    int32_t boxes_per_row, float *encoded, void *stream_) {
+  PGNN_GUARD_BEGIN
+  return encode64_impl(cls_labels, xyz, boxes, class_table, n_table, n_rows,
+                       boxes_per_row, encoded, (hipStream_t)stream_, true);
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_box_encode_canonical_f64_xyz64(
+    const int32_t *cls_labels, const double *xyz, const double *boxes,
+    const double *class_table, int32_t n_table, int64_t n_rows,
+    int32_t boxes_per_row, float *encoded, void *stream_) {
+  PGNN_GUARD_BEGIN
+  return encode64_impl(cls_labels, xyz, boxes, class_table, n_table, n_rows,
+                       boxes_per_row, encoded, (hipStream_t)stream_, true);
   PGNN_GUARD_END
 }

@@ -256,9 +256,10 @@ def detect_candidates_deferred(probs, box_encodings, last_layer_points_xyz,
                                appr_factor=100.0, top_k=-1):
     """The tail of detect_boxes for candidates that are already selected
     (idx, labels: the first n entries select_candidates[_dyn] wrote, n known
-    to the host), with nothing read back: decode the candidates' boxes -- the
-    codec is per box, so decoding the selection equals selecting from the
-    decoded whole --, run the NMS variant, and return ((class_labels,
+    to the host), with nothing read back: decode the candidates' boxes -- both
+    codecs of the registry (plain and canonical) are per box, so decoding the
+    selection equals selecting from the decoded whole --, run the NMS variant,
+    and return ((class_labels,
     boxes_3d, scores, nms_indices) with n rows each, kept count [1] on the
     device, candidate_xyz [n,3])."""
     import torch
