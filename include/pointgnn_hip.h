@@ -1483,6 +1483,59 @@ int pgnn_points_compact_f64(const double *xyz, const float *attr,
                             double *out_xyz, float *out_attr, int64_t capacity,
                             int32_t *out_count, void *stream);
 
+/* crop_aug object pasting: the trial search of parser_without_collision
+ * (models/crop_aug.py:75-186) for one frame in ONE launch of one workgroup.
+ * Device inputs: the float64 base cloud base_xyz [n_base,3]; the sampled
+ * objects' points sample_xyz [n_sample_points,3] with sample_offsets
+ * [n_samples+1] (0 = off[0] <= ... <= off[S] = n_sample_points; anything else
+ * is reported, see below, and nothing is written); their boxes sample_boxes
+ * [n_samples,7] (x,y,z,l,h,w,yaw); the labels' integer corner grids
+ * label_corners [n_labels,8,3] = np.int32(appr_factor *
+ * boxes_3d_to_corners(.)) (:87-92; not read in 'point' mode); and the draw
+ * table draws [n_samples*max_trails,3] = (delta_yaw, cos, sin) in the order
+ * NumPy's stream yields them.  expand_factor_3 is a HOST pointer.
+ * overlap_mode: 0 'box', 1 'point', 2 'box_and_point' (:131-164).
+ *
+ * Samples and trials are walked in the reference's order; draw k goes to the
+ * k-th trial actually run (one flat cursor).  A trial turns the centre by the
+ * drawn yaw (:104-113); with auto_box_height it takes the largest y among the
+ * alive points strictly inside the box's y/z normals (sel_xyz_in_box2d,
+ * kitti_dataset.py:164-182) as the ground, y3d += ground - y3d (:114-127; no
+ * such point: the trial is spent under must_have_ground, else no lift); the
+ * box test is overlapped_boxes_3d_fast_poly (nms.py:64-88) of the trial's
+ * integer corner grid against every label and every box accepted so far, all
+ * `< max_overlap_rate`; the point test is `count of alive points strictly
+ * inside the expanded box < max_overlap_num_allowed`.  Accepted: those points
+ * die, the sample's points come alive turned by the drawn yaw (and lifted).
+ *
+ * Outputs (device): work_xyz [n_sample_points+n_base,3] = [block of sample
+ * S-1, ..., block of sample 0, base cloud] with alive [.] int32 flags --
+ * pgnn_points_compact_f64 with keep = alive yields the reference's cloud, each
+ * accepted object in front of what was there (:172-175); record
+ * [3*n_samples+2] float64 = per sample (accepted, index of the accepting draw
+ * or -1, ground height or NaN), then the draws consumed and the number of alive
+ * rows (both -1 for a bad offset table).  cand_xyz [rows,3] / cand_idx [rows]
+ * are scratch of the same row count: per sample, the alive rows whose distance
+ * from the y axis is within the footprint's half diagonal of the centre's --
+ * the only ones a trial's box can hold, since a trial turns the box about that
+ * axis -- are gathered once and the trials read those.  Float64 throughout, no contraction;
+ * max and counts are order-independent.  Every loop is bounded by n_samples *
+ * (max_trails + 1) * ceil(rows / 512); one workgroup, so none waits for another.
+ * PGNN_E_UNSUPPORTED: n_labels + n_samples > 256 outside 'point' mode (the
+ * boxes live in LDS), 2^30 rows or draws.  No host synchronisation. */
+int pgnn_crop_aug_place(const double *base_xyz, int64_t n_base,
+                        const double *sample_xyz,
+                        const int32_t *sample_offsets, int32_t n_samples,
+                        int64_t n_sample_points, const double *sample_boxes,
+                        const int32_t *label_corners, int32_t n_labels,
+                        const double *draws, int32_t max_trails,
+                        int32_t overlap_mode, int32_t auto_box_height,
+                        int32_t must_have_ground, double max_overlap_rate,
+                        double appr_factor, double max_overlap_num_allowed,
+                        const double *expand_factor_3, double *work_xyz,
+                        int32_t *alive, double *cand_xyz, int32_t *cand_idx,
+                        double *record, void *stream);
+
 /* Streaming classification metrics of the training / evaluation loops
  * (train.py:301-368, eval.py:176-245): per class tf.metrics.recall and
  * tf.metrics.precision of argmax(probs) against the labels, and

@@ -467,6 +467,10 @@ _SIGNATURES = {
     "pgnn_points_compact_f64": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_vp, c_vp,
                                         c_vp, c_sz, c_vp, c_vp, c_i64, c_vp,
                                         c_vp]),
+    "pgnn_crop_aug_place": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i64,
+                                    c_vp, c_vp, c_i32, c_vp, c_i32, c_i32,
+                                    c_i32, c_i32, c_f64, c_f64, c_f64, c_vp,
+                                    c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # KITTI frame ingest
     "pgnn_kitti_ingest_workspace_bytes": (c_sz, [c_i64]),
     "pgnn_kitti_cam_points_in_image": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_f64,

@@ -528,6 +528,22 @@ def sel_xyz_in_box3d(label, xyz, expend_factor=(1.0, 1.0, 1.0)):
     return mask.cpu().numpy() if as_numpy else mask
 
 
+def sel_xyz_in_box2d(label, xyz, expend_factor=(1.0, 1.0, 1.0)):
+    """kitti_dataset.py:164-182: the strict predicate on the box's y and z
+    normals only (the column of space above and below the box).  Same kernel
+    as sel_xyz_in_box3d: the height normal's row is zero between infinite
+    bounds, so its test passes for every finite point."""
+    rec = np.zeros((1, 24), np.float64)
+    normals, lower, upper = box3d_to_normals(label, expend_factor)
+    rec[0, 3:9], rec[0, 10:12], rec[0, 13:15] = \
+        normals[1:].reshape(-1), lower[1:], upper[1:]
+    rec[0, 9], rec[0, 12] = -np.inf, np.inf
+    rec[0, 15] = 2.0
+    as_numpy, _, _, _, owner = _assign(xyz, rec, want_boxes=False)
+    mask = owner >= 0
+    return mask.cpu().numpy() if as_numpy else mask
+
+
 def assign_label_to_points(labels, xyz, expend_factor, label_map):
     """The shared body of kitti_dataset.py:1132-1284 -> (cls_labels [K,1],
     boxes_3d [K,1,7] float64, valid_boxes [K,1,1] float32, label_map).

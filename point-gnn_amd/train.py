@@ -262,8 +262,23 @@ _ASSIGN = {'yaw': 'assign_classaware_label_to_points',
                'assign_classaware_ped_and_cyc_label_to_points'}
 
 
+_CROP_SAMPLERS = {}
+
+
+def get_crop_sampler(train_config):
+    """train.py:75-76: the CropAugSampler of train_config['crop_aug'] (None
+    without that key), one per crop_filename."""
+    if 'crop_aug' not in train_config:
+        return None
+    from .crop_aug import CropAugSampler
+    filename = train_config['crop_aug']['crop_filename']
+    if filename not in _CROP_SAMPLERS:
+        _CROP_SAMPLERS[filename] = CropAugSampler(filename)
+    return _CROP_SAMPLERS[filename]
+
+
 def fetch_data(dataset, frame_idx, config, train_config, aug_fn=None,
-               graph_hints=None):
+               graph_hints=None, crop_sampler=None):
     """train.py:78-133 with every per-point step on the device: crop to the
     image, augmentations, training-mode graph, label assignment, box
     encoding.  Returns the 7-tuple `batch_data` / `Trainer.train_step` take
@@ -278,14 +293,24 @@ def fetch_data(dataset, frame_idx, config, train_config, aug_fn=None,
     `graph_hints` (a graph_gen.CountHints kept by the caller across frames):
     the graph -- fan-in cap included -- is built in capacity form and its sizes
     are read ONCE per frame instead of once per keypoint / count / cap stage
-    (same tensors for the same NumPy RNG state)."""
+    (same tensors for the same NumPy RNG state).
+
+    `crop_sampler` (a crop_aug.CropAugSampler): with 'crop_aug' in
+    train_config, objects of its database are pasted into the frame before
+    the augmentations (train.py:82-86); None builds the sampler of
+    train_config['crop_aug']['crop_filename'] once and keeps it."""
     from . import box_encoding, graph_gen, preprocess
     from .run import _input_features
     points = dataset.get_cam_points_in_image_with_rgb(
         frame_idx, config['downsample_by_voxel_size'])
     labels = dataset.get_label(frame_idx)
     if 'crop_aug' in train_config:
-        raise NotImplementedError("crop_aug: no shipped train config uses it")
+        if crop_sampler is None:
+            crop_sampler = get_crop_sampler(train_config)
+        points, labels = crop_sampler.crop_aug(
+            points, labels,
+            sample_rate=train_config['crop_aug']['sample_rate'],
+            parser_kwargs=train_config['crop_aug']['parser_kwargs'])
     if aug_fn is None:
         aug_fn = preprocess.get_data_aug(
             train_config.get('data_aug_configs', []))
@@ -354,6 +379,7 @@ def train_epochs(dataset, config, train_config, trainer=None, max_epoch=None,
             f.endswith('.index') for f in os.listdir(train_dir)):
         trainer.load_checkpoint(train_dir)
     aug_fn = preprocess.get_data_aug(train_config.get('data_aug_configs', []))
+    crop_sampler = get_crop_sampler(train_config)
     n_samples = train_config.get('NUM_TEST_SAMPLE', -1)
     if n_samples is None or n_samples < 0:
         n_samples = dataset.num_files
@@ -390,7 +416,8 @@ def train_epochs(dataset, config, train_config, trainer=None, max_epoch=None,
         def make_batch(b0):
             mine = order[b0 + rank * per_rank:b0 + (rank + 1) * per_rank]
             return batch_data([fetch_data(dataset, int(i), config,
-                                          train_config, aug_fn, graph_hints)
+                                          train_config, aug_fn, graph_hints,
+                                          crop_sampler)
                                for i in mine])
         # the epoch's batches come from a loader thread, two ahead (the
         # reference: a 16-process pool, train.py:430-440); the epoch's frame
