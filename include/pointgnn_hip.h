@@ -1555,6 +1555,83 @@ int pgnn_metrics_update(const float *probs, int64_t ld_probs,
 int pgnn_metrics_compute(const void *state, int32_t n_classes,
                          int32_t n_thresholds, float *out, void *stream);
 
+/* KITTI object-detection average precision of a frame set: the 2D box, the
+ * bird's-eye box and the 3D box, for Car / Pedestrian / Cyclist at the easy /
+ * moderate / hard difficulties, with 11- and 40-point interpolation.  The
+ * protocol (constants, overlaps, cleaning, matching, thresholds, curve) is
+ * stated in full in DESIGN.md section 9.5; these entries implement exactly
+ * that text, in float64.  The reference has no counterpart: its README hands
+ * the result files to an external evaluation program.
+ *
+ * Boxes are rows of PGNN_KITTI_ROW doubles,
+ *   xmin ymin xmax ymax  height width length  x3d y3d z3d  yaw
+ *   truncation occlusion score
+ * (score is read for detections only, truncation and occlusion for ground
+ * truths only), with one int32 name code per box: 0 Car, 1 Pedestrian,
+ * 2 Cyclist, 3 Van, 4 Person_sitting, 5 DontCare, 6 anything else.  Frame f
+ * owns the ground truths gt_offsets[f] .. gt_offsets[f+1]-1 and the detections
+ * det_offsets[f] .. det_offsets[f+1]-1, in file order.
+ *
+ * gt_offsets / det_offsets: HOST arrays of n_frames + 1 int32, starting at 0
+ * and ascending; the entries check them, derive every size from them and copy
+ * them to the workspace in stream order (keep them alive until the stream has
+ * passed the call).  Everything else is a device pointer; box and name
+ * pointers may be NULL when their count is 0.
+ *
+ * Caps, per frame: PGNN_KITTI_MAX_DET detections (the assigned set is a bit
+ * mask of 16 64-bit words per lane in LDS) and PGNN_KITTI_MAX_GT ground
+ * truths; at most PGNN_KITTI_MAX_FRAMES frames.  Beyond a cap:
+ * PGNN_E_UNSUPPORTED with the frame and its counts in pgnn_last_error, nothing
+ * launched and nothing written.  Other argument errors: PGNN_E_INVALID;
+ * workspace too small: PGNN_E_WORKSPACE; both before any HIP call.
+ *
+ * pgnn_kitti_eval_workspace_bytes: bytes for n_frames frames holding n_gt
+ * ground truths, n_det detections and n_pairs = sum over frames of (ground
+ * truths * detections) pairs; 0 for arguments out of range.
+ *
+ * pgnn_kitti_pair_overlaps: overlaps[m * n_pairs + pair_off[f] + i * nd_f + j]
+ * for ground truth i and detection j of frame f (pair_off[f] = the pairs of
+ * the frames before f): m = 0 the 2D, 1 the BEV, 2 the 3D union overlap, 3 the
+ * 2D detection-criterion overlap where ground truth i is a DontCare, else 0.
+ * pgnn_kitti_eval computes the same values once, into its workspace, and every
+ * comparison of the matching reads them from there.
+ *
+ * pgnn_kitti_eval: the number of launches does not depend on n_frames, nothing
+ * is read back, and the outputs are complete when `stream` has passed the
+ * call.  Combination index = (metric * 3 + class) * 3 + difficulty, metric
+ * 0 = 2D, 1 = BEV, 2 = 3D (PGNN_KITTI_COMBOS = 27 combinations):
+ *   precision, recall  [27][41] float64 (precision after the running maximum;
+ *                      entries past n_thresholds, and a quotient whose
+ *                      denominator is 0, are 0)
+ *   counters           [27][41][3] int64: tp, fp, fn at each threshold
+ *   thresholds         [27][41] float64, n_thresholds [27] int32
+ *   n_gt               [27] int64
+ *   ap_r11, ap_r40     [27] float64, in [0, 1]
+ * The counters are sums of integers, so the outputs are the same bits on
+ * every run and every stream.                                               */
+#define PGNN_KITTI_ROW 14
+#define PGNN_KITTI_COMBOS 27
+#define PGNN_KITTI_SAMPLE_PTS 41
+#define PGNN_KITTI_MAX_DET 1024
+#define PGNN_KITTI_MAX_GT 1024
+#define PGNN_KITTI_MAX_FRAMES (1 << 24)
+size_t pgnn_kitti_eval_workspace_bytes(int64_t n_frames, int64_t n_gt,
+                                       int64_t n_det, int64_t n_pairs);
+int pgnn_kitti_pair_overlaps(const int32_t *gt_offsets /* host */,
+                             const int32_t *det_offsets /* host */,
+                             int64_t n_frames, const double *gt_boxes,
+                             const int32_t *gt_names, const double *det_boxes,
+                             void *workspace, size_t workspace_bytes,
+                             double *overlaps, void *stream);
+int pgnn_kitti_eval(const int32_t *gt_offsets /* host */,
+                    const int32_t *det_offsets /* host */, int64_t n_frames,
+                    const double *gt_boxes, const int32_t *gt_names,
+                    const double *det_boxes, const int32_t *det_names,
+                    void *workspace, size_t workspace_bytes, double *precision,
+                    double *recall, int64_t *counters, double *thresholds,
+                    int32_t *n_thresholds, int64_t *n_gt, double *ap_r11,
+                    double *ap_r40, void *stream);
+
 size_t pgnn_kitti_ingest_workspace_bytes(int64_t n_points);
 int pgnn_kitti_cam_points_in_image(
     const float *velo_points, int64_t n_points, const float *velo_to_cam_3x4,

@@ -491,6 +491,12 @@ _SIGNATURES = {
     "pgnn_metrics_update": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32,
                                     c_vp, c_vp]),
     "pgnn_metrics_compute": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp]),
+    # KITTI object AP (offsets are host arrays)
+    "pgnn_kitti_eval_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
+    "pgnn_kitti_pair_overlaps": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                         c_vp, c_sz, c_vp, c_vp]),
+    "pgnn_kitti_eval": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                c_vp, c_sz] + [c_vp] * 9),
 }
 
 _lib = None

@@ -1,0 +1,691 @@
+// KITTI object-detection average precision (2D box, bird's-eye box, 3D box;
+// 11- and 40-point interpolation) of a whole frame set, on the device.  The
+// protocol is DESIGN.md §9.5; every name below (cleaning, matching, thresholds,
+// curve) is a heading there.  All arithmetic is float64.
+//
+// Launch structure (nine launches and two offset uploads, whatever the number
+// of frames; nothing is read back):
+//   prep        per box: the 9 (class, difficulty) cleaning results packed into
+//               one word; zeroes the counters and the score slots
+//   scan        pair_off[f] = sum over earlier frames of n_gt * n_det
+//   pairs       per (ground truth, detection) pair of a frame: the 2D / BEV /
+//               3D union overlaps and the 2D detection-criterion overlap, once;
+//               every later comparison reads these values
+//   pass 1      matching without false positives: wave = frame, lane = one of
+//               the 27 (metric, class, difficulty) combinations; records the
+//               matched scores (one slot per ground truth) and n_gt
+//   sort        per combination, descending (bitonic, one workgroup each)
+//   thresholds  per combination, serial: the <= 41 score thresholds
+//   pass 2      matching with false positives: wave = frame, lane = threshold,
+//               blockIdx.y = combination; int64 atomics into [27][41][3]
+//   finalize    precision, recall, running maximum, AP_R11 and AP_R40
+//
+// Pass 2 puts the thresholds of one (frame, combination) on the lanes of one
+// wave: the loops over ground truths and detections, the cleaning flags, the
+// overlaps and the `> MIN_OVERLAP` test are then the same in every lane (one
+// pair in ~15 passes that test), and only `score < thresh` and the assigned
+// bit differ.  The assigned set is a bit mask in LDS, word-major
+// ([word][lane], 8-byte words: consecutive lanes on consecutive bank pairs, no
+// conflicts), ceil(max detections / 64) words per lane, at most 32 KiB per
+// workgroup of four waves.  Waves stride over frames and add their counts once
+// at the end, so a counter sees one atomic per wave, not one per frame.
+#include "box_overlap.h"
+
+namespace pgnn {
+namespace {
+
+constexpr int kRow = PGNN_KITTI_ROW;
+constexpr int kCombos = PGNN_KITTI_COMBOS;  // [metric][class][difficulty]
+constexpr int kPts = PGNN_KITTI_SAMPLE_PTS;
+constexpr int kMaxDet = PGNN_KITTI_MAX_DET;
+constexpr int kMaxGt = PGNN_KITTI_MAX_GT;
+constexpr int kSortTile = 4096;  // keys of one LDS tile of the sort (32 KiB)
+constexpr int kWaves = 4;        // frames in flight per workgroup (passes 1, 2)
+
+// columns of a box row (PGNN_KITTI_ROW doubles, see the header)
+enum { X0, Y0, X1, Y1, BH, BW, BL, BX, BY, BZ, RY, TRUNC, OCC, SCORE };
+// name codes
+enum { kCar, kPed, kCyc, kVan, kSitting, kDontCare, kOther };
+constexpr int kDontCareBit = 1 << 18;
+
+__device__ __forceinline__ double min_overlap(int c) { return c == 0 ? 0.7 : 0.5; }
+__device__ __forceinline__ double min_height(int d) { return d == 0 ? 40.0 : 25.0; }
+__device__ __forceinline__ double max_occlusion(int d) { return (double)d; }
+__device__ __forceinline__ double max_truncation(int d) {
+  return d == 0 ? 0.15 : (d == 1 ? 0.3 : 0.5);
+}
+
+// §9.5 "Cleaning": ignored_gt / ignored_det in {-1, 0, 1}
+__device__ int clean_gt(const double *r, int name, int c, int d) {
+  const int valid =
+      name == c ? 1
+                : (((c == kCar && name == kVan) || (c == kPed && name == kSitting))
+                       ? 0
+                       : -1);
+  const double height = fabs(r[Y1] - r[Y0]);
+  const bool ignore = r[OCC] > max_occlusion(d) ||
+                      r[TRUNC] > max_truncation(d) || height <= min_height(d);
+  if (valid == 1 && !ignore) return 0;
+  if (valid == 0 || (ignore && valid == 1)) return 1;
+  return -1;
+}
+
+__device__ int clean_det(const double *r, int name, int c, int d) {
+  const double height = fabs(r[Y1] - r[Y0]);
+  if (height < min_height(d)) return 1;
+  return name == c ? 0 : -1;
+}
+
+// flags word of a box: bits [2s, 2s+1], s = class * 3 + difficulty, hold
+// ignored + 1; bit 18 marks a DontCare ground truth
+__device__ __forceinline__ int flag_of(int32_t word, int s) {
+  return ((word >> (2 * s)) & 3) - 1;
+}
+
+__global__ __launch_bounds__(256) void kitti_prep_kernel(
+    const double *__restrict__ gt, const int32_t *__restrict__ gt_names,
+    int64_t n_gt, const double *__restrict__ det,
+    const int32_t *__restrict__ det_names, int64_t n_det,
+    int32_t *__restrict__ gt_flags, int32_t *__restrict__ det_flags,
+    unsigned long long *__restrict__ keys, int64_t n_keys,
+    int64_t *__restrict__ counters, int64_t *__restrict__ n_gt_out,
+    int32_t *__restrict__ n_rec, int64_t total) {
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    if (idx < n_gt) {
+      const double *r = gt + idx * kRow;
+      const int name = gt_names[idx];
+      int32_t w = name == kDontCare ? kDontCareBit : 0;
+      for (int c = 0; c < 3; ++c)
+        for (int d = 0; d < 3; ++d)
+          w |= (clean_gt(r, name, c, d) + 1) << (2 * (c * 3 + d));
+      gt_flags[idx] = w;
+    }
+    if (idx < n_det) {
+      const double *r = det + idx * kRow;
+      const int name = det_names[idx];
+      int32_t w = 0;
+      for (int c = 0; c < 3; ++c)
+        for (int d = 0; d < 3; ++d)
+          w |= (clean_det(r, name, c, d) + 1) << (2 * (c * 3 + d));
+      det_flags[idx] = w;
+    }
+    if (idx < n_keys) keys[idx] = 0ull;
+    if (idx < (int64_t)kCombos * kPts * 3) counters[idx] = 0;
+    if (idx < kCombos) {
+      n_gt_out[idx] = 0;
+      n_rec[idx] = 0;
+    }
+  }
+}
+
+// pair_off[f] = sum_{g < f} n_gt(g) * n_det(g), pair_off[F] = the total; one
+// workgroup, each thread a contiguous run of frames
+__global__ __launch_bounds__(1024) void kitti_scan_kernel(
+    const int32_t *__restrict__ gt_off, const int32_t *__restrict__ det_off,
+    int64_t n_frames, int64_t *__restrict__ pair_off) {
+  __shared__ int64_t part[1024];
+  const int tid = threadIdx.x;
+  const int64_t chunk = (n_frames + 1023) / 1024;
+  int64_t begin = (int64_t)tid * chunk, end = begin + chunk;
+  if (begin > n_frames) begin = n_frames;
+  if (end > n_frames) end = n_frames;
+  int64_t sum = 0;
+  for (int64_t f = begin; f < end; ++f)
+    sum += (int64_t)(gt_off[f + 1] - gt_off[f]) *
+           (int64_t)(det_off[f + 1] - det_off[f]);
+  part[tid] = sum;
+  __syncthreads();
+  for (int s = 1; s < 1024; s <<= 1) {
+    const int64_t v = tid >= s ? part[tid - s] : 0;
+    __syncthreads();
+    part[tid] += v;
+    __syncthreads();
+  }
+  int64_t run = part[tid] - sum;
+  for (int64_t f = begin; f < end; ++f) {
+    pair_off[f] = run;
+    run += (int64_t)(gt_off[f + 1] - gt_off[f]) *
+           (int64_t)(det_off[f + 1] - det_off[f]);
+  }
+  if (tid == 1023) pair_off[n_frames] = part[1023];
+}
+
+// §9.5 "Overlaps": the BEV rectangle of a box row
+__device__ void bev_geom(const double *r, Geom &g) {
+  const double c = cos(r[RY]), s = sin(r[RY]);
+  const double hl = r[BL] / 2, hw = r[BW] / 2;
+  const double dx[4] = {hl, hl, -hl, -hl};
+  const double dz[4] = {hw, -hw, -hw, hw};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    g.px[k] = c * dx[k] + s * dz[k] + r[BX];
+    g.pz[k] = -s * dx[k] + c * dz[k] + r[BZ];
+  }
+}
+
+// planes of the overlap workspace, each n_pairs doubles; a frame's block
+// starts at pair_off[f], row-major [ground truth][detection]
+enum { kOv2d, kOvBev, kOv3d, kOvDontCare };
+
+__global__ __launch_bounds__(256) void kitti_pair_kernel(
+    const int32_t *__restrict__ gt_off, const int32_t *__restrict__ det_off,
+    const int64_t *__restrict__ pair_off, int64_t n_frames,
+    const double *__restrict__ gt, const int32_t *__restrict__ gt_names,
+    const double *__restrict__ det, double *__restrict__ ov, int64_t n_pairs) {
+  for (int64_t f = blockIdx.x; f < n_frames; f += gridDim.x) {
+    const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
+    const int d0 = det_off[f], nd = det_off[f + 1] - d0;
+    const int64_t base = pair_off[f];
+    const int np = ng * nd;  // <= kMaxGt * kMaxDet
+    for (int p = threadIdx.x; p < np; p += blockDim.x) {
+      const int i = p / nd, j = p - i * nd;
+      const double *b = gt + (int64_t)(g0 + i) * kRow;   // ground truth
+      const double *a = det + (int64_t)(d0 + j) * kRow;  // detection
+      // 2D
+      const double w = fmin(a[X1], b[X1]) - fmax(a[X0], b[X0]);
+      const double h = fmin(a[Y1], b[Y1]) - fmax(a[Y0], b[Y0]);
+      double o2 = 0.0, odc = 0.0;
+      if (!(w <= 0.0 || h <= 0.0)) {
+        const double inter = w * h;
+        const double area_a = (a[X1] - a[X0]) * (a[Y1] - a[Y0]);
+        const double area_b = (b[X1] - b[X0]) * (b[Y1] - b[Y0]);
+        o2 = inter / (area_a + area_b - inter);
+        odc = inter / area_a;
+      }
+      if (gt_names[g0 + i] != kDontCare) odc = 0.0;
+      // BEV and 3D
+      Geom ga, gb;
+      bev_geom(a, ga);
+      bev_geom(b, gb);
+      const double inter_bev = clip_area(ga, gb);
+      const double obev =
+          inter_bev / (a[BL] * a[BW] + b[BL] * b[BW] - inter_bev);
+      const double ymax = fmin(a[BY], b[BY]);
+      const double ymin = fmax(a[BY] - a[BH], b[BY] - b[BH]);
+      const double inter_vol = inter_bev * fmax(0.0, ymax - ymin);
+      const double o3 = inter_vol / (a[BH] * a[BL] * a[BW] +
+                                     b[BH] * b[BL] * b[BW] - inter_vol);
+      ov[kOv2d * n_pairs + base + p] = o2;
+      ov[kOvBev * n_pairs + base + p] = obev;
+      ov[kOv3d * n_pairs + base + p] = o3;
+      ov[kOvDontCare * n_pairs + base + p] = odc;
+    }
+  }
+}
+
+// a score as an unsigned key of the same order (-0.0 folded onto +0.0); key 0
+// is the empty slot and sorts last
+__device__ __forceinline__ unsigned long long score_key(double s) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(s + 0.0);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double key_score(unsigned long long k) {
+  const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  return __longlong_as_double((long long)u);
+}
+
+// §9.5 "Matching" of one frame for one (metric, class, difficulty) at one
+// threshold.  kFp = compute_fp.  `mask` is this lane's assigned set: word w at
+// mask[w * 64].  Without kFp the matched scores go to keys[i] (the slot of
+// ground truth i).
+template <bool kFp>
+__device__ void match_frame(int ng, int nd, const int32_t *__restrict__ gfl,
+                            const int32_t *__restrict__ dfl,
+                            const double *__restrict__ drow,
+                            const double *__restrict__ ov,
+                            const double *__restrict__ ov_dc, int s,
+                            double min_ov, double thresh, bool is_2d,
+                            unsigned long long *mask, int words,
+                            unsigned long long *keys, long long &tp,
+                            long long &fp, long long &fn) {
+  for (int w = 0; w < words; ++w) mask[w * 64] = 0ull;
+  for (int i = 0; i < ng; ++i) {
+    const int ig = flag_of(gfl[i], s);
+    if (ig < 0) continue;
+    int det_idx = -1;
+    bool valid = false, assigned_ignored = false;
+    double best = 0.0, max_overlap = 0.0;
+    const double *row = ov + (int64_t)i * nd;
+    for (int j = 0; j < nd; ++j) {
+      const int idj = flag_of(dfl[j], s);
+      if (idj < 0) continue;
+      // every rule of step 3 asks for ov > MIN_OVERLAP
+      const double o = row[j];
+      if (!(o > min_ov)) continue;
+      if ((mask[(j >> 6) * 64] >> (j & 63)) & 1ull) continue;
+      const double sc = drow[(int64_t)j * kRow + SCORE];
+      if (kFp) {
+        if (sc < thresh) continue;
+        if (idj == 0 && (o > max_overlap || assigned_ignored)) {
+          max_overlap = o;
+          det_idx = j;
+          valid = true;
+          assigned_ignored = false;
+        } else if (idj == 1 && !valid) {
+          det_idx = j;
+          valid = true;
+          assigned_ignored = true;
+        }
+      } else if (!valid || sc > best) {
+        det_idx = j;
+        best = sc;
+        valid = true;
+      }
+    }
+    if (det_idx < 0) {
+      if (ig == 0) ++fn;
+    } else {
+      if (!(ig == 1 || flag_of(dfl[det_idx], s) == 1)) {
+        ++tp;
+        if (!kFp)
+          keys[i] = score_key(drow[(int64_t)det_idx * kRow + SCORE]);
+      }
+      mask[(det_idx >> 6) * 64] |= 1ull << (det_idx & 63);
+    }
+  }
+  if (kFp) {
+    for (int j = 0; j < nd; ++j) {
+      if (flag_of(dfl[j], s) != 0) continue;
+      if ((mask[(j >> 6) * 64] >> (j & 63)) & 1ull) continue;
+      if (drow[(int64_t)j * kRow + SCORE] < thresh) continue;
+      ++fp;
+    }
+    if (is_2d) {
+      long long nstuff = 0;
+      for (int i = 0; i < ng; ++i) {
+        if (!(gfl[i] & kDontCareBit)) continue;
+        const double *row = ov_dc + (int64_t)i * nd;
+        for (int j = 0; j < nd; ++j) {
+          if (flag_of(dfl[j], s) != 0) continue;
+          if ((mask[(j >> 6) * 64] >> (j & 63)) & 1ull) continue;
+          if (drow[(int64_t)j * kRow + SCORE] < thresh) continue;
+          if (row[j] > min_ov) {
+            mask[(j >> 6) * 64] |= 1ull << (j & 63);
+            ++nstuff;
+          }
+        }
+      }
+      fp -= nstuff;
+    }
+  }
+}
+
+// blockDim = (64, kWaves): threadIdx.y picks the frame, threadIdx.x < 27 the
+// combination
+__global__ __launch_bounds__(64 * kWaves) void kitti_pass1_kernel(
+    const int32_t *__restrict__ gt_off, const int32_t *__restrict__ det_off,
+    const int64_t *__restrict__ pair_off, int64_t n_frames,
+    const int32_t *__restrict__ gt_flags, const int32_t *__restrict__ det_flags,
+    const double *__restrict__ det, const double *__restrict__ ov,
+    int64_t n_pairs, int words, unsigned long long *__restrict__ keys,
+    int64_t n_pad, int64_t *__restrict__ n_gt_out, int32_t *__restrict__ n_rec) {
+  extern __shared__ unsigned long long lds_mask[];
+  const int combo = threadIdx.x;
+  if (combo >= kCombos) return;  // no barrier below
+  unsigned long long *mask = lds_mask + (size_t)threadIdx.y * words * 64 + combo;
+  const int metric = combo / 9, c = (combo / 3) % 3, s = combo % 9;
+  long long tp = 0, fp = 0, fn = 0, n_gt = 0;
+  for (int64_t f = (int64_t)blockIdx.x * kWaves + threadIdx.y; f < n_frames;
+       f += (int64_t)gridDim.x * kWaves) {
+    const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
+    const int d0 = det_off[f], nd = det_off[f + 1] - d0;
+    for (int i = 0; i < ng; ++i) n_gt += flag_of(gt_flags[g0 + i], s) == 0;
+    match_frame<false>(ng, nd, gt_flags + g0, det_flags + d0,
+                       det + (int64_t)d0 * kRow,
+                       ov + metric * n_pairs + pair_off[f], nullptr, s,
+                       min_overlap(c), 0.0, false, mask, (nd + 63) >> 6,
+                       keys + combo * n_pad + g0, tp, fp, fn);
+  }
+  if (n_gt)
+    atomicAdd((unsigned long long *)n_gt_out + combo, (unsigned long long)n_gt);
+  if (tp) atomicAdd(n_rec + combo, (int)tp);
+}
+
+// Descending bitonic sort of each combination's n_pad keys (a power of two),
+// one workgroup per combination; steps whose stride fits a tile run in LDS.
+__device__ __forceinline__ void bitonic_step(unsigned long long *a, int64_t i,
+                                             int64_t l, bool down) {
+  const unsigned long long x = a[i], y = a[l];
+  if (down ? x < y : x > y) {
+    a[i] = y;
+    a[l] = x;
+  }
+}
+
+__global__ __launch_bounds__(1024) void kitti_sort_kernel(
+    unsigned long long *__restrict__ keys, int64_t n_pad) {
+  __shared__ unsigned long long tile[kSortTile];
+  unsigned long long *a = keys + (int64_t)blockIdx.x * n_pad;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int t = n_pad < kSortTile ? (int)n_pad : kSortTile;
+  // merge size k: the steps of stride >= t in global memory, then those of
+  // stride t/2 .. 1 tile by tile in LDS; the k == t round sorts each tile
+  // from scratch (merge sizes 2 .. t in one visit)
+  for (int64_t k = 2; k <= n_pad; k <<= 1) {
+    if (k < t) continue;  // folded into the k == t round below
+    for (int64_t j = k >> 1; j >= t; j >>= 1) {
+      for (int64_t idx = tid; idx < n_pad / 2; idx += nt) {
+        const int64_t i = ((idx & ~(j - 1)) << 1) | (idx & (j - 1));
+        bitonic_step(a, i, i | j, (i & k) == 0);
+      }
+      __syncthreads();
+    }
+    for (int64_t base = 0; base < n_pad; base += t) {
+      for (int x = tid; x < t; x += nt) tile[x] = a[base + x];
+      __syncthreads();
+      for (int64_t kk = (k == t ? 2 : k); kk <= k; kk <<= 1) {
+        for (int j = (int)(kk < t ? kk >> 1 : t >> 1); j > 0; j >>= 1) {
+          for (int idx = tid; idx < t / 2; idx += nt) {
+            const int i = ((idx & ~(j - 1)) << 1) | (idx & (j - 1));
+            bitonic_step(tile, i, i | j, ((base + i) & kk) == 0);
+          }
+          __syncthreads();
+        }
+      }
+      for (int x = tid; x < t; x += nt) a[base + x] = tile[x];
+      __syncthreads();
+    }
+  }
+}
+
+// §9.5 "Thresholds": one thread per combination
+__global__ void kitti_threshold_kernel(
+    const unsigned long long *__restrict__ keys, int64_t n_pad,
+    const int64_t *__restrict__ n_gt, const int32_t *__restrict__ n_rec,
+    double *__restrict__ thresholds, int32_t *__restrict__ n_thresholds) {
+  const int combo = threadIdx.x;
+  if (combo >= kCombos) return;
+  const unsigned long long *v = keys + combo * n_pad;
+  const int64_t n = n_rec[combo];
+  const double total = (double)n_gt[combo];
+  double current_recall = 0.0;
+  int k = 0;
+  for (int64_t i = 0; i < n && k < kPts; ++i) {
+    const double l = (double)(i + 1) / total;
+    const double r = i < n - 1 ? (double)(i + 2) / total : l;
+    if ((r - current_recall) < (current_recall - l) && i < n - 1) continue;
+    thresholds[combo * kPts + k++] = key_score(v[i]);
+    current_recall += 1.0 / 40.0;
+  }
+  n_thresholds[combo] = k;
+  for (; k < kPts; ++k) thresholds[combo * kPts + k] = 0.0;
+}
+
+// blockDim = (64, kWaves), grid = (frame groups, 27): threadIdx.x is the
+// threshold, threadIdx.y the frame slot, blockIdx.y the combination
+__global__ __launch_bounds__(64 * kWaves) void kitti_pass2_kernel(
+    const int32_t *__restrict__ gt_off, const int32_t *__restrict__ det_off,
+    const int64_t *__restrict__ pair_off, int64_t n_frames,
+    const int32_t *__restrict__ gt_flags, const int32_t *__restrict__ det_flags,
+    const double *__restrict__ det, const double *__restrict__ ov,
+    int64_t n_pairs, int words, const double *__restrict__ thresholds,
+    const int32_t *__restrict__ n_thresholds, int64_t *__restrict__ counters) {
+  extern __shared__ unsigned long long lds_mask[];
+  const int combo = blockIdx.y, t = threadIdx.x;
+  if (t >= n_thresholds[combo] || t >= kPts) return;  // no barrier below
+  unsigned long long *mask = lds_mask + (size_t)threadIdx.y * words * 64 + t;
+  const int metric = combo / 9, c = (combo / 3) % 3, s = combo % 9;
+  const double thresh = thresholds[combo * kPts + t];
+  long long tp = 0, fp = 0, fn = 0;
+  for (int64_t f = (int64_t)blockIdx.x * kWaves + threadIdx.y; f < n_frames;
+       f += (int64_t)gridDim.x * kWaves) {
+    const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
+    const int d0 = det_off[f], nd = det_off[f + 1] - d0;
+    const int64_t base = pair_off[f];
+    match_frame<true>(ng, nd, gt_flags + g0, det_flags + d0,
+                      det + (int64_t)d0 * kRow, ov + metric * n_pairs + base,
+                      ov + kOvDontCare * n_pairs + base, s, min_overlap(c),
+                      thresh, metric == 0, mask, (nd + 63) >> 6, nullptr, tp,
+                      fp, fn);
+  }
+  unsigned long long *out =
+      (unsigned long long *)counters + ((int64_t)combo * kPts + t) * 3;
+  if (tp) atomicAdd(out + 0, (unsigned long long)tp);
+  if (fp) atomicAdd(out + 1, (unsigned long long)fp);
+  if (fn) atomicAdd(out + 2, (unsigned long long)fn);
+}
+
+// §9.5 "Curve and AP": one thread per combination
+__global__ void kitti_finalize_kernel(const int64_t *__restrict__ counters,
+                                      const int32_t *__restrict__ n_thresholds,
+                                      double *__restrict__ precision,
+                                      double *__restrict__ recall,
+                                      double *__restrict__ ap_r11,
+                                      double *__restrict__ ap_r40) {
+  const int combo = threadIdx.x;
+  if (combo >= kCombos) return;
+  const int n = n_thresholds[combo];
+  double *p = precision + combo * kPts, *r = recall + combo * kPts;
+  for (int t = 0; t < kPts; ++t) {
+    const int64_t *k = counters + ((int64_t)combo * kPts + t) * 3;
+    const double tp = (double)k[0], fp = (double)k[1], fn = (double)k[2];
+    // an empty denominator (no detection kept, no ground truth) gives 0
+    p[t] = (t < n && k[0] + k[1] > 0) ? tp / (tp + fp) : 0.0;
+    r[t] = (t < n && k[0] + k[2] > 0) ? tp / (tp + fn) : 0.0;
+  }
+  for (int t = kPts - 2; t >= 0; --t) p[t] = fmax(p[t], p[t + 1]);
+  double s11 = 0.0, s40 = 0.0;
+  for (int t = 0; t < kPts; t += 4) s11 += p[t];
+  for (int t = 1; t < kPts; ++t) s40 += p[t];
+  ap_r11[combo] = s11 / 11.0;
+  ap_r40[combo] = s40 / 40.0;
+}
+
+int64_t next_pow2(int64_t n) {
+  int64_t p = 1;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+struct Sizes {
+  int64_t n_frames, n_gt, n_det, n_pairs, n_pad;
+  int max_det;
+};
+
+struct Workspace {
+  int32_t *gt_off, *det_off, *gt_flags, *det_flags, *n_rec;
+  int64_t *pair_off;
+  double *ov;
+  unsigned long long *keys;
+  size_t bytes;
+};
+
+// lays the workspace out; with base == nullptr only `bytes` is meaningful
+Workspace carve(void *base, size_t size, int64_t n_frames, int64_t n_gt,
+                int64_t n_det, int64_t n_pairs, bool with_eval) {
+  Arena arena(base, base ? size : 0);
+  Workspace w;
+  w.gt_off = arena.take<int32_t>((size_t)n_frames + 1);
+  w.det_off = arena.take<int32_t>((size_t)n_frames + 1);
+  w.pair_off = arena.take<int64_t>((size_t)n_frames + 1);
+  w.gt_flags = w.det_flags = w.n_rec = nullptr;
+  w.ov = nullptr;
+  w.keys = nullptr;
+  if (with_eval) {
+    w.gt_flags = arena.take<int32_t>((size_t)(n_gt > 0 ? n_gt : 1));
+    w.det_flags = arena.take<int32_t>((size_t)(n_det > 0 ? n_det : 1));
+    w.n_rec = arena.take<int32_t>(kCombos);
+    w.ov = arena.take<double>((size_t)(n_pairs > 0 ? n_pairs : 1) * 4);
+    w.keys = arena.take<unsigned long long>((size_t)kCombos *
+                                            (size_t)next_pow2(n_gt));
+  }
+  w.bytes = align_up(arena.used, 256);
+  return w;
+}
+
+// host-side checks shared by the two entries; fills `sz`
+int check_offsets(const char *who, const int32_t *gt_off,
+                  const int32_t *det_off, int64_t n_frames, Sizes *sz) {
+  static thread_local char msg[160];
+  if (n_frames < 0 || n_frames > PGNN_KITTI_MAX_FRAMES) {
+    snprintf(msg, sizeof msg, "%s: n_frames out of range", who);
+    return fail(n_frames < 0 ? PGNN_E_INVALID : PGNN_E_UNSUPPORTED, msg);
+  }
+  if (!gt_off || !det_off) {
+    snprintf(msg, sizeof msg, "%s: null offsets", who);
+    return fail(PGNN_E_INVALID, msg);
+  }
+  if (gt_off[0] != 0 || det_off[0] != 0) {
+    snprintf(msg, sizeof msg, "%s: offsets must start at 0", who);
+    return fail(PGNN_E_INVALID, msg);
+  }
+  sz->n_pairs = 0;
+  sz->max_det = 0;
+  for (int64_t f = 0; f < n_frames; ++f) {
+    const int64_t ng = (int64_t)gt_off[f + 1] - gt_off[f];
+    const int64_t nd = (int64_t)det_off[f + 1] - det_off[f];
+    if (ng < 0 || nd < 0) {
+      snprintf(msg, sizeof msg, "%s: offsets not ascending at frame %lld", who,
+               (long long)f);
+      return fail(PGNN_E_INVALID, msg);
+    }
+    if (ng > kMaxGt || nd > kMaxDet) {
+      snprintf(msg, sizeof msg,
+               "%s: frame %lld has %lld ground truths and %lld detections; "
+               "the caps are %d and %d per frame",
+               who, (long long)f, (long long)ng, (long long)nd, kMaxGt,
+               kMaxDet);
+      return fail(PGNN_E_UNSUPPORTED, msg);
+    }
+    sz->n_pairs += ng * nd;
+    if (nd > sz->max_det) sz->max_det = (int)nd;
+  }
+  sz->n_frames = n_frames;
+  sz->n_gt = gt_off[n_frames];
+  sz->n_det = det_off[n_frames];
+  sz->n_pad = next_pow2(sz->n_gt);
+  return 0;
+}
+
+int upload_and_pairs(const Workspace &w, const Sizes &sz,
+                     const int32_t *gt_off, const int32_t *det_off,
+                     const double *gt, const int32_t *gt_names,
+                     const double *det, double *ov, hipStream_t stream) {
+  const size_t off_bytes = ((size_t)sz.n_frames + 1) * sizeof(int32_t);
+  PGNN_HIP(hipMemcpyAsync(w.gt_off, gt_off, off_bytes, hipMemcpyHostToDevice,
+                          stream));
+  PGNN_HIP(hipMemcpyAsync(w.det_off, det_off, off_bytes, hipMemcpyHostToDevice,
+                          stream));
+  hipLaunchKernelGGL(kitti_scan_kernel, dim3(1), dim3(1024), 0, stream,
+                     w.gt_off, w.det_off, sz.n_frames, w.pair_off);
+  PGNN_HIP(hipGetLastError());
+  if (sz.n_pairs > 0) {
+    const unsigned grid = (unsigned)(sz.n_frames < 8192 ? sz.n_frames : 8192);
+    hipLaunchKernelGGL(kitti_pair_kernel, dim3(grid), dim3(256), 0, stream,
+                       w.gt_off, w.det_off, w.pair_off, sz.n_frames, gt,
+                       gt_names, det, ov, sz.n_pairs);
+    PGNN_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+}  // namespace
+}  // namespace pgnn
+
+extern "C" size_t pgnn_kitti_eval_workspace_bytes(int64_t n_frames,
+                                                  int64_t n_gt, int64_t n_det,
+                                                  int64_t n_pairs) {
+  if (n_frames < 0 || n_frames > PGNN_KITTI_MAX_FRAMES || n_gt < 0 ||
+      n_det < 0 || n_pairs < 0 || n_gt > INT32_MAX || n_det > INT32_MAX ||
+      n_pairs > n_gt * n_det)
+    return 0;
+  return pgnn::carve(nullptr, 0, n_frames, n_gt, n_det, n_pairs, true).bytes;
+}
+
+extern "C" int pgnn_kitti_pair_overlaps(
+    const int32_t *gt_offsets, const int32_t *det_offsets, int64_t n_frames,
+    const double *gt_boxes, const int32_t *gt_names, const double *det_boxes,
+    void *workspace, size_t workspace_bytes, double *overlaps, void *stream_) {
+  PGNN_GUARD_BEGIN
+  hipStream_t stream = (hipStream_t)stream_;
+  pgnn::Sizes sz;
+  if (int rc = pgnn::check_offsets("kitti_pair_overlaps", gt_offsets,
+                                   det_offsets, n_frames, &sz))
+    return rc;
+  PGNN_REQUIRE((sz.n_gt == 0 || (gt_boxes && gt_names)) &&
+                   (sz.n_det == 0 || det_boxes) &&
+                   (sz.n_pairs == 0 || overlaps) && workspace,
+               PGNN_E_INVALID, "kitti_pair_overlaps: null pointer");
+  const pgnn::Workspace w =
+      pgnn::carve(workspace, workspace_bytes, sz.n_frames, sz.n_gt, sz.n_det,
+                  sz.n_pairs, false);
+  PGNN_REQUIRE(w.bytes <= workspace_bytes, PGNN_E_WORKSPACE,
+               "kitti_pair_overlaps: workspace too small");
+  return pgnn::upload_and_pairs(w, sz, gt_offsets, det_offsets, gt_boxes,
+                                gt_names, det_boxes, overlaps, stream);
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_kitti_eval(
+    const int32_t *gt_offsets, const int32_t *det_offsets, int64_t n_frames,
+    const double *gt_boxes, const int32_t *gt_names, const double *det_boxes,
+    const int32_t *det_names, void *workspace, size_t workspace_bytes,
+    double *precision, double *recall, int64_t *counters, double *thresholds,
+    int32_t *n_thresholds, int64_t *n_gt, double *ap_r11, double *ap_r40,
+    void *stream_) {
+  PGNN_GUARD_BEGIN
+  using namespace pgnn;
+  hipStream_t stream = (hipStream_t)stream_;
+  Sizes sz;
+  if (int rc =
+          check_offsets("kitti_eval", gt_offsets, det_offsets, n_frames, &sz))
+    return rc;
+  PGNN_REQUIRE((sz.n_gt == 0 || (gt_boxes && gt_names)) &&
+                   (sz.n_det == 0 || (det_boxes && det_names)),
+               PGNN_E_INVALID, "kitti_eval: null box or name pointer");
+  PGNN_REQUIRE(workspace && precision && recall && counters && thresholds &&
+                   n_thresholds && n_gt && ap_r11 && ap_r40,
+               PGNN_E_INVALID, "kitti_eval: null workspace or output pointer");
+  const Workspace w = carve(workspace, workspace_bytes, sz.n_frames, sz.n_gt,
+                            sz.n_det, sz.n_pairs, true);
+  PGNN_REQUIRE(w.bytes <= workspace_bytes, PGNN_E_WORKSPACE,
+               "kitti_eval: workspace too small");
+
+  const int64_t n_keys = (int64_t)kCombos * sz.n_pad;
+  int64_t total = n_keys;
+  if (sz.n_gt > total) total = sz.n_gt;
+  if (sz.n_det > total) total = sz.n_det;
+  if (total < (int64_t)kCombos * kPts * 3) total = (int64_t)kCombos * kPts * 3;
+  const int64_t prep_blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(kitti_prep_kernel,
+                     dim3((unsigned)(prep_blocks < 4096 ? prep_blocks : 4096)),
+                     dim3(256), 0, stream, gt_boxes, gt_names, sz.n_gt,
+                     det_boxes, det_names, sz.n_det, w.gt_flags, w.det_flags,
+                     w.keys, n_keys, counters, n_gt, w.n_rec, total);
+  PGNN_HIP(hipGetLastError());
+  if (int rc = upload_and_pairs(w, sz, gt_offsets, det_offsets, gt_boxes,
+                                gt_names, det_boxes, w.ov, stream))
+    return rc;
+
+  // passes 1 and 2: kWaves frames per workgroup, waves stride over the rest
+  int words = (sz.max_det + 63) / 64;
+  if (words < 1) words = 1;
+  const size_t lds = (size_t)kWaves * words * 64 * sizeof(unsigned long long);
+  int64_t groups = (sz.n_frames + kWaves - 1) / kWaves;
+  if (groups < 1) groups = 1;
+  const unsigned grid1 = (unsigned)(groups < 2048 ? groups : 2048);
+  const unsigned grid2 = (unsigned)(groups < 256 ? groups : 256);
+  hipLaunchKernelGGL(kitti_pass1_kernel, dim3(grid1), dim3(64, kWaves), lds,
+                     stream, w.gt_off, w.det_off, w.pair_off, sz.n_frames,
+                     w.gt_flags, w.det_flags, det_boxes, w.ov, sz.n_pairs,
+                     words, w.keys, sz.n_pad, n_gt, w.n_rec);
+  PGNN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(kitti_sort_kernel, dim3(kCombos), dim3(1024), 0, stream,
+                     w.keys, sz.n_pad);
+  PGNN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(kitti_threshold_kernel, dim3(1), dim3(64), 0, stream,
+                     w.keys, sz.n_pad, n_gt, w.n_rec, thresholds, n_thresholds);
+  PGNN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(kitti_pass2_kernel, dim3(grid2, kCombos),
+                     dim3(64, kWaves), lds, stream, w.gt_off, w.det_off,
+                     w.pair_off, sz.n_frames, w.gt_flags, w.det_flags,
+                     det_boxes, w.ov, sz.n_pairs, words, thresholds,
+                     n_thresholds, counters);
+  PGNN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(kitti_finalize_kernel, dim3(1), dim3(64), 0, stream,
+                     counters, n_thresholds, precision, recall, ap_r11, ap_r40);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+  PGNN_GUARD_END
+}
