@@ -1684,6 +1684,56 @@ int pgnn_kitti_cam_points_voxel_in_image(
     double *out_xyz, double *out_attr, int32_t attr_dim, int64_t capacity,
     int32_t *out_count, void *stream);
 
+/* ---- beam decimation (scripts/point_cloud_downsample.py:19-53: the inputs of
+ * the sparse-LiDAR experiment, every rate-th scanning line of a scan kept).
+ * The script clusters the elevation cosine of every point into 64 beams with
+ * an UNSEEDED KMeans, so it has no output to match; the clustering here is
+ * DEFINED, a function of the input bits only.
+ * velo_points [n,4] float32 rows (x, y, z, reflectance) on the device.
+ *   cosine (:22-25, :29)  norm = sqrt_f32((x*x + y*y) + z*z), every operation
+ *     float32, round to nearest, no FMA, the root correctly rounded;
+ *     cos = (double)z / (double)norm -- bit for bit the script's NumPy value.
+ *     A row is INVALID when norm == 0 or x, y or z is not finite: it takes no
+ *     part in the clustering and is never kept (the script's KMeans raises).
+ *   quantisation  q = rint(cos * 2^30), ties to even; all clustering runs on
+ *     q, sums are exact integers.  s_0 <= ... <= s_{v-1}: the q of the v valid
+ *     rows, sorted; S_i their exact prefix sums.
+ *   initial centres (farthest-first)  C = {s_0}; n_beams - 1 times:
+ *     d_i = min over c in C of |s_i - c|, the SMALLEST i of maximal d_i joins
+ *     C; a maximal d_i of 0 is status 2.  c_0 <= ... = sorted(C) as float64.
+ *   Lloyd passes  m_j = c_{j-1} + c_j; hi_j = #{i : 2 s_i <= m_{j+1}} for
+ *     j < n_beams - 1, hi_{n_beams-1} = v; cluster j = [hi_{j-1}, hi_j) with
+ *     hi_{-1} = 0 (a point on a midpoint goes to the lower cluster);
+ *     c_j = (double)(S[hi_j] - S[hi_{j-1}]) / (double)(hi_j - hi_{j-1}), an
+ *     empty cluster keeps c_j.  A pass whose every hi_j equals the previous
+ *     pass's ends the loop (status 0; the first pass has no previous one);
+ *     max_iter passes without that is status 3, the centres still valid.
+ *   centers [n_beams] = c_j * 2^-30, ascending.
+ *   info [4] = {v, passes made, status, 0}; status 0 ok, 1: v < n_beams,
+ *     2: fewer than n_beams distinct q, 3: max_iter reached.  With status 1 or
+ *     2 centers are 0, passes 0, and pgnn_beam_select keeps nothing.
+ * pgnn_beam_select (:27-35, :50): ext = [-1, centers, +1]; for i = 0, rate,
+ *   2 rate, ... < n_beams a valid row is kept when (ext[i] + ext[i+1]) / 2 <
+ *   cos < (ext[i+1] + ext[i+2]) / 2 in float64 with the unquantised cos --
+ *   strict, as in the script: a row on a bound is dropped, even at rate 1, and
+ *   the outer bounds are (-1 + c_0) / 2 and (c_last + 1) / 2.  Kept rows are
+ *   copied bit for bit (all four floats) in their original order to
+ *   out_points [n_points,4]; *out_count (device) is their number.  info
+ *   (nullable, device): the info of pgnn_beam_centers.
+ * One workspace size serves both entries.  Both are enqueued on `stream`, no
+ * host read.  PGNN_E_INVALID: n_beams outside 2..64, rate < 1, max_iter < 1,
+ * null pointers.  n_points == 0 gives status 1 and a count of 0. */
+size_t pgnn_beam_workspace_bytes(int64_t n_points);
+int pgnn_beam_centers(const float *velo_points, int64_t n_points,
+                      int32_t n_beams, int32_t max_iter, void *workspace,
+                      size_t workspace_bytes, double *centers /* [n_beams] */,
+                      int32_t *info /* [4] */, void *stream);
+int pgnn_beam_select(const float *velo_points, int64_t n_points,
+                     const double *centers, int32_t n_beams, int32_t rate,
+                     const int32_t *info, void *workspace,
+                     size_t workspace_bytes, float *out_points,
+                     int32_t *out_count, void *stream);
+
 /* ---- diagnostics (not part of the reference-facing surface) -------------- */
 /* Process-wide knobs for benchmarks and tests; see "Conventions".  Keys:
  *   launch shape   scatter_rows_per_wave, scatter_nt, mlp_blocks_per_cu,

@@ -482,6 +482,11 @@ _SIGNATURES = {
     "pgnn_voxel_average_f32": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_vp, c_f64,
                                        c_vp, c_sz, c_vp, c_vp, c_vp, c_i64,
                                        c_vp, c_vp]),
+    "pgnn_beam_workspace_bytes": (c_sz, [c_i64]),
+    "pgnn_beam_centers": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_sz, c_vp,
+                                  c_vp, c_vp]),
+    "pgnn_beam_select": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp,
+                                 c_sz, c_vp, c_vp, c_vp]),
     "pgnn_kitti_cam_points_voxel_in_image_workspace_bytes": (c_sz, [c_i64]),
     "pgnn_kitti_cam_points_voxel_in_image": (
         c_i32, [c_vp, c_i64, c_vp, c_vp, c_f64, c_f64, c_vp, c_i64, c_i64,

@@ -235,7 +235,19 @@ class KittiDataset(object):
 
     def __init__(self, image_dir, point_dir, calib_dir, label_dir=None,
                  index_filename=None, is_training=False, is_raw=False,
-                 difficulty=-100, num_classes=8):
+                 difficulty=-100, num_classes=8, beam_downsample_rate=None,
+                 beam_count=64):
+        """beam_downsample_rate (extension): every method that reads a scan
+        keeps every rate-th of its `beam_count` LiDAR beams first
+        (beam_downsample.downsample, scripts/point_cloud_downsample.py) --
+        the WHOLE scan, before xyz_range, the transform, voxel averaging and
+        the crop, as a dataset read back from the script's output directory
+        behaves."""
+        if beam_downsample_rate is not None:
+            from .beam_downsample import _check_args
+            _check_args(n_beams=beam_count, rate=beam_downsample_rate)
+        self._beam_rate = beam_downsample_rate
+        self._beam_count = beam_count
         if is_raw:
             raise NotImplementedError(
                 "the raw-sequence layout is outside the ingest slice")
@@ -265,11 +277,28 @@ class KittiDataset(object):
         return parse_calib(os.path.join(
             self._calib_dir, self._file_list[frame_idx]) + '.txt')
 
-    def get_velo_points(self, frame_idx, xyz_range=None):
-        """kitti_dataset.py:587-609 -> host Points (the crop runs later)."""
+    def _read_scan(self, frame_idx, on_device=False):
+        """The file's [n,4] float32 rows (kitti_dataset.py:589-592).  With a
+        beam_downsample_rate: the decimated scan -- a CUDA tensor when
+        on_device (the rows stay where the crop wants them), else host rows.
+        The decimation's one host read happens here, on the calling thread."""
         data = np.fromfile(os.path.join(
             self._point_dir, self._file_list[frame_idx]) + '.bin',
             dtype=np.float32).reshape(-1, 4)
+        if self._beam_rate is None:
+            return data
+        import torch
+        from .beam_downsample import downsample_rows
+        dev = _cuda_device(None)
+        v = _stage_upload(data, dev) if data.size else \
+            torch.empty(0, dtype=torch.float32, device=dev)
+        rows = downsample_rows(v.reshape(-1, 4), self._beam_rate,
+                               n_beams=self._beam_count)
+        return rows if on_device else rows.cpu().numpy()
+
+    def get_velo_points(self, frame_idx, xyz_range=None):
+        """kitti_dataset.py:587-609 -> host Points (the crop runs later)."""
+        data = self._read_scan(frame_idx)
         if xyz_range is not None:
             m = np.ones(len(data), bool)
             for axis, (lo, hi) in enumerate(xyz_range):
@@ -306,8 +335,11 @@ class KittiDataset(object):
                                 calib=None, xyz_range=None):
         if calib is None:
             calib = self.get_calib(frame_idx)
-        pts = self.get_velo_points(frame_idx, xyz_range=xyz_range)
-        velo = np.concatenate([pts.xyz, pts.attr], axis=1)
+        if self._beam_rate is not None and xyz_range is None:
+            velo = self._read_scan(frame_idx, on_device=True)
+        else:
+            pts = self.get_velo_points(frame_idx, xyz_range=xyz_range)
+            velo = np.concatenate([pts.xyz, pts.attr], axis=1)
         return cam_points_in_image(
             velo, calib, self._image_shape(frame_idx),
             downsample_voxel_size=downsample_voxel_size)
@@ -325,9 +357,7 @@ class KittiDataset(object):
             calib = self.get_calib(frame_idx)
         if xyz_range is None:
             # the file's [n,4] rows as they are (no split + re-join)
-            velo = np.fromfile(os.path.join(
-                self._point_dir, self._file_list[frame_idx]) + '.bin',
-                dtype=np.float32).reshape(-1, 4)
+            velo = self._read_scan(frame_idx, on_device=True)
         else:
             pts = self.get_velo_points(frame_idx, xyz_range=xyz_range)
             velo = np.concatenate([pts.xyz, pts.attr], axis=1)
