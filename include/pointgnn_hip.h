@@ -1608,7 +1608,39 @@ int pgnn_metrics_compute(const void *state, int32_t n_classes,
  *   n_gt               [27] int64
  *   ap_r11, ap_r40     [27] float64, in [0, 1]
  * The counters are sums of integers, so the outputs are the same bits on
- * every run and every stream.                                               */
+ * every run and every stream.
+ *
+ * pgnn_kitti_eval_ex: pgnn_kitti_eval with two additions (DESIGN.md section
+ * 9.5, "Orientation" and "Overlap table").
+ *   min_overlap   HOST pointer to 9 doubles [metric][class], the bound of
+ *                 `overlap > MIN_OVERLAP` (the DontCare step of the 2D metric
+ *                 reads the 2D row); NULL = the official table, 0.7 / 0.5 / 0.5
+ *                 for every metric, which is what pgnn_kitti_eval uses.  Every
+ *                 entry must be finite and in [0, 1]: else PGNN_E_INVALID.
+ *   gt_alpha, det_alpha   device float64, one observation angle per box, in
+ *                 the order of the box rows.  Both NULL: no orientation, the
+ *                 four outputs below are not touched (and may be NULL), and
+ *                 the launches are those of pgnn_kitti_eval.  Exactly one
+ *                 NULL: PGNN_E_INVALID.
+ *   similarity    [9][41] float64, the 2D metric's [class][difficulty]: the
+ *                 sum over the true positives at each threshold of
+ *                 (1 + cos(alpha_gt - alpha_det)) / 2
+ *   orientation   [9][41] float64: similarity / (tp + fp) (0 past n_thresholds
+ *                 and for an empty denominator), after the running maximum
+ *   aos_r11, aos_r40   [9] float64, the sums of ap_r11 / ap_r40 over orientation
+ * Orientation changes no matching decision: every other output is the same
+ * bits with and without it.  The similarity sums use no floating-point
+ * atomics (each wave of the second pass has its own slot, added in ascending
+ * order), so they too are the same bits on every run and every stream.
+ * pgnn_kitti_eval_ex_workspace_bytes: as pgnn_kitti_eval_workspace_bytes;
+ * with_aos != 0 adds a fifth pair plane and the wave slots (at most
+ * 9 * 1024 * 41 doubles).
+ *
+ * pgnn_kitti_pair_orientation: sim[pair_off[f] + i * nd_f + j] =
+ * (1 + cos(gt_alpha[i] - det_alpha[j])) / 2 where the 2D union overlap of the
+ * pair is > 0, else 0: the plane the evaluation with orientation computes once
+ * into its workspace, in the layout of one plane of pgnn_kitti_pair_overlaps
+ * (and with its workspace).                                                  */
 #define PGNN_KITTI_ROW 14
 #define PGNN_KITTI_COMBOS 27
 #define PGNN_KITTI_SAMPLE_PTS 41
@@ -1631,6 +1663,28 @@ int pgnn_kitti_eval(const int32_t *gt_offsets /* host */,
                     double *recall, int64_t *counters, double *thresholds,
                     int32_t *n_thresholds, int64_t *n_gt, double *ap_r11,
                     double *ap_r40, void *stream);
+size_t pgnn_kitti_eval_ex_workspace_bytes(int64_t n_frames, int64_t n_gt,
+                                          int64_t n_det, int64_t n_pairs,
+                                          int32_t with_aos);
+int pgnn_kitti_eval_ex(const int32_t *gt_offsets /* host */,
+                       const int32_t *det_offsets /* host */, int64_t n_frames,
+                       const double *gt_boxes, const int32_t *gt_names,
+                       const double *det_boxes, const int32_t *det_names,
+                       void *workspace, size_t workspace_bytes,
+                       double *precision, double *recall, int64_t *counters,
+                       double *thresholds, int32_t *n_thresholds, int64_t *n_gt,
+                       double *ap_r11, double *ap_r40, const double *gt_alpha,
+                       const double *det_alpha,
+                       const double *min_overlap /* host */, double *similarity,
+                       double *orientation, double *aos_r11, double *aos_r40,
+                       void *stream);
+int pgnn_kitti_pair_orientation(const int32_t *gt_offsets /* host */,
+                                const int32_t *det_offsets /* host */,
+                                int64_t n_frames, const double *gt_boxes,
+                                const double *det_boxes, const double *gt_alpha,
+                                const double *det_alpha, void *workspace,
+                                size_t workspace_bytes, double *sim,
+                                void *stream);
 
 size_t pgnn_kitti_ingest_workspace_bytes(int64_t n_points);
 int pgnn_kitti_cam_points_in_image(

@@ -502,6 +502,13 @@ _SIGNATURES = {
                                          c_vp, c_sz, c_vp, c_vp]),
     "pgnn_kitti_eval": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                 c_vp, c_sz] + [c_vp] * 9),
+    "pgnn_kitti_eval_ex_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64,
+                                                  c_i32]),
+    "pgnn_kitti_eval_ex": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                   c_vp, c_sz] + [c_vp] * 16),
+    "pgnn_kitti_pair_orientation": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp,
+                                            c_vp, c_vp, c_vp, c_sz, c_vp,
+                                            c_vp]),
 }
 
 _lib = None

@@ -20,6 +20,14 @@
 //               blockIdx.y = combination; int64 atomics into [27][41][3]
 //   finalize    precision, recall, running maximum, AP_R11 and AP_R40
 //
+// Orientation (AOS, the 2D metric only) adds no launch: the pairs kernel writes
+// a fifth plane, sim = (1 + cos(alpha_gt - alpha_det)) / 2 of a pair, pass 2
+// adds the plane's value at every true positive to a float64 per lane, each
+// wave stores its 41 sums into its own slot, and finalize adds the slots in
+// ascending wave index.  The grid depends on the number of frames only, so the
+// sums are the same bits on every run.  All of it hangs on template flags: the
+// kernels without orientation are the code they were before it existed.
+//
 // Pass 2 puts the thresholds of one (frame, combination) on the lanes of one
 // wave: the loops over ground truths and detections, the cleaning flags, the
 // overlaps and the `> MIN_OVERLAP` test are then the same in every lane (one
@@ -48,7 +56,19 @@ enum { X0, Y0, X1, Y1, BH, BW, BL, BX, BY, BZ, RY, TRUNC, OCC, SCORE };
 enum { kCar, kPed, kCyc, kVan, kSitting, kDontCare, kOther };
 constexpr int kDontCareBit = 1 << 18;
 
-__device__ __forceinline__ double min_overlap(int c) { return c == 0 ? 0.7 : 0.5; }
+// MIN_OVERLAP[metric][class], a kernel argument by value; a chain of selects,
+// not an indexed load, since pass 1 has the combination on the lanes
+struct OverlapTable {
+  double v[9];
+};
+__device__ __forceinline__ double min_overlap(const OverlapTable &tab, int metric,
+                                              int c) {
+  const int k = metric * 3 + c;
+  double r = tab.v[0];
+#pragma unroll
+  for (int q = 1; q < 9; ++q) r = k == q ? tab.v[q] : r;
+  return r;
+}
 __device__ __forceinline__ double min_height(int d) { return d == 0 ? 40.0 : 25.0; }
 __device__ __forceinline__ double max_occlusion(int d) { return (double)d; }
 __device__ __forceinline__ double max_truncation(int d) {
@@ -166,13 +186,27 @@ __device__ void bev_geom(const double *r, Geom &g) {
 
 // planes of the overlap workspace, each n_pairs doubles; a frame's block
 // starts at pair_off[f], row-major [ground truth][detection]
-enum { kOv2d, kOvBev, kOv3d, kOvDontCare };
+enum { kOv2d, kOvBev, kOv3d, kOvDontCare, kOvSim };
 
+// kMode: what is written.  kPairOverlaps: the four overlap planes into `ov`;
+// kPairBoth: those and the orientation plane `sim`; kPairSim: `sim` alone.
+enum { kPairOverlaps, kPairBoth, kPairSim };
+
+// §9.5 "Orientation": sim of a pair, 0 unless the 2D union overlap is > 0 (a
+// pair that can become a true positive of the 2D metric has one)
+__device__ __forceinline__ double orientation_term(double o2, double alpha_gt,
+                                                   double alpha_det) {
+  return o2 > 0.0 ? (1.0 + cos(alpha_gt - alpha_det)) / 2.0 : 0.0;
+}
+
+template <int kMode>
 __global__ __launch_bounds__(256) void kitti_pair_kernel(
     const int32_t *__restrict__ gt_off, const int32_t *__restrict__ det_off,
     const int64_t *__restrict__ pair_off, int64_t n_frames,
     const double *__restrict__ gt, const int32_t *__restrict__ gt_names,
-    const double *__restrict__ det, double *__restrict__ ov, int64_t n_pairs) {
+    const double *__restrict__ det, double *__restrict__ ov, int64_t n_pairs,
+    const double *__restrict__ gt_alpha, const double *__restrict__ det_alpha,
+    double *__restrict__ sim) {
   for (int64_t f = blockIdx.x; f < n_frames; f += gridDim.x) {
     const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
     const int d0 = det_off[f], nd = det_off[f + 1] - d0;
@@ -193,6 +227,9 @@ __global__ __launch_bounds__(256) void kitti_pair_kernel(
         o2 = inter / (area_a + area_b - inter);
         odc = inter / area_a;
       }
+      if (kMode != kPairOverlaps)
+        sim[base + p] = orientation_term(o2, gt_alpha[g0 + i], det_alpha[d0 + j]);
+      if (kMode == kPairSim) continue;
       if (gt_names[g0 + i] != kDontCare) odc = 0.0;
       // BEV and 3D
       Geom ga, gb;
@@ -228,8 +265,10 @@ __device__ __forceinline__ double key_score(unsigned long long k) {
 // §9.5 "Matching" of one frame for one (metric, class, difficulty) at one
 // threshold.  kFp = compute_fp.  `mask` is this lane's assigned set: word w at
 // mask[w * 64].  Without kFp the matched scores go to keys[i] (the slot of
-// ground truth i).
-template <bool kFp>
+// ground truth i).  kAos (with kFp only): `sim` is the frame's block of the
+// orientation plane and `similarity` gains sim[i][det_idx] at every true
+// positive; no decision reads either.
+template <bool kFp, bool kAos = false>
 __device__ void match_frame(int ng, int nd, const int32_t *__restrict__ gfl,
                             const int32_t *__restrict__ dfl,
                             const double *__restrict__ drow,
@@ -238,7 +277,9 @@ __device__ void match_frame(int ng, int nd, const int32_t *__restrict__ gfl,
                             double min_ov, double thresh, bool is_2d,
                             unsigned long long *mask, int words,
                             unsigned long long *keys, long long &tp,
-                            long long &fp, long long &fn) {
+                            long long &fp, long long &fn,
+                            const double *__restrict__ sim = nullptr,
+                            double *similarity = nullptr) {
   for (int w = 0; w < words; ++w) mask[w * 64] = 0ull;
   for (int i = 0; i < ng; ++i) {
     const int ig = flag_of(gfl[i], s);
@@ -280,6 +321,7 @@ __device__ void match_frame(int ng, int nd, const int32_t *__restrict__ gfl,
         ++tp;
         if (!kFp)
           keys[i] = score_key(drow[(int64_t)det_idx * kRow + SCORE]);
+        if (kAos) *similarity += sim[(int64_t)i * nd + det_idx];
       }
       mask[(det_idx >> 6) * 64] |= 1ull << (det_idx & 63);
     }
@@ -319,12 +361,14 @@ __global__ __launch_bounds__(64 * kWaves) void kitti_pass1_kernel(
     const int32_t *__restrict__ gt_flags, const int32_t *__restrict__ det_flags,
     const double *__restrict__ det, const double *__restrict__ ov,
     int64_t n_pairs, int words, unsigned long long *__restrict__ keys,
-    int64_t n_pad, int64_t *__restrict__ n_gt_out, int32_t *__restrict__ n_rec) {
+    int64_t n_pad, int64_t *__restrict__ n_gt_out, int32_t *__restrict__ n_rec,
+    const OverlapTable table) {
   extern __shared__ unsigned long long lds_mask[];
   const int combo = threadIdx.x;
   if (combo >= kCombos) return;  // no barrier below
   unsigned long long *mask = lds_mask + (size_t)threadIdx.y * words * 64 + combo;
   const int metric = combo / 9, c = (combo / 3) % 3, s = combo % 9;
+  const double min_ov = min_overlap(table, metric, c);
   long long tp = 0, fp = 0, fn = 0, n_gt = 0;
   for (int64_t f = (int64_t)blockIdx.x * kWaves + threadIdx.y; f < n_frames;
        f += (int64_t)gridDim.x * kWaves) {
@@ -334,7 +378,7 @@ __global__ __launch_bounds__(64 * kWaves) void kitti_pass1_kernel(
     match_frame<false>(ng, nd, gt_flags + g0, det_flags + d0,
                        det + (int64_t)d0 * kRow,
                        ov + metric * n_pairs + pair_off[f], nullptr, s,
-                       min_overlap(c), 0.0, false, mask, (nd + 63) >> 6,
+                       min_ov, 0.0, false, mask, (nd + 63) >> 6,
                        keys + combo * n_pad + g0, tp, fp, fn);
   }
   if (n_gt)
@@ -413,31 +457,49 @@ __global__ void kitti_threshold_kernel(
 }
 
 // blockDim = (64, kWaves), grid = (frame groups, 27): threadIdx.x is the
-// threshold, threadIdx.y the frame slot, blockIdx.y the combination
+// threshold, threadIdx.y the frame slot, blockIdx.y the combination.  kAos:
+// the waves of the nine 2D combinations also sum the orientation plane over
+// their true positives and store the sums at wave_sim[combo][wave][t], wave =
+// blockIdx.x * kWaves + threadIdx.y; a lane past n_thresholds stores nothing.
+template <bool kAos>
 __global__ __launch_bounds__(64 * kWaves) void kitti_pass2_kernel(
     const int32_t *__restrict__ gt_off, const int32_t *__restrict__ det_off,
     const int64_t *__restrict__ pair_off, int64_t n_frames,
     const int32_t *__restrict__ gt_flags, const int32_t *__restrict__ det_flags,
     const double *__restrict__ det, const double *__restrict__ ov,
     int64_t n_pairs, int words, const double *__restrict__ thresholds,
-    const int32_t *__restrict__ n_thresholds, int64_t *__restrict__ counters) {
+    const int32_t *__restrict__ n_thresholds, int64_t *__restrict__ counters,
+    const OverlapTable table, double *__restrict__ wave_sim) {
   extern __shared__ unsigned long long lds_mask[];
   const int combo = blockIdx.y, t = threadIdx.x;
   if (t >= n_thresholds[combo] || t >= kPts) return;  // no barrier below
   unsigned long long *mask = lds_mask + (size_t)threadIdx.y * words * 64 + t;
   const int metric = combo / 9, c = (combo / 3) % 3, s = combo % 9;
   const double thresh = thresholds[combo * kPts + t];
+  const double min_ov = min_overlap(table, metric, c);
   long long tp = 0, fp = 0, fn = 0;
+  double similarity = 0.0;
   for (int64_t f = (int64_t)blockIdx.x * kWaves + threadIdx.y; f < n_frames;
        f += (int64_t)gridDim.x * kWaves) {
     const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
     const int d0 = det_off[f], nd = det_off[f + 1] - d0;
     const int64_t base = pair_off[f];
-    match_frame<true>(ng, nd, gt_flags + g0, det_flags + d0,
-                      det + (int64_t)d0 * kRow, ov + metric * n_pairs + base,
-                      ov + kOvDontCare * n_pairs + base, s, min_overlap(c),
-                      thresh, metric == 0, mask, (nd + 63) >> 6, nullptr, tp,
-                      fp, fn);
+    if (kAos && metric == 0)
+      match_frame<true, true>(
+          ng, nd, gt_flags + g0, det_flags + d0, det + (int64_t)d0 * kRow,
+          ov + base, ov + kOvDontCare * n_pairs + base, s, min_ov, thresh, true,
+          mask, (nd + 63) >> 6, nullptr, tp, fp, fn,
+          ov + kOvSim * n_pairs + base, &similarity);
+    else
+      match_frame<true>(ng, nd, gt_flags + g0, det_flags + d0,
+                        det + (int64_t)d0 * kRow, ov + metric * n_pairs + base,
+                        ov + kOvDontCare * n_pairs + base, s, min_ov, thresh,
+                        metric == 0, mask, (nd + 63) >> 6, nullptr, tp, fp, fn);
+  }
+  if (kAos && metric == 0) {
+    const int64_t waves = (int64_t)gridDim.x * kWaves;
+    const int64_t wave = (int64_t)blockIdx.x * kWaves + threadIdx.y;
+    wave_sim[(combo * waves + wave) * kPts + t] = similarity;
   }
   unsigned long long *out =
       (unsigned long long *)counters + ((int64_t)combo * kPts + t) * 3;
@@ -446,15 +508,58 @@ __global__ __launch_bounds__(64 * kWaves) void kitti_pass2_kernel(
   if (fn) atomicAdd(out + 2, (unsigned long long)fn);
 }
 
-// §9.5 "Curve and AP": one thread per combination
-__global__ void kitti_finalize_kernel(const int64_t *__restrict__ counters,
-                                      const int32_t *__restrict__ n_thresholds,
-                                      double *__restrict__ precision,
-                                      double *__restrict__ recall,
-                                      double *__restrict__ ap_r11,
-                                      double *__restrict__ ap_r40) {
+// §9.5 "Orientation", the curve: blockDim = (64, 9), threadIdx.y = one of the
+// nine 2D combinations, threadIdx.x = threshold.  Each thread adds its
+// threshold's wave slots in ascending wave index (41 neighbouring lanes read
+// neighbouring doubles); thread 0 of a combination then takes the running
+// maximum and the two sums, as for precision.
+__device__ void orientation_curve(const int64_t *__restrict__ counters,
+                                  const int32_t *__restrict__ n_thresholds,
+                                  const double *__restrict__ wave_sim,
+                                  int64_t waves, double *__restrict__ similarity,
+                                  double *__restrict__ orientation,
+                                  double *__restrict__ aos_r11,
+                                  double *__restrict__ aos_r40) {
+  const int combo = threadIdx.y, t = threadIdx.x;
+  const int n = n_thresholds[combo];
+  double *o = orientation + combo * kPts;
+  if (t < kPts) {
+    double sum = 0.0;
+    if (t < n) {
+      const double *slot = wave_sim + (int64_t)combo * waves * kPts + t;
+#pragma unroll 8
+      for (int64_t w = 0; w < waves; ++w) sum += slot[w * kPts];
+    }
+    const int64_t *k = counters + ((int64_t)combo * kPts + t) * 3;
+    similarity[combo * kPts + t] = sum;
+    o[t] = (t < n && k[0] + k[1] > 0) ? sum / ((double)k[0] + (double)k[1]) : 0.0;
+  }
+  __syncthreads();  // every thread of the workgroup arrives
+  if (t != 0) return;
+  for (int q = kPts - 2; q >= 0; --q) o[q] = fmax(o[q], o[q + 1]);
+  double s11 = 0.0, s40 = 0.0;
+  for (int q = 0; q < kPts; q += 4) s11 += o[q];
+  for (int q = 1; q < kPts; ++q) s40 += o[q];
+  aos_r11[combo] = s11 / 11.0;
+  aos_r40[combo] = s40 / 40.0;
+}
+
+// §9.5 "Curve and AP": one thread per combination.  kAos: blockDim = (64, 9)
+// and the orientation curve follows in the same launch.
+template <bool kAos>
+__global__ void kitti_finalize_kernel(
+    const int64_t *__restrict__ counters,
+    const int32_t *__restrict__ n_thresholds, double *__restrict__ precision,
+    double *__restrict__ recall, double *__restrict__ ap_r11,
+    double *__restrict__ ap_r40, const double *__restrict__ wave_sim,
+    int64_t waves, double *__restrict__ similarity,
+    double *__restrict__ orientation, double *__restrict__ aos_r11,
+    double *__restrict__ aos_r40) {
+  if (kAos)
+    orientation_curve(counters, n_thresholds, wave_sim, waves, similarity,
+                      orientation, aos_r11, aos_r40);
   const int combo = threadIdx.x;
-  if (combo >= kCombos) return;
+  if (combo >= kCombos || threadIdx.y != 0) return;
   const int n = n_thresholds[combo];
   double *p = precision + combo * kPts, *r = recall + combo * kPts;
   for (int t = 0; t < kPts; ++t) {
@@ -486,35 +591,49 @@ struct Sizes {
 struct Workspace {
   int32_t *gt_off, *det_off, *gt_flags, *det_flags, *n_rec;
   int64_t *pair_off;
-  double *ov;
+  double *ov, *wave_sim;
   unsigned long long *keys;
   size_t bytes;
 };
 
-// lays the workspace out; with base == nullptr only `bytes` is meaningful
+// workgroups of pass 2 along x: kWaves frames each, at most 256 (the waves
+// stride over the rest), so at most 1 024 waves per combination
+int64_t pass2_groups(int64_t n_frames) {
+  int64_t groups = (n_frames + kWaves - 1) / kWaves;
+  if (groups < 1) groups = 1;
+  return groups < 256 ? groups : 256;
+}
+
+// lays the workspace out; with base == nullptr only `bytes` is meaningful.
+// with_aos: a fifth pair plane and the wave slots [9][waves][41] of pass 2.
 Workspace carve(void *base, size_t size, int64_t n_frames, int64_t n_gt,
-                int64_t n_det, int64_t n_pairs, bool with_eval) {
+                int64_t n_det, int64_t n_pairs, bool with_eval,
+                bool with_aos = false) {
   Arena arena(base, base ? size : 0);
   Workspace w;
   w.gt_off = arena.take<int32_t>((size_t)n_frames + 1);
   w.det_off = arena.take<int32_t>((size_t)n_frames + 1);
   w.pair_off = arena.take<int64_t>((size_t)n_frames + 1);
   w.gt_flags = w.det_flags = w.n_rec = nullptr;
-  w.ov = nullptr;
+  w.ov = w.wave_sim = nullptr;
   w.keys = nullptr;
   if (with_eval) {
     w.gt_flags = arena.take<int32_t>((size_t)(n_gt > 0 ? n_gt : 1));
     w.det_flags = arena.take<int32_t>((size_t)(n_det > 0 ? n_det : 1));
     w.n_rec = arena.take<int32_t>(kCombos);
-    w.ov = arena.take<double>((size_t)(n_pairs > 0 ? n_pairs : 1) * 4);
+    w.ov = arena.take<double>((size_t)(n_pairs > 0 ? n_pairs : 1) *
+                              (with_aos ? 5 : 4));
     w.keys = arena.take<unsigned long long>((size_t)kCombos *
                                             (size_t)next_pow2(n_gt));
+    if (with_aos)
+      w.wave_sim = arena.take<double>(
+          (size_t)9 * (size_t)(pass2_groups(n_frames) * kWaves) * kPts);
   }
   w.bytes = align_up(arena.used, 256);
   return w;
 }
 
-// host-side checks shared by the two entries; fills `sz`
+// host-side checks shared by the entries; fills `sz`
 int check_offsets(const char *who, const int32_t *gt_off,
                   const int32_t *det_off, int64_t n_frames, Sizes *sz) {
   static thread_local char msg[160];
@@ -558,10 +677,34 @@ int check_offsets(const char *who, const int32_t *gt_off,
   return 0;
 }
 
+// the official table, or the caller's 3x3 host doubles after the check that
+// every entry is finite and in [0, 1]
+int overlap_table(const char *who, const double *min_overlap,
+                  OverlapTable *table) {
+  static thread_local char msg[160];
+  static const double official[9] = {0.7, 0.5, 0.5, 0.7, 0.5,
+                                     0.5, 0.7, 0.5, 0.5};
+  const double *src = min_overlap ? min_overlap : official;
+  for (int k = 0; k < 9; ++k) {
+    if (!(src[k] >= 0.0 && src[k] <= 1.0)) {  // false for a NaN as well
+      snprintf(msg, sizeof msg,
+               "%s: min_overlap[%d][%d] = %g is not in [0, 1]", who, k / 3,
+               k % 3, src[k]);
+      return fail(PGNN_E_INVALID, msg);
+    }
+    table->v[k] = src[k];
+  }
+  return 0;
+}
+
+// kMode as kitti_pair_kernel's
+template <int kMode>
 int upload_and_pairs(const Workspace &w, const Sizes &sz,
                      const int32_t *gt_off, const int32_t *det_off,
                      const double *gt, const int32_t *gt_names,
-                     const double *det, double *ov, hipStream_t stream) {
+                     const double *det, double *ov, const double *gt_alpha,
+                     const double *det_alpha, double *sim,
+                     hipStream_t stream) {
   const size_t off_bytes = ((size_t)sz.n_frames + 1) * sizeof(int32_t);
   PGNN_HIP(hipMemcpyAsync(w.gt_off, gt_off, off_bytes, hipMemcpyHostToDevice,
                           stream));
@@ -572,12 +715,134 @@ int upload_and_pairs(const Workspace &w, const Sizes &sz,
   PGNN_HIP(hipGetLastError());
   if (sz.n_pairs > 0) {
     const unsigned grid = (unsigned)(sz.n_frames < 8192 ? sz.n_frames : 8192);
-    hipLaunchKernelGGL(kitti_pair_kernel, dim3(grid), dim3(256), 0, stream,
-                       w.gt_off, w.det_off, w.pair_off, sz.n_frames, gt,
-                       gt_names, det, ov, sz.n_pairs);
+    hipLaunchKernelGGL(kitti_pair_kernel<kMode>, dim3(grid), dim3(256), 0,
+                       stream, w.gt_off, w.det_off, w.pair_off, sz.n_frames, gt,
+                       gt_names, det, ov, sz.n_pairs, gt_alpha, det_alpha, sim);
     PGNN_HIP(hipGetLastError());
   }
   return 0;
+}
+
+// the outputs of an evaluation; the last four only with orientation
+struct EvalOut {
+  double *precision, *recall;
+  int64_t *counters;
+  double *thresholds;
+  int32_t *n_thresholds;
+  int64_t *n_gt;
+  double *ap_r11, *ap_r40, *similarity, *orientation, *aos_r11, *aos_r40;
+};
+
+// the launches of one evaluation, after every check
+template <bool kAos>
+int launch_eval(const Workspace &w, const Sizes &sz, const int32_t *gt_offsets,
+                const int32_t *det_offsets, const double *gt_boxes,
+                const int32_t *gt_names, const double *det_boxes,
+                const int32_t *det_names, const double *gt_alpha,
+                const double *det_alpha, const OverlapTable &table,
+                const EvalOut &o, hipStream_t stream) {
+  const int64_t n_keys = (int64_t)kCombos * sz.n_pad;
+  int64_t total = n_keys;
+  if (sz.n_gt > total) total = sz.n_gt;
+  if (sz.n_det > total) total = sz.n_det;
+  if (total < (int64_t)kCombos * kPts * 3) total = (int64_t)kCombos * kPts * 3;
+  const int64_t prep_blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(kitti_prep_kernel,
+                     dim3((unsigned)(prep_blocks < 4096 ? prep_blocks : 4096)),
+                     dim3(256), 0, stream, gt_boxes, gt_names, sz.n_gt,
+                     det_boxes, det_names, sz.n_det, w.gt_flags, w.det_flags,
+                     w.keys, n_keys, o.counters, o.n_gt, w.n_rec, total);
+  PGNN_HIP(hipGetLastError());
+  if (int rc = upload_and_pairs<kAos ? kPairBoth : kPairOverlaps>(
+          w, sz, gt_offsets, det_offsets, gt_boxes, gt_names, det_boxes, w.ov,
+          gt_alpha, det_alpha, kAos ? w.ov + kOvSim * sz.n_pairs : nullptr,
+          stream))
+    return rc;
+
+  // passes 1 and 2: kWaves frames per workgroup, waves stride over the rest
+  int words = (sz.max_det + 63) / 64;
+  if (words < 1) words = 1;
+  const size_t lds = (size_t)kWaves * words * 64 * sizeof(unsigned long long);
+  int64_t groups = (sz.n_frames + kWaves - 1) / kWaves;
+  if (groups < 1) groups = 1;
+  const unsigned grid1 = (unsigned)(groups < 2048 ? groups : 2048);
+  const unsigned grid2 = (unsigned)pass2_groups(sz.n_frames);
+  hipLaunchKernelGGL(kitti_pass1_kernel, dim3(grid1), dim3(64, kWaves), lds,
+                     stream, w.gt_off, w.det_off, w.pair_off, sz.n_frames,
+                     w.gt_flags, w.det_flags, det_boxes, w.ov, sz.n_pairs,
+                     words, w.keys, sz.n_pad, o.n_gt, w.n_rec, table);
+  PGNN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(kitti_sort_kernel, dim3(kCombos), dim3(1024), 0, stream,
+                     w.keys, sz.n_pad);
+  PGNN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(kitti_threshold_kernel, dim3(1), dim3(64), 0, stream,
+                     w.keys, sz.n_pad, o.n_gt, w.n_rec, o.thresholds,
+                     o.n_thresholds);
+  PGNN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(kitti_pass2_kernel<kAos>, dim3(grid2, kCombos),
+                     dim3(64, kWaves), lds, stream, w.gt_off, w.det_off,
+                     w.pair_off, sz.n_frames, w.gt_flags, w.det_flags,
+                     det_boxes, w.ov, sz.n_pairs, words, o.thresholds,
+                     o.n_thresholds, o.counters, table, w.wave_sim);
+  PGNN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(kitti_finalize_kernel<kAos>, dim3(1),
+                     dim3(64, kAos ? 9 : 1), 0, stream, o.counters,
+                     o.n_thresholds, o.precision, o.recall, o.ap_r11, o.ap_r40,
+                     w.wave_sim, (int64_t)grid2 * kWaves, o.similarity,
+                     o.orientation, o.aos_r11, o.aos_r40);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+}
+
+// checks, then launches; `who` names the entry in the messages
+int eval_entry(const char *who, const int32_t *gt_offsets,
+               const int32_t *det_offsets, int64_t n_frames,
+               const double *gt_boxes, const int32_t *gt_names,
+               const double *det_boxes, const int32_t *det_names,
+               void *workspace, size_t workspace_bytes, const double *gt_alpha,
+               const double *det_alpha, const double *min_overlap,
+               const EvalOut &o, hipStream_t stream) {
+  static thread_local char msg[160];
+  Sizes sz;
+  if (int rc = check_offsets(who, gt_offsets, det_offsets, n_frames, &sz))
+    return rc;
+  const bool aos = gt_alpha && det_alpha;
+  snprintf(msg, sizeof msg, "%s: null box or name pointer", who);
+  PGNN_REQUIRE((sz.n_gt == 0 || (gt_boxes && gt_names)) &&
+                   (sz.n_det == 0 || (det_boxes && det_names)),
+               PGNN_E_INVALID, msg);
+  snprintf(msg, sizeof msg, "%s: null workspace or output pointer", who);
+  PGNN_REQUIRE(workspace && o.precision && o.recall && o.counters &&
+                   o.thresholds && o.n_thresholds && o.n_gt && o.ap_r11 &&
+                   o.ap_r40,
+               PGNN_E_INVALID, msg);
+  snprintf(msg, sizeof msg,
+           "%s: gt_alpha and det_alpha must both be given or both be null",
+           who);
+  PGNN_REQUIRE((gt_alpha != nullptr) == (det_alpha != nullptr), PGNN_E_INVALID,
+               msg);
+  snprintf(msg, sizeof msg, "%s: null orientation output pointer", who);
+  PGNN_REQUIRE(!aos || (o.similarity && o.orientation && o.aos_r11 && o.aos_r40),
+               PGNN_E_INVALID, msg);
+  OverlapTable table;
+  if (int rc = overlap_table(who, min_overlap, &table)) return rc;
+  const Workspace w = carve(workspace, workspace_bytes, sz.n_frames, sz.n_gt,
+                            sz.n_det, sz.n_pairs, true, aos);
+  snprintf(msg, sizeof msg, "%s: workspace too small", who);
+  PGNN_REQUIRE(w.bytes <= workspace_bytes, PGNN_E_WORKSPACE, msg);
+  return aos ? launch_eval<true>(w, sz, gt_offsets, det_offsets, gt_boxes,
+                                 gt_names, det_boxes, det_names, gt_alpha,
+                                 det_alpha, table, o, stream)
+             : launch_eval<false>(w, sz, gt_offsets, det_offsets, gt_boxes,
+                                  gt_names, det_boxes, det_names, nullptr,
+                                  nullptr, table, o, stream);
+}
+
+bool sizes_in_range(int64_t n_frames, int64_t n_gt, int64_t n_det,
+                    int64_t n_pairs) {
+  return !(n_frames < 0 || n_frames > PGNN_KITTI_MAX_FRAMES || n_gt < 0 ||
+           n_det < 0 || n_pairs < 0 || n_gt > INT32_MAX || n_det > INT32_MAX ||
+           n_pairs > n_gt * n_det);
 }
 
 }  // namespace
@@ -586,11 +851,19 @@ int upload_and_pairs(const Workspace &w, const Sizes &sz,
 extern "C" size_t pgnn_kitti_eval_workspace_bytes(int64_t n_frames,
                                                   int64_t n_gt, int64_t n_det,
                                                   int64_t n_pairs) {
-  if (n_frames < 0 || n_frames > PGNN_KITTI_MAX_FRAMES || n_gt < 0 ||
-      n_det < 0 || n_pairs < 0 || n_gt > INT32_MAX || n_det > INT32_MAX ||
-      n_pairs > n_gt * n_det)
-    return 0;
+  if (!pgnn::sizes_in_range(n_frames, n_gt, n_det, n_pairs)) return 0;
   return pgnn::carve(nullptr, 0, n_frames, n_gt, n_det, n_pairs, true).bytes;
+}
+
+extern "C" size_t pgnn_kitti_eval_ex_workspace_bytes(int64_t n_frames,
+                                                     int64_t n_gt,
+                                                     int64_t n_det,
+                                                     int64_t n_pairs,
+                                                     int32_t with_aos) {
+  if (!pgnn::sizes_in_range(n_frames, n_gt, n_det, n_pairs)) return 0;
+  return pgnn::carve(nullptr, 0, n_frames, n_gt, n_det, n_pairs, true,
+                     with_aos != 0)
+      .bytes;
 }
 
 extern "C" int pgnn_kitti_pair_overlaps(
@@ -612,8 +885,35 @@ extern "C" int pgnn_kitti_pair_overlaps(
                   sz.n_pairs, false);
   PGNN_REQUIRE(w.bytes <= workspace_bytes, PGNN_E_WORKSPACE,
                "kitti_pair_overlaps: workspace too small");
-  return pgnn::upload_and_pairs(w, sz, gt_offsets, det_offsets, gt_boxes,
-                                gt_names, det_boxes, overlaps, stream);
+  return pgnn::upload_and_pairs<pgnn::kPairOverlaps>(
+      w, sz, gt_offsets, det_offsets, gt_boxes, gt_names, det_boxes, overlaps,
+      nullptr, nullptr, nullptr, stream);
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_kitti_pair_orientation(
+    const int32_t *gt_offsets, const int32_t *det_offsets, int64_t n_frames,
+    const double *gt_boxes, const double *det_boxes, const double *gt_alpha,
+    const double *det_alpha, void *workspace, size_t workspace_bytes,
+    double *sim, void *stream_) {
+  PGNN_GUARD_BEGIN
+  hipStream_t stream = (hipStream_t)stream_;
+  pgnn::Sizes sz;
+  if (int rc = pgnn::check_offsets("kitti_pair_orientation", gt_offsets,
+                                   det_offsets, n_frames, &sz))
+    return rc;
+  PGNN_REQUIRE((sz.n_gt == 0 || (gt_boxes && gt_alpha)) &&
+                   (sz.n_det == 0 || (det_boxes && det_alpha)) &&
+                   (sz.n_pairs == 0 || sim) && workspace,
+               PGNN_E_INVALID, "kitti_pair_orientation: null pointer");
+  const pgnn::Workspace w =
+      pgnn::carve(workspace, workspace_bytes, sz.n_frames, sz.n_gt, sz.n_det,
+                  sz.n_pairs, false);
+  PGNN_REQUIRE(w.bytes <= workspace_bytes, PGNN_E_WORKSPACE,
+               "kitti_pair_orientation: workspace too small");
+  return pgnn::upload_and_pairs<pgnn::kPairSim>(
+      w, sz, gt_offsets, det_offsets, gt_boxes, nullptr, det_boxes, nullptr,
+      gt_alpha, det_alpha, sim, stream);
   PGNN_GUARD_END
 }
 
@@ -625,67 +925,32 @@ extern "C" int pgnn_kitti_eval(
     int32_t *n_thresholds, int64_t *n_gt, double *ap_r11, double *ap_r40,
     void *stream_) {
   PGNN_GUARD_BEGIN
-  using namespace pgnn;
-  hipStream_t stream = (hipStream_t)stream_;
-  Sizes sz;
-  if (int rc =
-          check_offsets("kitti_eval", gt_offsets, det_offsets, n_frames, &sz))
-    return rc;
-  PGNN_REQUIRE((sz.n_gt == 0 || (gt_boxes && gt_names)) &&
-                   (sz.n_det == 0 || (det_boxes && det_names)),
-               PGNN_E_INVALID, "kitti_eval: null box or name pointer");
-  PGNN_REQUIRE(workspace && precision && recall && counters && thresholds &&
-                   n_thresholds && n_gt && ap_r11 && ap_r40,
-               PGNN_E_INVALID, "kitti_eval: null workspace or output pointer");
-  const Workspace w = carve(workspace, workspace_bytes, sz.n_frames, sz.n_gt,
-                            sz.n_det, sz.n_pairs, true);
-  PGNN_REQUIRE(w.bytes <= workspace_bytes, PGNN_E_WORKSPACE,
-               "kitti_eval: workspace too small");
+  const pgnn::EvalOut out = {precision, recall,  counters, thresholds,
+                             n_thresholds, n_gt, ap_r11,   ap_r40,
+                             nullptr,   nullptr, nullptr,  nullptr};
+  return pgnn::eval_entry("kitti_eval", gt_offsets, det_offsets, n_frames,
+                          gt_boxes, gt_names, det_boxes, det_names, workspace,
+                          workspace_bytes, nullptr, nullptr, nullptr, out,
+                          (hipStream_t)stream_);
+  PGNN_GUARD_END
+}
 
-  const int64_t n_keys = (int64_t)kCombos * sz.n_pad;
-  int64_t total = n_keys;
-  if (sz.n_gt > total) total = sz.n_gt;
-  if (sz.n_det > total) total = sz.n_det;
-  if (total < (int64_t)kCombos * kPts * 3) total = (int64_t)kCombos * kPts * 3;
-  const int64_t prep_blocks = (total + 255) / 256;
-  hipLaunchKernelGGL(kitti_prep_kernel,
-                     dim3((unsigned)(prep_blocks < 4096 ? prep_blocks : 4096)),
-                     dim3(256), 0, stream, gt_boxes, gt_names, sz.n_gt,
-                     det_boxes, det_names, sz.n_det, w.gt_flags, w.det_flags,
-                     w.keys, n_keys, counters, n_gt, w.n_rec, total);
-  PGNN_HIP(hipGetLastError());
-  if (int rc = upload_and_pairs(w, sz, gt_offsets, det_offsets, gt_boxes,
-                                gt_names, det_boxes, w.ov, stream))
-    return rc;
-
-  // passes 1 and 2: kWaves frames per workgroup, waves stride over the rest
-  int words = (sz.max_det + 63) / 64;
-  if (words < 1) words = 1;
-  const size_t lds = (size_t)kWaves * words * 64 * sizeof(unsigned long long);
-  int64_t groups = (sz.n_frames + kWaves - 1) / kWaves;
-  if (groups < 1) groups = 1;
-  const unsigned grid1 = (unsigned)(groups < 2048 ? groups : 2048);
-  const unsigned grid2 = (unsigned)(groups < 256 ? groups : 256);
-  hipLaunchKernelGGL(kitti_pass1_kernel, dim3(grid1), dim3(64, kWaves), lds,
-                     stream, w.gt_off, w.det_off, w.pair_off, sz.n_frames,
-                     w.gt_flags, w.det_flags, det_boxes, w.ov, sz.n_pairs,
-                     words, w.keys, sz.n_pad, n_gt, w.n_rec);
-  PGNN_HIP(hipGetLastError());
-  hipLaunchKernelGGL(kitti_sort_kernel, dim3(kCombos), dim3(1024), 0, stream,
-                     w.keys, sz.n_pad);
-  PGNN_HIP(hipGetLastError());
-  hipLaunchKernelGGL(kitti_threshold_kernel, dim3(1), dim3(64), 0, stream,
-                     w.keys, sz.n_pad, n_gt, w.n_rec, thresholds, n_thresholds);
-  PGNN_HIP(hipGetLastError());
-  hipLaunchKernelGGL(kitti_pass2_kernel, dim3(grid2, kCombos),
-                     dim3(64, kWaves), lds, stream, w.gt_off, w.det_off,
-                     w.pair_off, sz.n_frames, w.gt_flags, w.det_flags,
-                     det_boxes, w.ov, sz.n_pairs, words, thresholds,
-                     n_thresholds, counters);
-  PGNN_HIP(hipGetLastError());
-  hipLaunchKernelGGL(kitti_finalize_kernel, dim3(1), dim3(64), 0, stream,
-                     counters, n_thresholds, precision, recall, ap_r11, ap_r40);
-  PGNN_HIP(hipGetLastError());
-  return 0;
+extern "C" int pgnn_kitti_eval_ex(
+    const int32_t *gt_offsets, const int32_t *det_offsets, int64_t n_frames,
+    const double *gt_boxes, const int32_t *gt_names, const double *det_boxes,
+    const int32_t *det_names, void *workspace, size_t workspace_bytes,
+    double *precision, double *recall, int64_t *counters, double *thresholds,
+    int32_t *n_thresholds, int64_t *n_gt, double *ap_r11, double *ap_r40,
+    const double *gt_alpha, const double *det_alpha, const double *min_overlap,
+    double *similarity, double *orientation, double *aos_r11, double *aos_r40,
+    void *stream_) {
+  PGNN_GUARD_BEGIN
+  const pgnn::EvalOut out = {precision,  recall,      counters, thresholds,
+                             n_thresholds, n_gt,      ap_r11,   ap_r40,
+                             similarity, orientation, aos_r11,  aos_r40};
+  return pgnn::eval_entry("kitti_eval_ex", gt_offsets, det_offsets, n_frames,
+                          gt_boxes, gt_names, det_boxes, det_names, workspace,
+                          workspace_bytes, gt_alpha, det_alpha, min_overlap,
+                          out, (hipStream_t)stream_);
   PGNN_GUARD_END
 }

@@ -11,9 +11,17 @@ hard), with 11- and 40-point interpolation.  The protocol is DESIGN.md §9.5.
     print(result.format())
 
     python -m pointgnn_amd.kitti_eval LABEL_DIR RESULT_DIR [--split FILE] [--json]
+        [--aos] [--alpha-from-box] [--min-overlap official|loose|<9 numbers>]
 
 A label is the dict of `kitti_dataset.read_label_file`; a detection carries
 `score` as well.
+
+Two additions go through `pgnn_kitti_eval_ex`, and only when asked for:
+
+    result = evaluate(gt, det, aos=True)            # orientation similarity
+    result.aos('Car', 'moderate')                   # AOS_R40, beside the 2D AP
+    result = evaluate(gt, det, aos=True, det_alpha='box')   # alpha from the box
+    result = evaluate(gt, det, min_overlap='loose')  # BEV / 3D at .5 / .25 / .25
 """
 import ctypes
 import json
@@ -35,6 +43,13 @@ N_SAMPLE_PTS = 41   # PGNN_KITTI_SAMPLE_PTS
 N_COMBOS = 27       # PGNN_KITTI_COMBOS
 MAX_DET = 1024      # PGNN_KITTI_MAX_DET
 MAX_GT = 1024       # PGNN_KITTI_MAX_GT
+# MIN_OVERLAP[metric][class] (METRICS, CLASSES); the official table is what
+# pgnn_kitti_eval has compiled in
+OFFICIAL_MIN_OVERLAP = ((0.7, 0.5, 0.5),) * 3
+LOOSE_MIN_OVERLAP = ((0.7, 0.5, 0.5), (0.5, 0.25, 0.25), (0.5, 0.25, 0.25))
+# a detection file written without an observation angle carries this alpha;
+# the official rule: one such detection and AOS is not computed
+NO_ALPHA = -10.0
 
 # name codes of the C ABI; names compare case-insensitively
 _NAME_CODES = {'car': 0, 'pedestrian': 1, 'cyclist': 2, 'van': 3,
@@ -68,6 +83,42 @@ def pack_labels(frames):
             names[k] = name_code(lab['name'])
             k += 1
     return offsets, rows, names
+
+
+def pack_alpha(frames):
+    """Lists over frames of label dicts -> float64 [N], the `alpha` fields in
+    the order of `pack_labels`' rows."""
+    return np.array([lab['alpha'] for labels in frames for lab in labels],
+                    np.float64)
+
+
+def alpha_from_box(rows):
+    """The observation angle of packed rows from their 3D box: yaw -
+    atan2(x3d, z3d), float64, not wrapped (only its cosine is used)."""
+    rows = np.asarray(rows, np.float64).reshape(-1, ROW)
+    return rows[:, 10] - np.arctan2(rows[:, 7], rows[:, 9])
+
+
+def min_overlap_table(value):
+    """None / 'official' / 'loose' / a 3x3 array-like (or 9 numbers) ->
+    float64 [3, 3], [metric][class].  The range of the entries is the C
+    entry's check."""
+    if value is None:
+        return np.array(OFFICIAL_MIN_OVERLAP, np.float64)
+    if isinstance(value, str):
+        named = {'official': OFFICIAL_MIN_OVERLAP, 'loose': LOOSE_MIN_OVERLAP}
+        if value.lower() in named:
+            return np.array(named[value.lower()], np.float64)
+        try:
+            value = [float(x) for x in value.split(',')]
+        except ValueError:
+            raise ValueError("min_overlap: 'official', 'loose' or 9 "
+                             "comma-separated numbers, not %r" % (value,))
+    table = np.array(value, np.float64)
+    if table.size != 9:
+        raise ValueError("min_overlap needs 3 x 3 numbers [metric][class], "
+                         "got %d" % table.size)
+    return np.ascontiguousarray(table.reshape(3, 3))
 
 
 def _pair_count(gt_off, det_off):
@@ -105,6 +156,28 @@ def _out_sections():
 
 def output_bytes():
     return _out_sections()[1]
+
+
+# the output buffer of run_packed_ex: the sections above (int32 n_thresholds
+# last) with the orientation outputs of the 2D metric, [class][difficulty]
+_AOS_LAYOUT = (('similarity', np.float64, (3, 3, N_SAMPLE_PTS)),
+               ('orientation', np.float64, (3, 3, N_SAMPLE_PTS)),
+               ('aos_r11', np.float64, (3, 3)),
+               ('aos_r40', np.float64, (3, 3)))
+_EX_LAYOUT = _OUT_LAYOUT[:-1] + _AOS_LAYOUT + _OUT_LAYOUT[-1:]
+
+
+def _sections_of(layout):
+    off, sections = 0, {}
+    for key, dtype, shape in layout:
+        nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        sections[key] = (off, nbytes, dtype, shape)
+        off += nbytes
+    return sections, off
+
+
+def output_bytes_ex():
+    return _sections_of(_EX_LAYOUT)[1]
 
 
 def run_packed(gt, det, out=None, device=None):
@@ -149,6 +222,116 @@ def run_packed(gt, det, out=None, device=None):
         # the host offsets and the device inputs must outlive the launches
         torch.cuda.current_stream().synchronize()
     return out
+
+
+def run_packed_ex(gt, det, gt_alpha=None, det_alpha=None, min_overlap=None,
+                  out=None, device=None):
+    """pgnn_kitti_eval_ex on packed labels.  gt_alpha / det_alpha: float64
+    host arrays, one per row (`pack_alpha`, `alpha_from_box`), both or
+    neither; without them no orientation work is launched and the four
+    orientation sections of `out` are not written.  min_overlap: see
+    `min_overlap_table`.  `out`: a uint8 device tensor of output_bytes_ex()
+    bytes (a new one otherwise).  Returns it; nothing has been read back."""
+    lib = _lib.load()
+    gt_off, gt_rows, gt_names = gt
+    det_off, det_rows, det_names = det
+    if len(gt_off) != len(det_off):
+        raise ValueError("ground truth and detections cover %d and %d frames"
+                         % (len(gt_off) - 1, len(det_off) - 1))
+    if (gt_alpha is None) != (det_alpha is None):
+        raise ValueError("gt_alpha and det_alpha: both or neither")
+    with_aos = gt_alpha is not None
+    table = min_overlap_table(min_overlap)
+    dev = _device(device)
+    sections, total = _sections_of(_EX_LAYOUT)
+    if out is None:
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+    n_frames = len(gt_off) - 1
+    n_pairs = _pair_count(gt_off, det_off)
+    ws_bytes = int(lib.pgnn_kitti_eval_ex_workspace_bytes(
+        n_frames, len(gt_rows), len(det_rows), n_pairs, int(with_aos)))
+    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+    d_gt = torch.from_numpy(gt_rows).to(dev)
+    d_gt_names = torch.from_numpy(gt_names).to(dev)
+    d_det = torch.from_numpy(det_rows).to(dev)
+    d_det_names = torch.from_numpy(det_names).to(dev)
+    d_gt_alpha = d_det_alpha = None
+    if with_aos:
+        d_gt_alpha = _alpha_tensor(gt_alpha, len(gt_rows), 'gt_alpha', dev)
+        d_det_alpha = _alpha_tensor(det_alpha, len(det_rows), 'det_alpha', dev)
+
+    def at(key):
+        return ctypes.c_void_p(out.data_ptr() + sections[key][0])
+
+    def dptr(t):
+        return _lib.ptr(t if t.numel() else None)
+
+    gt_off = np.ascontiguousarray(gt_off, np.int32)
+    det_off = np.ascontiguousarray(det_off, np.int32)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pgnn_kitti_eval_ex(
+            _host_ptr(gt_off), _host_ptr(det_off), n_frames, dptr(d_gt),
+            dptr(d_gt_names), dptr(d_det), dptr(d_det_names), _lib.ptr(ws),
+            ws.numel(), at('precision'), at('recall'), at('counters'),
+            at('thresholds'), at('n_thresholds'), at('n_gt'), at('ap_r11'),
+            at('ap_r40'), _lib.ptr(d_gt_alpha), _lib.ptr(d_det_alpha),
+            _host_ptr(table), at('similarity'), at('orientation'),
+            at('aos_r11'), at('aos_r40'), _lib.stream_ptr()),
+            "pgnn_kitti_eval_ex")
+        # the host offsets and the device inputs must outlive the launches
+        torch.cuda.current_stream().synchronize()
+    return out
+
+
+def _alpha_tensor(alpha, n, what, dev):
+    """One float64 per row on the device; a set without rows still hands the
+    entry a pointer (NULL there means "no orientation")."""
+    alpha = np.ascontiguousarray(alpha, np.float64).reshape(-1)
+    if len(alpha) != n:
+        raise ValueError("%s has %d entries for %d rows" % (what, len(alpha), n))
+    if n == 0:
+        return torch.zeros(1, dtype=torch.float64, device=dev)
+    return torch.from_numpy(alpha).to(dev)
+
+
+def pair_orientation(gt_labels, det_labels, gt_alpha=None, det_alpha=None,
+                     device=None):
+    """pgnn_kitti_pair_orientation -> (sim float64 [n_pairs], pair_off int64
+    [F+1]) in the layout of one plane of `pair_overlaps`: (1 + cos(alpha_gt -
+    alpha_det)) / 2 where the pair's 2D overlap is > 0, else 0.  The alphas
+    default to the labels' `alpha` fields."""
+    lib = _lib.load()
+    gt_off, gt_rows, _ = pack_labels(gt_labels)
+    det_off, det_rows, _ = pack_labels(det_labels)
+    if len(gt_off) != len(det_off):
+        raise ValueError("frame counts differ")
+    if gt_alpha is None:
+        gt_alpha = pack_alpha(gt_labels)
+    if det_alpha is None:
+        det_alpha = pack_alpha(det_labels)
+    dev = _device(device)
+    n_frames = len(gt_off) - 1
+    per_frame = np.diff(gt_off).astype(np.int64) * np.diff(det_off)
+    pair_off = np.concatenate([[0], np.cumsum(per_frame)]).astype(np.int64)
+    n_pairs = int(pair_off[-1])
+    ws_bytes = int(lib.pgnn_kitti_eval_workspace_bytes(
+        n_frames, len(gt_rows), len(det_rows), n_pairs))
+    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+    sim = torch.zeros(n_pairs, dtype=torch.float64, device=dev)
+    d_gt = torch.from_numpy(gt_rows).to(dev)
+    d_det = torch.from_numpy(det_rows).to(dev)
+    d_gt_alpha = _alpha_tensor(gt_alpha, len(gt_rows), 'gt_alpha', dev)
+    d_det_alpha = _alpha_tensor(det_alpha, len(det_rows), 'det_alpha', dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pgnn_kitti_pair_orientation(
+            _host_ptr(gt_off), _host_ptr(det_off), n_frames,
+            _lib.ptr(d_gt if len(gt_rows) else None),
+            _lib.ptr(d_det if len(det_rows) else None), _lib.ptr(d_gt_alpha),
+            _lib.ptr(d_det_alpha), _lib.ptr(ws), ws.numel(),
+            _lib.ptr(sim if n_pairs else None), _lib.stream_ptr()),
+            "pgnn_kitti_pair_orientation")
+        torch.cuda.current_stream().synchronize()
+    return sim.cpu().numpy(), pair_off
 
 
 def pair_overlaps(gt_labels, det_labels, device=None):
@@ -200,25 +383,46 @@ class KittiEvalResult(object):
     """The arrays of pgnn_kitti_eval on the host, indexed [metric][class]
     [difficulty] (METRICS, CLASSES, DIFFICULTIES): precision, recall,
     thresholds [.., 41]; counters [.., 41, 3] (tp, fp, fn); n_thresholds, n_gt,
-    ap_r11, ap_r40 [..]."""
+    ap_r11, ap_r40 [..].  `min_overlap` [metric][class] is the table the run
+    used.  With `has_aos`, the orientation of the 2D metric, [class]
+    [difficulty]: similarity, orientation [.., 41]; aos_r11, aos_r40 [..];
+    without, those arrays are NaN."""
 
-    def __init__(self, arrays, classes=CLASSES):
+    def __init__(self, arrays, classes=CLASSES, has_aos=False,
+                 min_overlap=None):
         for key, _, _ in _OUT_LAYOUT:
             setattr(self, key, arrays[key])
+        self.has_aos = bool(has_aos)
+        for key, _, shape in _AOS_LAYOUT:
+            setattr(self, key, arrays[key] if self.has_aos
+                    else np.full(shape, np.nan))
+        self.min_overlap = min_overlap_table(min_overlap)
         self.classes = tuple(CLASSES[_index(c, CLASSES, 'class')]
                              for c in classes)
 
     @classmethod
-    def from_buffer(cls, out, classes=CLASSES):
-        """One read of the device output buffer."""
+    def from_buffer(cls, out, classes=CLASSES, ex=False, has_aos=False,
+                    min_overlap=None):
+        """One read of the device output buffer: run_packed's, or with `ex`
+        run_packed_ex's (`has_aos`: it ran with alphas)."""
         host = out.cpu().numpy().tobytes()
-        sections, _ = _out_sections()
+        sections, _ = _sections_of(_EX_LAYOUT if ex else _OUT_LAYOUT)
         arrays = {}
         for key, (off, nbytes, dtype, shape) in sections.items():
             arrays[key] = np.frombuffer(
                 host, dtype=dtype, count=nbytes // np.dtype(dtype).itemsize,
                 offset=off).reshape(shape).copy()
-        return cls(arrays, classes)
+        return cls(arrays, classes, has_aos, min_overlap)
+
+    def aos(self, cls, difficulty, points=40):
+        """One average orientation similarity in [0, 1] (NaN without
+        `has_aos`); arguments as `ap`'s."""
+        c = _index(cls, CLASSES, 'class')
+        d = _index(difficulty, DIFFICULTIES, 'difficulty')
+        if points not in (11, 40):
+            raise ValueError("points must be 11 or 40")
+        table = self.aos_r40 if points == 40 else self.aos_r11
+        return float(table[c, d])
 
     def ap(self, metric, cls, difficulty, points=40):
         """One average precision in [0, 1].  metric: '2d' / 'bev' / '3d' (or
@@ -239,7 +443,8 @@ class KittiEvalResult(object):
         """The official tool's report lines, `<class>_<metric> AP: easy
         moderate hard` in percent, for the `points`-point interpolation; with
         `alongside` the other interpolation follows under `<...>_R11` (or
-        `_R40`) names."""
+        `_R40`) names.  With `has_aos`, `<class>_orientation AOS: ...`
+        follows each class's `detection` line."""
         lines = []
         sets = [(points, '')]
         if alongside:
@@ -252,6 +457,11 @@ class KittiEvalResult(object):
                         cls.lower(), rep, suffix, ' '.join(
                             '%.6f' % (100.0 * self.ap(m, cls, d, pts))
                             for d in range(3))))
+                    if m == 0 and self.has_aos:
+                        lines.append('%s_orientation%s AOS: %s' % (
+                            cls.lower(), suffix, ' '.join(
+                                '%.6f' % (100.0 * self.aos(cls, d, pts))
+                                for d in range(3))))
         return '\n'.join(lines)
 
     def to_json(self):
@@ -261,19 +471,47 @@ class KittiEvalResult(object):
                 for pts in (40, 11):
                     out['%s_%s_R%d' % (cls.lower(), rep, pts)] = [
                         100.0 * self.ap(m, cls, d, pts) for d in range(3)]
+            if self.has_aos:
+                for pts in (40, 11):
+                    out['%s_orientation_R%d' % (cls.lower(), pts)] = [
+                        100.0 * self.aos(cls, d, pts) for d in range(3)]
         return out
 
 
-def evaluate(gt_labels, det_labels, classes=CLASSES, device=None):
+def detection_alpha(det_labels, det_rows, source):
+    """The detections' alphas for AOS, or None where the official rule says
+    AOS is not computed.  source 'file': the labels' `alpha`, None if any is
+    -10; 'box': `alpha_from_box` of the packed rows."""
+    if source == 'box':
+        return alpha_from_box(det_rows)
+    if source != 'file':
+        raise ValueError("det_alpha must be 'file' or 'box', not %r"
+                         % (source,))
+    alpha = pack_alpha(det_labels)
+    return None if np.any(alpha == NO_ALPHA) else alpha
+
+
+def evaluate(gt_labels, det_labels, classes=CLASSES, device=None, aos=False,
+             det_alpha='file', min_overlap=None):
     """gt_labels / det_labels: lists, over the same frames, of label lists.
     `classes` picks (and orders) the classes of the report; all three are
-    always computed.  Returns a KittiEvalResult."""
+    always computed.  aos: also the orientation similarity of the 2D metric,
+    ground-truth alpha from the labels, detection alpha by `det_alpha` ('file'
+    or 'box', see `detection_alpha`).  min_overlap: None / 'official' /
+    'loose' / 3x3 [metric][class].  Returns a KittiEvalResult."""
     if len(gt_labels) != len(det_labels):
         raise ValueError("ground truth and detections cover %d and %d frames"
                          % (len(gt_labels), len(det_labels)))
-    out = run_packed(pack_labels(gt_labels), pack_labels(det_labels),
-                     device=device)
-    return KittiEvalResult.from_buffer(out, classes)
+    gt, det = pack_labels(gt_labels), pack_labels(det_labels)
+    if not aos and min_overlap is None:
+        return KittiEvalResult.from_buffer(run_packed(gt, det, device=device),
+                                           classes)
+    alpha_det = detection_alpha(det_labels, det[1], det_alpha) if aos else None
+    has_aos = alpha_det is not None
+    out = run_packed_ex(gt, det, pack_alpha(gt_labels) if has_aos else None,
+                        alpha_det, min_overlap, device=device)
+    return KittiEvalResult.from_buffer(out, classes, True, has_aos,
+                                       min_overlap)
 
 
 def read_result_file(path):
@@ -297,12 +535,13 @@ def read_dirs(label_dir, result_dir, frame_names=None):
 
 
 def evaluate_dirs(label_dir, result_dir, frame_names=None, classes=CLASSES,
-                  device=None):
+                  device=None, aos=False, det_alpha='file', min_overlap=None):
     _, gt, det = read_dirs(label_dir, result_dir, frame_names)
-    return evaluate(gt, det, classes, device)
+    return evaluate(gt, det, classes, device, aos, det_alpha, min_overlap)
 
 
-def evaluate_dataset(dataset, result_dir, classes=CLASSES, device=None):
+def evaluate_dataset(dataset, result_dir, classes=CLASSES, device=None,
+                     aos=False, det_alpha='file', min_overlap=None):
     """Scores `result_dir` (one <frame>.txt per frame, as run.run_dataset
     writes them) against the labels of a KittiDataset, over its frame list."""
     gt, det = [], []
@@ -310,10 +549,10 @@ def evaluate_dataset(dataset, result_dir, classes=CLASSES, device=None):
         gt.append(dataset.get_label(i))
         det.append(read_result_file(os.path.join(
             result_dir, dataset.get_filename(i) + '.txt')))
-    return evaluate(gt, det, classes, device)
+    return evaluate(gt, det, classes, device, aos, det_alpha, min_overlap)
 
 
-def main(argv=None):
+def parse_args(argv=None):
     import argparse
     ap = argparse.ArgumentParser(
         description="KITTI object AP (2D, BEV, 3D) of a result directory")
@@ -324,12 +563,28 @@ def main(argv=None):
                          "file)")
     ap.add_argument('--json', action='store_true',
                     help="print one JSON line after the report")
-    args = ap.parse_args(argv)
+    ap.add_argument('--aos', action='store_true',
+                    help="also the average orientation similarity (2D)")
+    ap.add_argument('--alpha-from-box', action='store_true',
+                    help="with --aos: the detections' alpha is yaw - "
+                         "atan2(x3d, z3d) of their 3D box, not the alpha field")
+    ap.add_argument('--min-overlap', metavar='TABLE', type=min_overlap_table,
+                    default=None,
+                    help="official (default), loose (BEV and 3D at 0.5 / 0.25 "
+                         "/ 0.25) or 9 comma-separated numbers [metric][class]")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
     names = None
     if args.split:
         with open(args.split) as f:
             names = [l.strip() for l in f if l.strip()]
-    result = evaluate_dirs(args.label_dir, args.result_dir, names)
+    result = evaluate_dirs(args.label_dir, args.result_dir, names,
+                           aos=args.aos,
+                           det_alpha='box' if args.alpha_from_box else 'file',
+                           min_overlap=args.min_overlap)
     print(result.format())
     if args.json:
         print(json.dumps(result.to_json()))

@@ -84,16 +84,30 @@ def inside_box_host(label, xyz, _nlu=None, _xyz64=None):
     return inside
 
 
+def box_alpha(yaw, x3d, z3d):
+    """KITTI's observation angle of a box: yaw - atan2(x3d, z3d) in float64,
+    brought into [-pi, pi] by whole turns; a Python float."""
+    a = float(np.float64(yaw) - np.arctan2(np.float64(x3d), np.float64(z3d)))
+    while a > np.pi:
+        a -= 2 * np.pi
+    while a < -np.pi:
+        a += 2 * np.pi
+    return a
+
+
 def detections_to_kitti_labels(class_labels, detection_boxes_3d, box_probs,
                                calib, label_method, candidate_xyz=None,
                                use_box_score=True,
-                               image_size=(1242.0, 375.0), host_only=False):
+                               image_size=(1242.0, 375.0), host_only=False,
+                               write_alpha=False):
     """run.py:360-412.  class_labels [M], detection_boxes_3d [M,7], box_probs
     [M] = the NMS outputs; candidate_xyz [n_candidates,3] = the vertices of
     ALL candidates that entered the NMS (`last_layer_points_xyz[box_indices]`),
     needed for the occlusion rescoring when use_box_score.  Returns the list
     of 16-field tuples the reference writes.  host_only: every argument is a
-    NumPy array and nothing touches the device (inside_box_host)."""
+    NumPy array and nothing touches the device (inside_box_host).
+    write_alpha: field 3 is the observation angle of the box, `box_alpha`,
+    where the reference writes 0 (run.py:407); kitti_eval's AOS reads it."""
     labels = _host(class_labels)
     boxes = _host(detection_boxes_3d)
     probs = _host(box_probs)
@@ -137,7 +151,8 @@ def detections_to_kitti_labels(class_labels, detection_boxes_3d, box_probs,
                 if host_only else \
                 _host(kitti_dataset.sel_xyz_in_box3d(tmp, cand_dev))
             score = (1 + occlusion(tmp, cand_host[inside], nlu)) * score
-        out.append((names[int(labels[i])], -1, -1, 0, clip_xmin, clip_ymin,
+        alpha = box_alpha(yaw, x3d, z3d) if write_alpha else 0
+        out.append((names[int(labels[i])], -1, -1, alpha, clip_xmin, clip_ymin,
                     clip_xmax, clip_ymax, h, w, l, x3d, y3d, z3d, yaw, score))
     return out
 

@@ -59,10 +59,13 @@ def _input_features(config, points):
 
 
 def detect_frame(dataset, frame_idx, model, config, use_box_merge=True,
-                 use_box_score=True, time_dict=None, image_reader=None):
+                 use_box_score=True, time_dict=None, image_reader=None,
+                 write_alpha=False):
     """One iteration of run.py:203-412.  Returns (rows, stages): the KITTI
     rows of the frame and the device tensors of every stage (points, graph,
-    logits, box encodings, probs, NMS outputs) for callers that check them."""
+    logits, box encodings, probs, NMS outputs) for callers that check them.
+    write_alpha: the rows carry the boxes' observation angle, not the
+    reference's 0 (kitti_output.detections_to_kitti_labels)."""
     td = time_dict if time_dict is not None else {}
 
     def lap(key, t_prev):
@@ -110,7 +113,8 @@ def detect_frame(dataset, frame_idx, model, config, use_box_merge=True,
     t = lap('decode box + nms', t)
     rows = kitti_output.detections_to_kitti_labels(
         labels, boxes, scores, calib, config['label_method'],
-        candidate_xyz=cand_xyz, use_box_score=use_box_score)
+        candidate_xyz=cand_xyz, use_box_score=use_box_score,
+        write_alpha=write_alpha)
     lap('kitti rows', t)
     stages = {'points': points, 'calib': calib, 'coords': coords, 'kps': kps,
               'edges': edges, 'logits': logits, 'box_encodings': box_encodings,
@@ -123,7 +127,7 @@ def detect_frame(dataset, frame_idx, model, config, use_box_merge=True,
 def run_dataset(dataset, config, checkpoint_dir, output_dir,
                 frame_indices=None, use_box_merge=True, use_box_score=True,
                 params=None, log=None, image_reader=None, edge_arith='f32',
-                pipelined=True, in_flight=3, prefetch=4):
+                pipelined=True, in_flight=3, prefetch=4, write_alpha=False):
     """run.py:203-433 over `frame_indices` (default: the whole dataset).
     Writes `<output_dir>/data/<frame name>.txt` in the reference's format and
     returns the accumulated `time_dict` (seconds per stage under run.py's
@@ -137,7 +141,10 @@ def run_dataset(dataset, config, checkpoint_dir, output_dir,
     DEVICE time between events for the device stages (they overlap: their sum
     exceeds 'wall') and host time for the others.  pipelined=False is the
     reference's strictly sequential loop, a device synchronisation after
-    every stage."""
+    every stage.
+
+    write_alpha: field 3 of every line is the box's observation angle (what
+    kitti_eval's AOS reads) instead of the reference's 0."""
     model = build_model(config, checkpoint_dir, params, edge_arith)
     if frame_indices is None:
         frame_indices = range(dataset.num_files)
@@ -148,13 +155,13 @@ def run_dataset(dataset, config, checkpoint_dir, output_dir,
             config['graph_gen_method'] == 'multi_level_local_graph_v3':
         n = FramePipeline(dataset, config, model, output_dir, use_box_merge,
                           use_box_score, log, image_reader, in_flight,
-                          prefetch, time_dict).run(frame_indices)
+                          prefetch, time_dict, write_alpha).run(frame_indices)
     else:
         n = 0
         for frame_idx in frame_indices:
             _frame_sequential(dataset, frame_idx, model, config, output_dir,
                               use_box_merge, use_box_score, time_dict,
-                              image_reader, log)
+                              image_reader, log, write_alpha)
             n += 1
     time_dict['frames'] = n
     time_dict['wall'] = time.time() - t_wall
@@ -163,10 +170,10 @@ def run_dataset(dataset, config, checkpoint_dir, output_dir,
 
 def _frame_sequential(dataset, frame_idx, model, config, output_dir,
                       use_box_merge, use_box_score, time_dict, image_reader,
-                      log):
+                      log, write_alpha=False):
     rows, stages = detect_frame(dataset, frame_idx, model, config,
                                 use_box_merge, use_box_score, time_dict,
-                                image_reader)
+                                image_reader, write_alpha)
     t = time.time()
     kitti_output.write_kitti_txt(
         os.path.join(output_dir, 'data',
@@ -210,10 +217,11 @@ class FramePipeline(object):
 
     def __init__(self, dataset, config, model, output_dir, use_box_merge,
                  use_box_score, log, image_reader, in_flight, prefetch,
-                 time_dict):
+                 time_dict, write_alpha=False):
         self.dataset, self.config, self.model = dataset, config, model
         self.output_dir = output_dir
         self.use_box_merge, self.use_box_score = use_box_merge, use_box_score
+        self.write_alpha = write_alpha
         self.log, self.image_reader = log, image_reader
         self.in_flight = max(1, int(in_flight))
         self.prefetch = max(1, int(prefetch))
@@ -341,7 +349,8 @@ class FramePipeline(object):
                 _frame_sequential(self.dataset, f.idx, self.model, self.config,
                                   self.output_dir, self.use_box_merge,
                                   self.use_box_score, self.td,
-                                  self.image_reader, self.log)
+                                  self.image_reader, self.log,
+                                  self.write_alpha)
             finally:
                 self.model.edge_arith = edge_arith
             return
@@ -370,7 +379,7 @@ class FramePipeline(object):
         rows = kitti_output.detections_to_kitti_labels(
             labels, boxes, scores, calib, self.config['label_method'],
             candidate_xyz=cand_xyz, use_box_score=self.use_box_score,
-            host_only=True)
+            host_only=True, write_alpha=self.write_alpha)
         t1 = time.time()
         kitti_output.write_kitti_txt(
             os.path.join(self.output_dir, 'data',
@@ -391,7 +400,7 @@ class FramePipeline(object):
         st = _frame_sequential(self.dataset, frame_indices[0], self.model,
                                self.config, self.output_dir,
                                self.use_box_merge, self.use_box_score, self.td,
-                               self.image_reader, self.log)
+                               self.image_reader, self.log, self.write_alpha)
         self.hints = graph_gen.CountHints().update(
             int(st['coords'][1].shape[0]),
             [int(e.shape[0]) for e in st['edges']])
