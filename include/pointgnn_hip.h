@@ -73,7 +73,16 @@ int pgnn_stream_destroy(void *stream);
  * [0, num_segments) are ignored.  `ids_sorted` != 0 promises that seg_ids is
  * non-decreasing (what the radius-graph builder emits): whole-segment runs
  * are then written with plain stores instead of atomics.  Any order is
- * accepted when ids_sorted == 0.  ld_* are row strides in floats.
+ * accepted when ids_sorted == 0.  ld_* are row strides in floats; pad columns
+ * of `out` (ld_out > n_cols) are left untouched.
+ * One result, one bit pattern: every cell is max(lowest, its rows) + 0.0f,
+ * i.e. TF's initialise-with-lowest-then-max with a zero written as +0.0.  A
+ * segment of only -0.0 gives +0.0 and a segment of only -inf gives the lowest
+ * finite float, whatever ids_sorted, the tunables or the device make of the
+ * row ranges (plain stores and atomics write the same form).  NaN rows are
+ * unspecified, as in TF.  n_cols <= 2048 when n_cols and both strides are
+ * multiples of 4 and both pointers 16-byte aligned, <= 1024 otherwise
+ * (PGNN_E_UNSUPPORTED beyond).
  * Algorithmic bytes: n_rows*n_cols*4 + n_rows*4 + num_segments*n_cols*4. */
 int pgnn_scatter_max_f32(const float *data, int64_t ld_data,
                          const int32_t *seg_ids, int64_t n_rows,

@@ -17,6 +17,18 @@ int g_scatter_rows_per_wave = 0;  // 0 = auto
 int g_scatter_nt = 1;            // non-temporal row loads
 }
 
+namespace pgnn {
+// The one form of a result, whichever way it is written.  The atomic path
+// starts from the lowest() fill and combines `v + 0.0f` through integer
+// max / min: a zero arrives as +0.0 and -inf never gets below lowest().  A
+// whole run written with a plain store takes the same form here, so that the
+// bits of a result depend neither on ids_sorted nor on where the wave ranges
+// happen to end.
+__device__ __forceinline__ float scatter_canon(float v) {
+  return fmaxf(v, kFloatLowest) + 0.0f;
+}
+}  // namespace pgnn
+
 namespace {
 
 template <int VEC>
@@ -38,7 +50,9 @@ struct Vec<4> {
                        fmaxf(a.w, b.w));
   }
   static __device__ __forceinline__ void store(float *p, type v) {
-    *reinterpret_cast<float4 *>(p) = v;
+    *reinterpret_cast<float4 *>(p) =
+        make_float4(pgnn::scatter_canon(v.x), pgnn::scatter_canon(v.y),
+                    pgnn::scatter_canon(v.z), pgnn::scatter_canon(v.w));
   }
   static __device__ __forceinline__ void amax(float *p, type v) {
     pgnn::atomic_max_f32(p + 0, v.x + 0.0f);
@@ -57,7 +71,9 @@ struct Vec<1> {
   static __device__ __forceinline__ type vmax(type a, type b) {
     return fmaxf(a, b);
   }
-  static __device__ __forceinline__ void store(float *p, type v) { *p = v; }
+  static __device__ __forceinline__ void store(float *p, type v) {
+    *p = pgnn::scatter_canon(v);
+  }
   static __device__ __forceinline__ void amax(float *p, type v) {
     pgnn::atomic_max_f32(p, v + 0.0f);
   }
