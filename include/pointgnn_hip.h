@@ -1797,6 +1797,101 @@ int pgnn_beam_select(const float *velo_points, int64_t n_points,
                      size_t workspace_bytes, float *out_points,
                      int32_t *out_count, void *stream);
 
+/* ---- rendering: the frame, its boxes and its graph drawn into an image on
+ * the device (run.py -l 1|2: :152-175 the open3d window, :328-359 the cloud and
+ * the graph edges into the kept vertices, :410-421 cv2.rectangle per detection,
+ * :434-535 the box line sets and the camera image; kitti_dataset.py
+ * boxes_3d_to_line_set :785-822, vis_draw_2d_box, vis_draw_3d_box, vis_points,
+ * vis_graph, vis_point_graph, inspect_points).  There is no display, open3d or
+ * cv2 here: the output is a uint8 RGB image [height, width, 3], row-major,
+ * origin top left.  NOT drawn: text (cv2.putText: no font) and the interactive
+ * 3D window.  The semantics are integer-exact: every step below is an IEEE
+ * float64 + - * / in the order written, a floor, or integer arithmetic.
+ *
+ * canvas   1 <= width, height <= PGNN_RENDER_MAX_DIM (4096).
+ * view     view_m [3][4] and view_d [4] float64 in HOST memory, near float64.
+ *   For a point (x, y, z), float32 or float64 (is_f64), widened to float64:
+ *     hu = ((m00 x + m01 y) + m02 z) + m03, hv and hw from rows 1 and 2,
+ *     depth = ((d0 x + d1 y) + d2 z) + d3.
+ *   A point is VISIBLE when hu, hv, hw and depth are finite and hw >= near;
+ *   its pixel is u = floor(hu / hw), v = floor(hv / hw), compared as float64
+ *   with 0 <= u < width, 0 <= v < height; a point whose pixel is off the
+ *   canvas is not drawn.
+ * points   (pgnn_render_points) a visible point covers [u, u+p) x [v, v+p)
+ *   clipped to the canvas, p = point_size in 1..3.  On each pixel the point
+ *   with the smallest float32(depth) wins (-0 and +0 are equal), among equal
+ *   depths the smallest index.  n_points < 2^30.
+ * segments (pgnn_render_segments) [n, 2, 3]: ends a, b mapped to (hu, hv, hw)
+ *   as above.  A non-finite value drops the segment; hw < near at both ends
+ *   drops it; hw < near at one end (call it a) clips that end:
+ *     t = (near - hw_a) / (hw_b - hw_a), hu_a = hu_a + t (hu_b - hu_a), hv_a
+ *     alike, hw_a = near exactly.
+ *   Each end's pixel is (floor(hu / hw), floor(hv / hw)); a coordinate with
+ *   |value| >= 2^30 (or NaN) drops the segment; the rest is int64.  With
+ *   dx = x1 - x0, dy = y1 - y0, N = max(|dx|, |dy|): N = 0 is the one pixel;
+ *   if |dx| >= |dy| the pixels are x = x0 + k sgn(dx),
+ *   y = y0 + floordiv(2 k dy + N, 2 N) for k = 0..N (floordiv rounds toward
+ *   -inf: a midpoint on a half goes up by one), otherwise with x and y
+ *   swapped.  Each pixel is stamped with a t x t square at offsets
+ *   -floor((t-1)/2) .. floor(t/2) on both axes, t = thickness in 1..3: one
+ *   value for all, or thickness_per_segment (device uint8 [n], then
+ *   `thickness` is ignored; a value outside 1..3 drops that segment).  Pixels
+ *   off the canvas are skipped.  Only the k whose major coordinate lies within
+ *   one pixel of the canvas are visited: the work per segment is bounded by
+ *   the canvas, not by N.  On each pixel the segment with the LARGEST index
+ *   wins, as a later cv2.line overwrites an earlier one.
+ * resolve  (pgnn_render_resolve) per pixel the first that applies: the
+ *   winning segment's colour, the winning point's colour, the background
+ *   (background_image, device uint8 [height, width, 3], or when that is null
+ *   background_rgb = r << 16 | g << 8 | b).  Colours are device uint8 [n, 3];
+ *   n_*_colors == 1 is one colour for the whole layer, otherwise one row per
+ *   primitive (a winner without a row shows the background).
+ * The workspace holds one uint64 key per pixel; pgnn_render_clear empties it,
+ * pgnn_render_points / pgnn_render_segments may then be called any number of
+ * times with the SAME canvas (indices are per call: colours resolve against
+ * the last call of each kind), pgnn_render_resolve writes the image.
+ * pgnn_render_colorize: i = floor((float64(v) - lo) / (hi - lo) * 255) clamped
+ * to 0..255, NaN gives 0; colors [n, 3] = table[i], table device uint8
+ * [256, 3].
+ * pgnn_render_graph_segments (run.py:341-350, vis_graph): segments [n_edges,
+ * 2, 3] float32 = (src_xyz[edges[e][0]], dst_xyz[edges[e][1]]), edges int32
+ * [n_edges, 2]; an index outside its array gives a NaN end (the segment is
+ * dropped when drawn).  Host-sized only.
+ * All entries enqueue on `stream`; none reads back.  PGNN_E_INVALID (nothing
+ * enqueued): width or height outside 1..4096, point_size or thickness outside
+ * 1..3, near not finite, a null pointer with a non-zero count;
+ * PGNN_E_WORKSPACE: workspace_bytes below pgnn_render_workspace_bytes (which
+ * is 0 for a canvas out of range).                                          */
+#define PGNN_RENDER_MAX_DIM 4096
+size_t pgnn_render_workspace_bytes(int32_t width, int32_t height);
+int pgnn_render_clear(int32_t width, int32_t height, void *workspace,
+                      size_t workspace_bytes, void *stream);
+int pgnn_render_points(const void *xyz, int32_t is_f64, int64_t n_points,
+                       const double *view_m /* host [12] */,
+                       const double *view_d /* host [4] */, double near,
+                       int32_t width, int32_t height, int32_t point_size,
+                       void *workspace, size_t workspace_bytes, void *stream);
+int pgnn_render_segments(const void *segments, int32_t is_f64,
+                         int64_t n_segments,
+                         const double *view_m /* host [12] */, double near,
+                         int32_t width, int32_t height,
+                         const uint8_t *thickness_per_segment,
+                         int32_t thickness, void *workspace,
+                         size_t workspace_bytes, void *stream);
+int pgnn_render_resolve(int32_t width, int32_t height, const void *workspace,
+                        size_t workspace_bytes, const uint8_t *point_colors,
+                        int64_t n_point_colors, const uint8_t *segment_colors,
+                        int64_t n_segment_colors,
+                        const uint8_t *background_image,
+                        uint32_t background_rgb, uint8_t *image, void *stream);
+int pgnn_render_colorize(const void *values, int32_t is_f64, int64_t n,
+                         double lo, double hi, const uint8_t *table,
+                         uint8_t *colors, void *stream);
+int pgnn_render_graph_segments(const float *src_xyz, int64_t n_src,
+                               const float *dst_xyz, int64_t n_dst,
+                               const int32_t *edges, int64_t n_edges,
+                               float *segments, void *stream);
+
 /* ---- diagnostics (not part of the reference-facing surface) -------------- */
 /* Process-wide knobs for benchmarks and tests; see "Conventions".  Keys:
  *   launch shape   scatter_rows_per_wave, scatter_nt, mlp_blocks_per_cu,

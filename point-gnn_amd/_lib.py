@@ -509,6 +509,20 @@ _SIGNATURES = {
     "pgnn_kitti_pair_orientation": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp,
                                             c_vp, c_vp, c_vp, c_sz, c_vp,
                                             c_vp]),
+    # rendering (views are host arrays)
+    "pgnn_render_workspace_bytes": (c_sz, [c_i32, c_i32]),
+    "pgnn_render_clear": (c_i32, [c_i32, c_i32, c_vp, c_sz, c_vp]),
+    "pgnn_render_points": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp, c_f64,
+                                   c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
+    "pgnn_render_segments": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_f64, c_i32,
+                                     c_i32, c_vp, c_i32, c_vp, c_sz, c_vp]),
+    "pgnn_render_resolve": (c_i32, [c_i32, c_i32, c_vp, c_sz, c_vp, c_i64,
+                                    c_vp, c_i64, c_vp, ctypes.c_uint32, c_vp,
+                                    c_vp]),
+    "pgnn_render_colorize": (c_i32, [c_vp, c_i32, c_i64, c_f64, c_f64, c_vp,
+                                     c_vp, c_vp]),
+    "pgnn_render_graph_segments": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp,
+                                           c_i64, c_vp, c_vp]),
 }
 
 _lib = None

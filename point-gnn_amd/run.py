@@ -5,7 +5,8 @@ with every stage on the device, and `run_dataset` is the loop with the
 reference's checkpoint restore (:192-201), per-stage `time_dict` (:216-263,
 :326, :412) and `<output_dir>/data/<frame>.txt` files (:414-423).
 
-No session, placeholders, visualisation or command line: `config` is the
+No session, placeholders or command line (the windows of `-l 1|2` are the
+images of pointgnn_amd.render, `run_dataset(render_dir=...)`): `config` is the
 dictionary `util/config_util.load_config` returns for the reference's config
 files, `dataset` a `pointgnn_amd.kitti_dataset.KittiDataset`.
 """
@@ -127,7 +128,8 @@ def detect_frame(dataset, frame_idx, model, config, use_box_merge=True,
 def run_dataset(dataset, config, checkpoint_dir, output_dir,
                 frame_indices=None, use_box_merge=True, use_box_score=True,
                 params=None, log=None, image_reader=None, edge_arith='f32',
-                pipelined=True, in_flight=3, prefetch=4, write_alpha=False):
+                pipelined=True, in_flight=3, prefetch=4, write_alpha=False,
+                render_dir=None, render_views=('bev',)):
     """run.py:203-433 over `frame_indices` (default: the whole dataset).
     Writes `<output_dir>/data/<frame name>.txt` in the reference's format and
     returns the accumulated `time_dict` (seconds per stage under run.py's
@@ -144,7 +146,14 @@ def run_dataset(dataset, config, checkpoint_dir, output_dir,
     every stage.
 
     write_alpha: field 3 of every line is the box's observation angle (what
-    kitti_eval's AOS reads) instead of the reference's 0."""
+    kitti_eval's AOS reads) instead of the reference's 0.
+
+    render_dir: after the frame loop, every frame's cloud, labels (when the
+    dataset has them) and written detections are drawn into
+    `<render_dir>/<view>/<frame name>.png` for each of render_views ('bev',
+    'camera'): render.render_results on the files just written, what
+    run.py -l 1|2 shows in its windows.  The txt files do not depend on it;
+    its time is time_dict['render'], outside 'wall'."""
     model = build_model(config, checkpoint_dir, params, edge_arith)
     if frame_indices is None:
         frame_indices = range(dataset.num_files)
@@ -165,6 +174,13 @@ def run_dataset(dataset, config, checkpoint_dir, output_dir,
             n += 1
     time_dict['frames'] = n
     time_dict['wall'] = time.time() - t_wall
+    if render_dir is not None:
+        from . import render
+        t_render = time.time()
+        render.render_results(dataset, os.path.join(output_dir, 'data'),
+                              render_dir, views=render_views,
+                              frame_indices=frame_indices)
+        time_dict['render'] = time.time() - t_render
     return time_dict
 
 
