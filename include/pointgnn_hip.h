@@ -1892,6 +1892,42 @@ int pgnn_render_graph_segments(const float *src_xyz, int64_t n_src,
                                const int32_t *edges, int64_t n_edges,
                                float *segments, void *stream);
 
+/* ---- PNG scanline unfilter: an inflated 8-bit PNG stream -> pixels ---------
+ * The second half of a PNG decode (the first, inflate, stays on the host:
+ * pointgnn_amd/png.py).  `raw` is the inflated IDAT stream of a non-interlaced
+ * file of bit depth 8 on the device: `height` rows of 1 + width * C bytes, a
+ * filter byte (0..4) followed by the filtered bytes.  C follows color_type:
+ *   0 grey C = 1, 2 RGB C = 3, 3 palette index C = 1, 4 grey + alpha C = 2,
+ *   6 RGBA C = 4.
+ * Filter arithmetic (PNG specification, section 9; modulo 256 per byte): with
+ * a = the byte C positions to the left, b = the byte above, c = the byte above
+ * and C to the left, each 0 outside the image, the reconstructed byte is the
+ * filtered byte plus
+ *   type 0 (None) 0, 1 (Sub) a, 2 (Up) b, 3 (Average) (a + b) >> 1 with the
+ *   sum in at least 9 bits, 4 (Paeth) the Paeth predictor: p = a + b - c,
+ *   pa = |p - a|, pb = |p - b|, pc = |p - c|; a if pa <= pb && pa <= pc, else
+ *   b if pb <= pc, else c (the order of the tests decides ties).
+ * A filter byte above 4 reconstructs like None (png.inflate rejects it first).
+ * image uint8 [height, width, 3], channel order R, G, B (bgr = 0) or B, G, R
+ * (bgr != 0, cv2.imread's layout):
+ *   grey is replicated into the three channels; alpha is dropped, not
+ *   composited (cv2.imread's default flag does the same); a palette index i
+ *   gives palette[i] (device uint8 [palette_entries, 3] RGB, entries 1..256),
+ *   an index >= palette_entries gives (0, 0, 0).
+ * One workgroup walks the image in a skewed wavefront (lane = row; bands of
+ * rows for taller images, whose last unfiltered row passes through the
+ * workspace).  Enqueues on `stream`; reads nothing back.
+ * PGNN_E_INVALID (nothing enqueued, pgnn_last_error names the entry): width or
+ * height < 1 or a stream size beyond int64, color_type not one of 0, 2, 3, 4,
+ * 6, a null pointer, color_type 3 without a palette of 1..256 entries;
+ * PGNN_E_WORKSPACE: workspace_bytes below pgnn_png_unfilter_workspace_bytes
+ * (which is 0 for sizes out of range).                                       */
+size_t pgnn_png_unfilter_workspace_bytes(int64_t width, int64_t height);
+int pgnn_png_unfilter(const uint8_t *raw, int64_t width, int64_t height,
+                      int32_t color_type, const uint8_t *palette,
+                      int32_t palette_entries, int32_t bgr, void *workspace,
+                      size_t workspace_bytes, uint8_t *image, void *stream);
+
 /* ---- diagnostics (not part of the reference-facing surface) -------------- */
 /* Process-wide knobs for benchmarks and tests; see "Conventions".  Keys:
  *   launch shape   scatter_rows_per_wave, scatter_nt, mlp_blocks_per_cu,

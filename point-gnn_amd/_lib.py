@@ -523,6 +523,10 @@ _SIGNATURES = {
                                      c_vp, c_vp]),
     "pgnn_render_graph_segments": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp,
                                            c_i64, c_vp, c_vp]),
+    # PNG scanline unfilter
+    "pgnn_png_unfilter_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pgnn_png_unfilter": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_i32,
+                                  c_i32, c_vp, c_sz, c_vp, c_vp]),
 }
 
 _lib = None

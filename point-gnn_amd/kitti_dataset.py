@@ -15,9 +15,14 @@ voxel-averaged between the transform and the crop
 / `pgnn_kitti_cam_points_voxel_in_image`) and comes out float64, as the
 reference's does.
 
-Not implemented here (raise or absent): PNG decoding -- only the image SIZE
-is needed for the crop, read from the PNG header; for 'irgb' features pass a
-decoded BGR array.
+Colour: the crop needs only the image SIZE, read from the PNG header, and by
+default the file is not decoded (the colour columns of
+`get_cam_points_in_image_with_rgb` are then zero unless the caller passes a
+decoded BGR array).  `KittiDataset(..., decode_images=True)` decodes the
+frame's PNG itself -- zlib on the host, the scanline filters on the device
+(`pointgnn_amd.png`, `pgnn_png_unfilter`) -- and fills them: the 'irgb' /
+'0rgb' / 'rgb' input features from a KITTI directory.  `get_image` is that
+image, a BGR CUDA tensor.
 """
 import os
 import struct
@@ -236,8 +241,11 @@ class KittiDataset(object):
     def __init__(self, image_dir, point_dir, calib_dir, label_dir=None,
                  index_filename=None, is_training=False, is_raw=False,
                  difficulty=-100, num_classes=8, beam_downsample_rate=None,
-                 beam_count=64):
-        """beam_downsample_rate (extension): every method that reads a scan
+                 beam_count=64, decode_images=False):
+        """decode_images (extension): get_cam_points_in_image_with_rgb called
+        without `image=` decodes the frame's PNG (get_image) and fills the
+        colour columns; False leaves them zero, as before.
+        beam_downsample_rate (extension): every method that reads a scan
         keeps every rate-th of its `beam_count` LiDAR beams first
         (beam_downsample.downsample, scripts/point_cloud_downsample.py) --
         the WHOLE scan, before xyz_range, the transform, voxel averaging and
@@ -248,6 +256,7 @@ class KittiDataset(object):
             _check_args(n_beams=beam_count, rate=beam_downsample_rate)
         self._beam_rate = beam_downsample_rate
         self._beam_count = beam_count
+        self._decode_images = bool(decode_images)
         if is_raw:
             raise NotImplementedError(
                 "the raw-sequence layout is outside the ingest slice")
@@ -310,6 +319,14 @@ class KittiDataset(object):
         return png_size(os.path.join(
             self._image_dir, self._file_list[frame_idx]) + '.png')
 
+    def get_image(self, frame_idx):
+        """kitti_dataset.py:691-701 (`cv2.imread`): the frame's image, uint8
+        [H, W, 3] in BGR order, as a CUDA tensor; decoded on the current
+        stream (png.read_png), nothing read back."""
+        from . import png
+        return png.read_png(os.path.join(
+            self._image_dir, self._file_list[frame_idx]) + '.png', order='bgr')
+
     def get_cam_points(self, frame_idx, downsample_voxel_size=None,
                        calib=None, xyz_range=None):
         """kitti_dataset.py:612-628: the whole scan in camera coordinates (no
@@ -349,12 +366,16 @@ class KittiDataset(object):
                                          calib=None, xyz_range=None,
                                          image=None, deferred=False):
         """With `image` (decoded BGR array) the attributes are
-        [reflectance, r, g, b]; without one (PNG decoding is not part of this
-        package) the colour channels are zero -- enough for the 'i' / 'i000' /
-        '0' input features of the shipped configs (run.py:226-241).
-        deferred (extension): enqueue only and return a PendingPoints."""
+        [reflectance, r, g, b]; without one the frame's PNG is decoded when
+        the dataset was built with decode_images=True, else the colour
+        channels are zero -- enough for the 'i' / 'i000' / '0' input features
+        of the shipped configs (run.py:226-241).
+        deferred (extension): enqueue only and return a PendingPoints; the
+        decode too runs on the caller's current stream."""
         if calib is None:
             calib = self.get_calib(frame_idx)
+        if image is None and self._decode_images:
+            image = self.get_image(frame_idx)
         if xyz_range is None:
             # the file's [n,4] rows as they are (no split + re-join)
             velo = self._read_scan(frame_idx, on_device=True)

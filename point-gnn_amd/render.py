@@ -560,6 +560,19 @@ def write_ppm(path, image):
         f.write(image.tobytes())
 
 
+def image_background(dataset):
+    """A `background_reader` for render_results: the frame's camera image,
+    decoded on the device (png.read_png) as uint8 RGB [H, W, 3] -- the camera
+    view then draws on the photograph, as run.py -l does."""
+    from . import png
+
+    def reader(frame_idx):
+        return png.read_png(os.path.join(
+            dataset._image_dir, dataset.get_filename(frame_idx) + '.png'),
+            order='rgb')
+    return reader
+
+
 def render_results(dataset, result_dir, render_dir, views=('bev',),
                    frame_indices=None, fmt='png', with_gt=True,
                    background_reader=None, time_dict=None):
@@ -567,7 +580,8 @@ def render_results(dataset, result_dir, render_dir, views=('bev',),
     run.run_dataset writes them under <output_dir>/data, or any other KITTI
     result directory) into <render_dir>/<view>/<name>.<fmt>, fmt 'png' or
     'ppm'.  with_gt: also the labels, when the dataset has a label directory.
-    background_reader(frame_idx) -> uint8 RGB [H, W, 3] for the camera view.
+    background_reader(frame_idx) -> uint8 RGB [H, W, 3] for the camera view
+    (image_background(dataset): the frame's own PNG, decoded on the device).
     Sequential: one host read per image.  Returns the paths written."""
     from . import kitti_eval
     import time
@@ -638,6 +652,9 @@ def build_parser():
                     help="frame names, one per line (default: every scan)")
     ap.add_argument('--ppm', action='store_true',
                     help="write binary PPM files instead of PNG")
+    ap.add_argument('--image-background', action='store_true',
+                    help="camera view: draw on the frame's decoded image "
+                         "instead of black")
     return ap
 
 
@@ -654,7 +671,9 @@ def main(argv=None):
                            index_filename=args.split)
     paths = render_results(dataset, args.result_dir, args.render_dir,
                            views=tuple(args.view or ('bev',)),
-                           fmt='ppm' if args.ppm else 'png')
+                           fmt='ppm' if args.ppm else 'png',
+                           background_reader=image_background(dataset)
+                           if args.image_background else None)
     print("wrote %d images to %s" % (len(paths), args.render_dir))
     return 0
 

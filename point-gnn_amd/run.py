@@ -77,7 +77,8 @@ def detect_frame(dataset, frame_idx, model, config, use_box_merge=True,
 
     t = time.time()
     # run.py:210-211 (colour channels are zero unless `image_reader` supplies
-    # the decoded BGR image: PNG decoding is not part of this package)
+    # the decoded BGR image or the dataset decodes its PNGs itself:
+    # KittiDataset(decode_images=True))
     image = image_reader(frame_idx) if image_reader is not None else None
     points = dataset.get_cam_points_in_image_with_rgb(
         frame_idx, config['downsample_by_voxel_size'], image=image)
