@@ -139,6 +139,67 @@ int pgnn_radius_graph_fill_f64(const double *points, int64_t n_points,
                                const int32_t *offsets /* from _count */,
                                int32_t *edges /* [capacity, 2] */,
                                int64_t capacity, void *stream);
+/* ---- k nearest neighbours within the radius (extension) -----------------
+ * An EXTENSION of gen_disjointed_rnn_local_graph_v3 (models/graph_gen.py:
+ * 197-220): the reference bounds a neighbourhood with np.random.choice only
+ * (its neighbors_downsample_method hook ignores every value but 'random');
+ * these entries keep the k nearest points of the radius neighbourhood.
+ * Inputs as pgnn_radius_graph_count / _fill: points [n_points, 3] and centres
+ * [n_centers, 3], both float32 or (_f64) both float64, radius > 0, optional
+ * scale3_host; new: k, 1 <= k <= 256 (256 is the num_neighbors of the shipped
+ * training configs).  k > 256 returns PGNN_E_UNSUPPORTED; k < 1 returns
+ * PGNN_E_INVALID before any HIP call.  For every centre q:
+ *   Candidate set: N(q) is exactly the set of points the radius graph returns
+ *     for q, by the same arithmetic: coordinates pre-divided by scale3,
+ *     d2 = (dx*dx + dy*dy) + dz*dz in float64 with no contraction, and
+ *     d2 <= r*r, inclusive.
+ *   Selection: the min(k, |N(q)|) members of N(q) with the smallest key
+ *     (d2, point index), compared lexicographically -- equal distances are
+ *     broken by the smaller point index, so duplicate points and lattice ties
+ *     are defined.
+ *   Rows: (point_idx, centre_idx), grouped by ascending centre and sorted by
+ *     ascending key inside a centre; offsets[n_centers + 1] is the CSR of the
+ *     groups.  Hence offsets[q+1] - offsets[q] == min(k, radius fan-in of q)
+ *     and the rows of a centre are a subset of its radius-graph rows.  The
+ *     order is independent of the cell grid (the radius graph's own row order
+ *     is not part of this contract).
+ *   NaN coordinates: unspecified, as in the radius graph.
+ * Two phases, no hidden sync: count -> caller reads offsets[n_centers] and
+ * allocates -> fill (same workspace, same arguments).  Rows at or beyond
+ * `capacity` are not written, as in pgnn_radius_graph_fill.  The uncapped
+ * neighbour list is never materialised: the workspace is a function of
+ * (n_points, n_centers, k) alone (0 for an unsupported k). */
+size_t pgnn_knn_graph_workspace_bytes(int64_t n_points, int64_t n_centers,
+                                      int32_t k);
+int pgnn_knn_graph_count(const float *points, int64_t n_points,
+                         const float *centers, int64_t n_centers,
+                         double radius, const double *scale3_host, int32_t k,
+                         void *workspace, size_t workspace_bytes,
+                         int32_t *offsets /* [n_centers + 1] */,
+                         void *stream);
+int pgnn_knn_graph_fill(const float *points, int64_t n_points,
+                        const float *centers, int64_t n_centers,
+                        double radius, const double *scale3_host, int32_t k,
+                        void *workspace, size_t workspace_bytes,
+                        const int32_t *offsets /* from _count */,
+                        int32_t *edges /* [capacity, 2] */,
+                        int64_t capacity, void *stream);
+/* float64 points / centres (extension of models/graph_gen.py:197-220 on the
+ * training path's float64 cloud, like pgnn_radius_graph_count_f64). */
+int pgnn_knn_graph_count_f64(const double *points, int64_t n_points,
+                             const double *centers, int64_t n_centers,
+                             double radius, const double *scale3_host,
+                             int32_t k, void *workspace,
+                             size_t workspace_bytes,
+                             int32_t *offsets /* [n_centers + 1] */,
+                             void *stream);
+int pgnn_knn_graph_fill_f64(const double *points, int64_t n_points,
+                            const double *centers, int64_t n_centers,
+                            double radius, const double *scale3_host,
+                            int32_t k, void *workspace, size_t workspace_bytes,
+                            const int32_t *offsets /* from _count */,
+                            int32_t *edges /* [capacity, 2] */,
+                            int64_t capacity, void *stream);
 /* Capacity form of the same builder -- count, scan and fill in ONE call with
  * no size leaving the device (graph_gen.py:155-220 never waits for one: its
  * NumPy arrays carry their sizes; a device pipeline that reads K or E back

@@ -132,6 +132,17 @@ _SIGNATURES = {
     "pgnn_radius_graph_fill_f64": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_f64,
                                            c_vp, c_vp, c_sz, c_vp, c_vp, c_i64,
                                            c_vp]),
+    "pgnn_knn_graph_workspace_bytes": (c_sz, [c_i64, c_i64, c_i32]),
+    "pgnn_knn_graph_count": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_f64, c_vp,
+                                     c_i32, c_vp, c_sz, c_vp, c_vp]),
+    "pgnn_knn_graph_fill": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_f64, c_vp,
+                                    c_i32, c_vp, c_sz, c_vp, c_vp, c_i64,
+                                    c_vp]),
+    "pgnn_knn_graph_count_f64": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_f64,
+                                         c_vp, c_i32, c_vp, c_sz, c_vp, c_vp]),
+    "pgnn_knn_graph_fill_f64": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_f64, c_vp,
+                                        c_i32, c_vp, c_sz, c_vp, c_vp, c_i64,
+                                        c_vp]),
     "pgnn_radius_graph_dyn_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "pgnn_radius_graph_dyn": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp,
                                       c_f64, c_vp, c_vp, c_sz, c_vp, c_i64,

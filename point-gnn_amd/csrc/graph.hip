@@ -318,6 +318,216 @@ __global__ __launch_bounds__(1024) void radius_query_kernel(
   }
 }
 
+// ---- k nearest neighbours within the radius -------------------------------------
+// (extension; the reference's neighbors_downsample_method hook,
+// models/graph_gen.py:197-220, knows 'random' only.)  The candidate set of a
+// centre is the radius graph's, found by the same walk with the same float64
+// predicate; of it the wave keeps the k smallest keys (d2, point index),
+// compared lexicographically, and writes them in ascending key order.  The
+// count phase is radius_query_kernel<false> followed by a clamp to k, so
+// offsets[q + 1] - offsets[q] == min(k, fan-in) by construction.
+constexpr int kKnnMaxK = 256;
+
+__device__ __forceinline__ bool knn_key_less(double da, int32_t ia, double db,
+                                             int32_t ib) {
+  return da < db || (da == db && ia < ib);
+}
+
+// Orders one wave's LDS accesses across its lanes: the hardware executes a
+// wave's LDS instructions in issue order, so all that is needed is that the
+// compiler keeps the accesses on their side of this point.
+__device__ __forceinline__ void knn_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ void knn_clamp_counts_kernel(int32_t *__restrict__ counts,
+                                        int64_t n, int32_t k) {
+  graph_prio();
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    if (counts[i] > k) counts[i] = k;
+}
+
+// One wave per centre, the walk of radius_query_kernel (64-cell box, bucket
+// scan, 64 candidates a chunk, two chunks a round).  The wave's k best keys so
+// far live in LDS as one ascending list, ld2[k] / lidx[k] per wave (dynamic
+// LDS: waves * k * 12 bytes).  A chunk's hits are merged into it by rank:
+//   - once the list is full, hits not below its last key are dropped at once
+//     (after the first chunks most hits go here; nothing else is done for a
+//     chunk that has none left);
+//   - a surviving hit's new slot is (hits of this chunk below it) + (list
+//     entries below it: a binary search in LDS);
+//   - a list entry's new slot is its old one + (hits below it);
+//   - keys are distinct (a point is a candidate once), so the new slots are a
+//     permutation; slots >= k are not written.
+// All reads of the old list precede all writes of the new one (knn_wave_sync).
+// The uncapped neighbour list is never written anywhere.
+template <typename T>
+__global__ __launch_bounds__(1024) void knn_select_kernel(
+    const T *__restrict__ centers, int64_t n_centers, Scale3 sc, double r,
+    uint32_t mask, const int32_t *__restrict__ cell_start,
+    const int32_t *__restrict__ cell_end,
+    const SortedPoint *__restrict__ sorted,
+    const int32_t *__restrict__ offsets, int32_t *__restrict__ edges,
+    int64_t capacity, int k) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char knn_lds[];
+  graph_prio();
+  const int lane = threadIdx.x & 63;
+  const int wpb = blockDim.x >> 6;
+  const int wib = threadIdx.x >> 6;
+  double *ld2 = (double *)knn_lds + (size_t)wib * k;
+  int32_t *lidx = (int32_t *)((double *)knn_lds + (size_t)wpb * k) +
+                  (size_t)wib * k;
+  const int64_t wave0 = (int64_t)blockIdx.x * wpb + wib;
+  const int64_t n_waves = (int64_t)gridDim.x * wpb;
+  const double r2 = r * r;
+  const double inv_r = 1.0 / r;  // as in cell_keys_kernel
+  const double rr = r * (1.0 + 1e-9) + 1e-300;  // as in radius_query_kernel
+  for (int64_t q = wave0; q < n_centers; q += n_waves) {
+    double cx, cy, cz;
+    load_point(centers, q, sc, cx, cy, cz);
+    const int x0 = rcell_of(cx - rr, inv_r), x1 = rcell_of(cx + rr, inv_r);
+    const int y0 = rcell_of(cy - rr, inv_r), y1 = rcell_of(cy + rr, inv_r);
+    const int z0 = rcell_of(cz - rr, inv_r), z1 = rcell_of(cz + rr, inv_r);
+    const int nx = x1 - x0 + 1, ny = y1 - y0 + 1, nz = z1 - z0 + 1;
+    const int n_cells = nx * ny * nz;  // <= 64
+    int my_s = 0, my_cnt = 0, my_ix = 0, my_iy = 0, my_iz = 0;
+    if (lane < n_cells) {
+      my_ix = x0 + lane % nx;
+      my_iy = y0 + (lane / nx) % ny;
+      my_iz = z0 + lane / (nx * ny);
+      const uint32_t b = cell_hash(my_ix, my_iy, my_iz, mask);
+      my_s = cell_start[b];
+      my_cnt = cell_end[b] - my_s;
+    }
+    int incl = my_cnt;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int t = __shfl_up(incl, d);
+      if (lane >= d) incl += t;
+    }
+    const int total_cand = __shfl(incl, 63);
+    int n_list = 0;              // wave-uniform: entries of the list
+    double thr_d = 0.0;          // the list's last key once it is full
+    int32_t thr_i = 0;
+    for (int j0 = 0; j0 < total_cand; j0 += 128) {
+      const bool two = j0 + 64 < total_cand;  // wave-uniform
+      bool valid[2];
+      int ix[2], iy[2], iz[2];
+      SortedPoint sp[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        if (u == 1 && !two) break;
+        valid[u] = j0 + 64 * u + lane < total_cand;
+        const int j = valid[u] ? j0 + 64 * u + lane : total_cand - 1;
+        int lo = 0, hi = n_cells - 1;
+#pragma unroll
+        for (int step = 0; step < 6; ++step) {
+          const int mid = (lo + hi) >> 1;
+          const int v = __shfl(incl, mid);
+          if (v > j) hi = mid; else lo = mid + 1;
+        }
+        const int c = lo < n_cells ? lo : n_cells - 1;
+        const int c_incl = __shfl(incl, c), c_cnt = __shfl(my_cnt, c);
+        const int c_s = __shfl(my_s, c);
+        ix[u] = __shfl(my_ix, c);
+        iy[u] = __shfl(my_iy, c);
+        iz[u] = __shfl(my_iz, c);
+        sp[u] = sorted[c_s + (j - (c_incl - c_cnt))];
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        if (u == 1 && !two) break;
+        bool hit = false;
+        double d2 = 0.0;
+        const int32_t id = sp[u].idx;
+        if (valid[u] && rcell_of(sp[u].x, inv_r) == ix[u] &&
+            rcell_of(sp[u].y, inv_r) == iy[u] &&
+            rcell_of(sp[u].z, inv_r) == iz[u]) {
+          const double dx = sp[u].x - cx, dy = sp[u].y - cy,
+                       dz = sp[u].z - cz;
+          d2 = (dx * dx + dy * dy) + dz * dz;
+          hit = d2 <= r2;
+        }
+        if (n_list == k) hit = hit && knn_key_less(d2, id, thr_d, thr_i);
+        const unsigned long long m = __ballot(hit);
+        if (m == 0ull) continue;  // wave-uniform
+        // my slots of the old list: lane + 64 t
+        const int tiers = (n_list + 63) >> 6;
+        double od[4];
+        int32_t oi[4];
+        int shift[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int s = lane + 64 * t;
+          od[t] = 0.0;
+          oi[t] = 0;
+          if (t < tiers && s < n_list) {
+            od[t] = ld2[s];
+            oi[t] = lidx[s];
+          }
+        }
+        int below = 0;  // hits of this chunk below mine
+        const int d2_hi = __double2hiint(d2), d2_lo = __double2loint(d2);
+        for (unsigned long long mm = m; mm != 0ull; mm &= mm - 1ull) {
+          const int b = __builtin_ctzll(mm);  // wave-uniform
+          const double hd =
+              __hiloint2double(__builtin_amdgcn_readlane(d2_hi, b),
+                               __builtin_amdgcn_readlane(d2_lo, b));
+          const int32_t hi_ = __builtin_amdgcn_readlane(id, b);
+          below += knn_key_less(hd, hi_, d2, id) ? 1 : 0;
+#pragma unroll
+          for (int t = 0; t < 4; ++t)
+            if (t < tiers)
+              shift[t] += knn_key_less(hd, hi_, od[t], oi[t]) ? 1 : 0;
+        }
+        int rank = 0;  // list entries below my hit
+        if (hit) {
+          int lo = 0, hi = n_list;
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (knn_key_less(ld2[mid], lidx[mid], d2, id)) lo = mid + 1;
+            else hi = mid;
+          }
+          rank = lo;
+        }
+        knn_wave_sync();  // the old list has been read
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int s = lane + 64 * t;
+          if (t < tiers && s < n_list && shift[t] > 0 && s + shift[t] < k) {
+            ld2[s + shift[t]] = od[t];
+            lidx[s + shift[t]] = oi[t];
+          }
+        }
+        if (hit && below + rank < k) {
+          ld2[below + rank] = d2;
+          lidx[below + rank] = id;
+        }
+        knn_wave_sync();  // the new list is in place
+        n_list += __popcll(m);
+        if (n_list >= k) {
+          n_list = k;
+          thr_d = ld2[k - 1];
+          thr_i = lidx[k - 1];
+        }
+      }
+    }
+    const int64_t out0 = (int64_t)offsets[q];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int s = lane + 64 * t;
+      if (s < n_list && out0 + s < capacity) {
+        edges[2 * (out0 + s)] = lidx[s];
+        edges[2 * (out0 + s) + 1] = (int32_t)q;
+      }
+    }
+    knn_wave_sync();  // before the next centre overwrites the list
+  }
+}
+
 // ---- neighbour cap (training) ---------------------------------------------------
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
   x ^= x >> 30;
@@ -1120,6 +1330,153 @@ extern "C" int pgnn_radius_graph_fill_f64(
   return radius_fill_impl(points, n_points, centers, n_centers, radius,
                           scale3_host, workspace, workspace_bytes, offsets,
                           edges, capacity, (hipStream_t)stream_);
+  PGNN_GUARD_END
+}
+
+// ---- k nearest neighbours within the radius (extension) -------------------------
+// models/graph_gen.py:197-220 caps a neighbourhood with np.random.choice only;
+// these entries keep the k nearest instead (contract: pointgnn_hip.h).  Same
+// workspace layout as the radius graph: [Grid | counts | scan scratch] -- the
+// selection happens in LDS, so nothing here grows with k or with the fan-in.
+extern "C" size_t pgnn_knn_graph_workspace_bytes(int64_t n_points,
+                                                 int64_t n_centers, int32_t k) {
+  if (k < 1 || k > kKnnMaxK) return 0;
+  return pgnn_radius_graph_workspace_bytes(n_points, n_centers);
+}
+
+namespace {
+int knn_check(int64_t n_points, int64_t n_centers, double radius, int32_t k,
+              bool extra_ok) {
+  PGNN_REQUIRE(k >= 1, PGNN_E_INVALID, "knn_graph: k < 1");
+  PGNN_REQUIRE(n_points >= 0 && n_centers >= 0 && radius > 0.0 && extra_ok,
+               PGNN_E_INVALID, "knn_graph: bad argument");
+  PGNN_REQUIRE(k <= kKnnMaxK, PGNN_E_UNSUPPORTED,
+               "knn_graph: k > 256 is not supported");
+  return 0;
+}
+
+template <typename T>
+int knn_count_impl(const T *points, int64_t n_points, const T *centers,
+                   int64_t n_centers, double radius, const double *scale3_host,
+                   int32_t k, void *workspace, size_t workspace_bytes,
+                   int32_t *offsets, hipStream_t stream) {
+  int rc = knn_check(n_points, n_centers, radius, k, offsets != nullptr);
+  if (rc) return rc;
+  PGNN_REQUIRE((n_points == 0 || points) && (n_centers == 0 || centers),
+               PGNN_E_INVALID, "knn_graph_count: null input");
+  PGNN_REQUIRE(workspace != nullptr &&
+                   workspace_bytes >= pgnn_knn_graph_workspace_bytes(
+                                          n_points, n_centers, k),
+               PGNN_E_WORKSPACE, "knn_graph: workspace too small");
+  RadiusWs w;
+  rc = radius_carve(workspace, workspace_bytes, n_points, n_centers, w);
+  if (rc) return rc;
+  const Scale3 sc = make_scale(scale3_host);
+  rc = grid_build(points, n_points, sc, 0.0, 0.0, 0.0, nullptr, radius, w.g,
+                  stream);
+  if (rc) return rc;
+  if (n_centers > 0) {
+    const unsigned wpb = graph_wide_block() >> 6;
+    hipLaunchKernelGGL((radius_query_kernel<false, T>),
+                       dim3(graph_grid((n_centers + wpb - 1) / wpb)),
+                       dim3(graph_wide_block()), graph_lds_pad(), stream,
+                       centers, n_centers, sc, radius, w.g.mask,
+                       w.g.cell_start, w.g.cell_end, w.g.sorted, w.counts,
+                       (const int32_t *)nullptr, (int32_t *)nullptr,
+                       (int64_t)0, (const int32_t *)nullptr);
+    hipLaunchKernelGGL(knn_clamp_counts_kernel,
+                       dim3(graph_grid((n_centers + 255) / 256)), dim3(256),
+                       graph_lds_pad(), stream, w.counts, n_centers, k);
+    PGNN_HIP(hipGetLastError());
+  }
+  return exclusive_scan_i32(w.counts, offsets, n_centers, w.scan_scratch,
+                            w.scan_bytes, stream);
+}
+
+template <typename T>
+int knn_fill_impl(const T *points, int64_t n_points, const T *centers,
+                  int64_t n_centers, double radius, const double *scale3_host,
+                  int32_t k, void *workspace, size_t workspace_bytes,
+                  const int32_t *offsets, int32_t *edges, int64_t capacity,
+                  hipStream_t stream) {
+  int rc = knn_check(n_points, n_centers, radius, k,
+                     offsets != nullptr && capacity >= 0);
+  if (rc) return rc;
+  if (n_centers == 0 || capacity == 0) return 0;
+  PGNN_REQUIRE(edges && points && centers, PGNN_E_INVALID,
+               "knn_graph_fill: null pointer");
+  PGNN_REQUIRE(workspace != nullptr &&
+                   workspace_bytes >= pgnn_knn_graph_workspace_bytes(
+                                          n_points, n_centers, k),
+               PGNN_E_WORKSPACE, "knn_graph: workspace too small");
+  RadiusWs w;  // same carve as _count: the grid built there is reused
+  rc = radius_carve(workspace, workspace_bytes, n_points, n_centers, w);
+  if (rc) return rc;
+  const Scale3 sc = make_scale(scale3_host);
+  const unsigned block = graph_wide_block(), wpb = block >> 6;
+  // the waves' lists: k keys of 8 + 4 bytes each
+  const size_t lds = (size_t)wpb * (size_t)k * 12 + graph_lds_pad();
+  if (lds > 48 * 1024) {
+    rc = ensure_dynamic_lds((const void *)knn_select_kernel<T>, lds);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL((knn_select_kernel<T>),
+                     dim3(graph_grid((n_centers + wpb - 1) / wpb)), dim3(block),
+                     lds, stream, centers, n_centers, sc, radius, w.g.mask,
+                     w.g.cell_start, w.g.cell_end, w.g.sorted, offsets, edges,
+                     capacity, (int)k);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+}
+}  // namespace
+
+extern "C" int pgnn_knn_graph_count(const float *points, int64_t n_points,
+                                    const float *centers, int64_t n_centers,
+                                    double radius, const double *scale3_host,
+                                    int32_t k, void *workspace,
+                                    size_t workspace_bytes, int32_t *offsets,
+                                    void *stream_) {
+  PGNN_GUARD_BEGIN
+  return knn_count_impl(points, n_points, centers, n_centers, radius,
+                        scale3_host, k, workspace, workspace_bytes, offsets,
+                        (hipStream_t)stream_);
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_knn_graph_fill(const float *points, int64_t n_points,
+                                   const float *centers, int64_t n_centers,
+                                   double radius, const double *scale3_host,
+                                   int32_t k, void *workspace,
+                                   size_t workspace_bytes,
+                                   const int32_t *offsets, int32_t *edges,
+                                   int64_t capacity, void *stream_) {
+  PGNN_GUARD_BEGIN
+  return knn_fill_impl(points, n_points, centers, n_centers, radius,
+                       scale3_host, k, workspace, workspace_bytes, offsets,
+                       edges, capacity, (hipStream_t)stream_);
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_knn_graph_count_f64(
+    const double *points, int64_t n_points, const double *centers,
+    int64_t n_centers, double radius, const double *scale3_host, int32_t k,
+    void *workspace, size_t workspace_bytes, int32_t *offsets, void *stream_) {
+  PGNN_GUARD_BEGIN
+  return knn_count_impl(points, n_points, centers, n_centers, radius,
+                        scale3_host, k, workspace, workspace_bytes, offsets,
+                        (hipStream_t)stream_);
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_knn_graph_fill_f64(
+    const double *points, int64_t n_points, const double *centers,
+    int64_t n_centers, double radius, const double *scale3_host, int32_t k,
+    void *workspace, size_t workspace_bytes, const int32_t *offsets,
+    int32_t *edges, int64_t capacity, void *stream_) {
+  PGNN_GUARD_BEGIN
+  return knn_fill_impl(points, n_points, centers, n_centers, radius,
+                       scale3_host, k, workspace, workspace_bytes, offsets,
+                       edges, capacity, (hipStream_t)stream_);
   PGNN_GUARD_END
 }
 

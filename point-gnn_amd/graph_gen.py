@@ -32,6 +32,7 @@ import torch
 from . import _lib
 
 __all__ = ["gen_disjointed_rnn_local_graph_v3",
+           "gen_disjointed_knn_local_graph_v3", "knn_graph_device",
            "gen_multi_level_local_graph_v3", "get_graph_generate_fn",
            "multi_layer_downsampling_select", "multi_layer_downsampling_random",
            "gen_multi_level_local_graph_v3_one_read",
@@ -462,6 +463,63 @@ def gen_disjointed_rnn_local_graph_v3(
         seed = int(np.random.randint(0, 2 ** 31 - 1))
     edges, _ = radius_graph_device(p, c, radius, scale, num_neighbors,
                                    seed or 0)
+    if was_np:
+        return edges.cpu().numpy()
+    return edges
+
+
+def knn_graph_device(points, centers, radius, num_neighbors, scale=None):
+    """The `num_neighbors` nearest points of every centre's radius
+    neighbourhood (extension; contract: pgnn_knn_graph_count in
+    include/pointgnn_hip.h).  Device tensors in/out.  Returns (edges int32
+    [E,2], offsets int32 [Q+1]); rows are (point_idx, centre_idx), grouped by
+    ascending centre and sorted by ascending (squared distance, point index)
+    inside a centre -- a pure function of the inputs.  One host sync (reading
+    E).  1 <= num_neighbors <= 256."""
+    k = int(num_neighbors)
+    if k < 1:
+        raise ValueError("knn graph: num_neighbors must be >= 1, got %r"
+                         % (num_neighbors,))
+    lib = _lib.load()
+    dev = points.device
+    points, centers, wide = _same_precision(points, centers)
+    count_fn = lib.pgnn_knn_graph_count_f64 if wide else \
+        lib.pgnn_knn_graph_count
+    fill_fn = lib.pgnn_knn_graph_fill_f64 if wide else \
+        lib.pgnn_knn_graph_fill
+    n_p, n_c = int(points.shape[0]), int(centers.shape[0])
+    ws_bytes = lib.pgnn_knn_graph_workspace_bytes(n_p, n_c, k)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    offsets = torch.empty(n_c + 1, dtype=torch.int32, device=dev)
+    keep, sp = _scale3(scale)
+    st = _lib.stream_ptr()
+    _lib.check(count_fn(
+        _lib.ptr(points), n_p, _lib.ptr(centers), n_c, float(radius), sp, k,
+        _lib.ptr(ws), ws_bytes, _lib.ptr(offsets), st),
+        "pgnn_knn_graph_count")
+    n_e = int(offsets[-1].item())  # the one host sync
+    edges = torch.empty((n_e, 2), dtype=torch.int32, device=dev)
+    _lib.check(fill_fn(
+        _lib.ptr(points), n_p, _lib.ptr(centers), n_c, float(radius), sp, k,
+        _lib.ptr(ws), ws_bytes, _lib.ptr(offsets), _lib.ptr(edges), n_e, st),
+        "pgnn_knn_graph_fill")
+    del keep
+    edges._pgnn_sorted = 1  # grouped by ascending centre (see gnn.mark_sorted)
+    return edges, offsets
+
+
+def gen_disjointed_knn_local_graph_v3(points_xyz, center_xyz, radius,
+                                      num_neighbors, scale=None):
+    """Extension of graph_gen.py:197-220: every centre keeps the
+    `num_neighbors` nearest points within `radius` (ties by the smaller point
+    index) instead of a random subset -- see knn_graph_device.  Registry key
+    'disjointed_knn_local_graph_v3'."""
+    if int(num_neighbors) < 1:
+        raise ValueError("knn graph: num_neighbors must be >= 1, got %r"
+                         % (num_neighbors,))
+    p, was_np = _to_dev(points_xyz)
+    c, _ = _to_dev(center_xyz)
+    edges, _ = knn_graph_device(p, c, radius, num_neighbors, scale)
     if was_np:
         return edges.cpu().numpy()
     return edges
@@ -1086,6 +1144,7 @@ def get_graph_generate_fn(method_name):
     """graph_gen.py:222-227."""
     method_map = {
         'disjointed_rnn_local_graph_v3': gen_disjointed_rnn_local_graph_v3,
+        'disjointed_knn_local_graph_v3': gen_disjointed_knn_local_graph_v3,
         'multi_level_local_graph_v3': gen_multi_level_local_graph_v3,
     }
     return method_map[method_name]
