@@ -1865,9 +1865,10 @@ int pgnn_beam_select(const float *velo_points, int64_t n_points,
  * boxes_3d_to_line_set :785-822, vis_draw_2d_box, vis_draw_3d_box, vis_points,
  * vis_graph, vis_point_graph, inspect_points).  There is no display, open3d or
  * cv2 here: the output is a uint8 RGB image [height, width, 3], row-major,
- * origin top left.  NOT drawn: text (cv2.putText: no font) and the interactive
- * 3D window.  The semantics are integer-exact: every step below is an IEEE
- * float64 + - * / in the order written, a floor, or integer arithmetic.
+ * origin top left.  Text (cv2.putText) is a pass of its own over a finished
+ * image: "text" below.  NOT drawn: the interactive 3D window.  The semantics
+ * are integer-exact: every step below is an IEEE float64 + - * / in the order
+ * written, a floor, or integer arithmetic.
  *
  * canvas   1 <= width, height <= PGNN_RENDER_MAX_DIM (4096).
  * view     view_m [3][4] and view_d [4] float64 in HOST memory, near float64.
@@ -1952,6 +1953,70 @@ int pgnn_render_graph_segments(const float *src_xyz, int64_t n_src,
                                const float *dst_xyz, int64_t n_dst,
                                const int32_t *edges, int64_t n_edges,
                                float *segments, void *stream);
+
+/* ---- text: strings of a built-in 5 x 7 font drawn into an image -------------
+ * What cv2.putText does for run.py -l 1 (:414-421, 'P | 0.873' beside every
+ * detection) and vis_draw_2d_box (kitti_dataset.py:1069-1084, the object's
+ * name).  There is no font file here: the font is one table of this library,
+ * uint8 [95][7] for the printable ASCII codes 0x20..0x7E (csrc/font5x7.h).  A
+ * glyph has 5 columns and 7 rows; a row is a bit mask, bit 4 the leftmost
+ * column, bit 0 the rightmost; row 0 is the top.  pgnn_render_font copies the
+ * table to HOST memory [95 * 7] (no device needed).  Integer arithmetic only.
+ *
+ * image    pgnn_render_text draws IN PLACE into a device uint8 [height, width,
+ *   3] image, over whatever it holds (the output of pgnn_render_resolve, a
+ *   camera picture, one colour).  Canvas as above, 1..PGNN_RENDER_MAX_DIM.
+ * inputs   all in DEVICE memory; none is read on the host.
+ *   chars    uint8 [total], the strings one after another;
+ *   offsets  int32 [n_strings + 1], ascending, offsets[0] == 0; string j is
+ *     chars[offsets[j] .. offsets[j + 1]) and total == offsets[n_strings].  A
+ *     string with offsets[j] < 0, offsets[j + 1] < offsets[j] or offsets[j + 1]
+ *     > offsets[n_strings] is DROPPED on the device (nothing of chars outside
+ *     [0, offsets[n_strings]) is ever read); chars == NULL drops every string;
+ *   anchors  int32 [n_strings, 2] (x, y): the top left pixel of the string's
+ *     first glyph cell; any int32 value is legal;
+ *   scales   uint8 [n_strings], or NULL with `scale` for all strings; 1..4.  A
+ *     per-string value outside 1..4 drops that string;
+ *   colors   uint8 [n_colors, 3]; n_colors == 1 is one colour for all strings,
+ *     otherwise n_colors == n_strings, one row per string;
+ *   plate_colors  the same convention; n_plate_colors == 0: no plates.
+ * glyphs   character i of a string with scale s and anchor (x, y) has its cell
+ *   origin at (x + 6 i s, y), in int64.  Its glyph pixel (column c, row r),
+ *   when lit, covers the s x s block whose top left is (x + (6 i + c) s,
+ *   y + r s).  The advance is 6 s, the cell height 7 s.  A byte outside
+ *   0x20..0x7E draws the glyph of '?'.
+ * plate    with plates, a string of n >= 1 characters also owns the rectangle
+ *   [x - s, x + (6 n - 1) s + s) x [y - s, y + 7 s + s), shown in its plate
+ *   colour.  An empty string draws nothing.
+ * stacking on each pixel the string with the LARGEST index wins, by a glyph
+ *   pixel or by a plate pixel; within one string a glyph pixel beats a plate
+ *   pixel.  A later string's plate therefore covers an earlier string's
+ *   glyph, as a later cv2.putText would.  A pixel no string owns keeps its
+ *   bytes exactly.
+ * clipping pixels off the canvas are skipped.  Only the characters with a
+ *   glyph column on the canvas are visited, and the plate is cut to the
+ *   canvas first: the work per string is bounded by the canvas, not by its
+ *   length.
+ * limits   n_strings < 2^30; total < 2^31 (it is an int32).
+ * The workspace is one uint32 key per pixel, (string + 1) << 1 | is_glyph,
+ * raised with an atomic max; one call clears it, stamps every string and
+ * resolves into the image: three launches whatever n_strings is.  Enqueues on
+ * `stream`; reads nothing back.  PGNN_E_INVALID (nothing enqueued): width or
+ * height outside 1..4096; `scale` outside 1..4 when scales is NULL; n_strings
+ * outside 0..2^30-1; n_colors not 1 or n_strings; n_plate_colors not 0, 1 or
+ * n_strings; a null colour table with a non-zero count; for n_strings > 0 a
+ * null image, offsets, anchors or workspace.  n_strings == 0 returns 0 and
+ * enqueues nothing.  PGNN_E_WORKSPACE: workspace_bytes below
+ * pgnn_render_text_workspace_bytes (which is 0 for a canvas out of range).  */
+size_t pgnn_render_text_workspace_bytes(int32_t width, int32_t height);
+int pgnn_render_text(uint8_t *image, int32_t width, int32_t height,
+                     const uint8_t *chars, const int32_t *offsets,
+                     int64_t n_strings, const int32_t *anchors,
+                     const uint8_t *scales, int32_t scale,
+                     const uint8_t *colors, int64_t n_colors,
+                     const uint8_t *plate_colors, int64_t n_plate_colors,
+                     void *workspace, size_t workspace_bytes, void *stream);
+int pgnn_render_font(uint8_t *table_host /* [95 * 7] */);
 
 /* ---- PNG scanline unfilter: an inflated 8-bit PNG stream -> pixels ---------
  * The second half of a PNG decode (the first, inflate, stays on the host:

@@ -534,6 +534,13 @@ _SIGNATURES = {
                                      c_vp, c_vp]),
     "pgnn_render_graph_segments": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp,
                                            c_i64, c_vp, c_vp]),
+    # text (chars, offsets, anchors, scales and colours are device arrays;
+    # pgnn_render_font writes host memory)
+    "pgnn_render_text_workspace_bytes": (c_sz, [c_i32, c_i32]),
+    "pgnn_render_text": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp,
+                                 c_vp, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp,
+                                 c_sz, c_vp]),
+    "pgnn_render_font": (c_i32, [c_vp]),
     # PNG scanline unfilter
     "pgnn_png_unfilter_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "pgnn_png_unfilter": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_i32,

@@ -11,8 +11,12 @@
 //   bit 63 | s                               segment s (the larger index wins;
 //                                            any segment beats any point)
 // pgnn_render_resolve turns keys into colours.
+//
+// Text (pgnn_render_text, "text" below) is a pass of its own over a finished
+// image, with a uint32 key plane and the 5 x 7 font of font5x7.h.
 #include <math.h>
 
+#include "font5x7.h"
 #include "pgnn_common.h"
 
 namespace {
@@ -283,6 +287,119 @@ __global__ void render_graph_segments_kernel(
   }
 }
 
+// ---- text ---------------------------------------------------------------------
+// A pass over a finished image with a key plane of its own: one uint32 per
+// pixel, (string + 1) << 1 | is_glyph, atomic max.  The later string wins
+// and, within a string, the glyph wins over the plate.
+__constant__ pgnn::Font5x7 d_font = pgnn::kFont5x7;
+
+constexpr int kAdvance = pgnn::kFontCols + 1;  // columns from glyph to glyph
+constexpr int kMaxScale = 4;
+
+__device__ __forceinline__ void put_key32(uint32_t *keys, int64_t pix,
+                                          uint32_t key) {
+  uint32_t cur = __hip_atomic_load(keys + pix, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+  if (cur >= key) return;
+  __hip_atomic_fetch_max(keys + pix, key, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void text_clear_kernel(uint32_t *keys, int64_t n) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    keys[i] = 0;
+}
+
+// One wave per string, its lanes over (glyph row, visible character) and then
+// over the pixels of the clipped plate: the work of a string is bounded by
+// the canvas, and a character left or right of it is never visited.
+__global__ __launch_bounds__(kBlock) void text_stamp_kernel(
+    const uint8_t *__restrict__ chars, const int32_t *__restrict__ offsets,
+    int64_t n_strings,
+    const int32_t *__restrict__ anchors, const uint8_t *__restrict__ scales,
+    int scale_uniform, int plates, int32_t w, int32_t h, uint32_t *keys) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  // chars holds offsets[n_strings] bytes: a string that ends beyond is dropped
+  const int64_t total = chars ? (int64_t)offsets[n_strings] : 0;
+  for (int64_t j = wave; j < n_strings; j += n_waves) {
+    const int64_t begin = offsets[j], end = offsets[j + 1];
+    if (begin < 0 || end <= begin || end > total) continue;  // empty, malformed
+    const int64_t s = scales ? (int64_t)scales[j] : (int64_t)scale_uniform;
+    if (s < 1 || s > kMaxScale) continue;
+    const int64_t n = end - begin;
+    const int64_t x = anchors[2 * j], y = anchors[2 * j + 1];
+    const int64_t adv = kAdvance * s;
+    const uint32_t key = (uint32_t)(j + 1) << 1;
+    // characters with a glyph column on the canvas:
+    //   x + i adv + 5 s > 0  and  x + i adv < w
+    if (y + pgnn::kFontRows * s > 0 && y < h) {
+      int64_t i_lo = floordiv64(-x - pgnn::kFontCols * s, adv) + 1;
+      int64_t i_hi = floordiv64((int64_t)w - 1 - x, adv);
+      if (i_lo < 0) i_lo = 0;
+      if (i_hi > n - 1) i_hi = n - 1;
+      const int64_t n_vis = i_hi - i_lo + 1;
+      for (int64_t item = lane; item < n_vis * pgnn::kFontRows; item += 64) {
+        const int r = (int)(item / n_vis);
+        const int64_t i = i_lo + item % n_vis;
+        const int64_t py0 = y + r * s;
+        if (py0 + s <= 0 || py0 >= h) continue;
+        int code = (int)chars[begin + i] - pgnn::kFontFirst;
+        if (code < 0 || code >= pgnn::kFontGlyphs) code = '?' - pgnn::kFontFirst;
+        const unsigned bits = d_font.rows[code][r];
+        for (int c = 0; c < pgnn::kFontCols; ++c) {
+          if (!(bits >> (pgnn::kFontCols - 1 - c) & 1u)) continue;
+          const int64_t px0 = x + (kAdvance * i + c) * s;
+          for (int64_t yy = py0; yy < py0 + s; ++yy) {
+            if (yy < 0 || yy >= h) continue;
+            for (int64_t xx = px0; xx < px0 + s; ++xx) {
+              if (xx < 0 || xx >= w) continue;
+              put_key32(keys, yy * w + xx, key | 1u);
+            }
+          }
+        }
+      }
+    }
+    if (plates) {
+      // [x - s, x + (6 n - 1) s + s) x [y - s, y + 7 s + s), cut to the canvas
+      int64_t x0 = x - s, x1 = x + kAdvance * n * s;
+      int64_t y0 = y - s, y1 = y + (pgnn::kFontRows + 1) * s;
+      if (x0 < 0) x0 = 0;
+      if (y0 < 0) y0 = 0;
+      if (x1 > w) x1 = w;
+      if (y1 > h) y1 = h;
+      if (x0 < x1 && y0 < y1) {
+        const int64_t cw = x1 - x0, area = cw * (y1 - y0);
+        for (int64_t p = lane; p < area; p += 64)
+          put_key32(keys, (y0 + p / cw) * w + (x0 + p % cw), key);
+      }
+    }
+  }
+}
+
+__global__ void text_resolve_kernel(const uint32_t *__restrict__ keys,
+                                    int64_t n_pix,
+                                    const uint8_t *__restrict__ colors,
+                                    int64_t n_colors,
+                                    const uint8_t *__restrict__ plate_colors,
+                                    int64_t n_plate_colors,
+                                    uint8_t *__restrict__ image) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_pix;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t key = keys[i];
+    if (key == 0) continue;  // no string owns the pixel: its bytes stay
+    const int64_t j = (int64_t)(key >> 1) - 1;
+    const uint8_t *c = (key & 1u) ? colors + (n_colors == 1 ? 0 : 3 * j)
+                                  : plate_colors +
+                                        (n_plate_colors == 1 ? 0 : 3 * j);
+    image[3 * i] = c[0];
+    image[3 * i + 1] = c[1];
+    image[3 * i + 2] = c[2];
+  }
+}
+
 unsigned grid_of(int64_t n) {
   int64_t g = (n + kBlock - 1) / kBlock;
   return (unsigned)(g < 1 ? 1 : g > kMaxGrid ? kMaxGrid : g);
@@ -478,6 +595,80 @@ extern "C" int pgnn_render_graph_segments(const float *src_xyz, int64_t n_src,
   hipLaunchKernelGGL(render_graph_segments_kernel, dim3(grid_of(2 * n_edges)),
                      dim3(kBlock), 0, stream, src_xyz, n_src, dst_xyz, n_dst,
                      edges, n_edges, segments);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+  PGNN_GUARD_END
+}
+
+namespace {
+
+size_t text_key_bytes(int32_t w, int32_t h) {
+  return pgnn::align_up((size_t)w * (size_t)h * sizeof(uint32_t), 256);
+}
+
+}  // namespace
+
+extern "C" size_t pgnn_render_text_workspace_bytes(int32_t width,
+                                                   int32_t height) {
+  if (!canvas_ok(width, height)) return 0;
+  return text_key_bytes(width, height);
+}
+
+extern "C" int pgnn_render_font(uint8_t *table_host) {
+  PGNN_GUARD_BEGIN
+  PGNN_REQUIRE(table_host, PGNN_E_INVALID, "render_font: null pointer");
+  for (int g = 0; g < pgnn::kFontGlyphs; ++g)
+    for (int r = 0; r < pgnn::kFontRows; ++r)
+      table_host[g * pgnn::kFontRows + r] = pgnn::kFont5x7.rows[g][r];
+  return 0;
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_render_text(uint8_t *image, int32_t width, int32_t height,
+                                const uint8_t *chars, const int32_t *offsets,
+                                int64_t n_strings, const int32_t *anchors,
+                                const uint8_t *scales, int32_t scale,
+                                const uint8_t *colors, int64_t n_colors,
+                                const uint8_t *plate_colors,
+                                int64_t n_plate_colors, void *workspace,
+                                size_t workspace_bytes, void *stream_) {
+  PGNN_GUARD_BEGIN
+  hipStream_t stream = (hipStream_t)stream_;
+  PGNN_REQUIRE(canvas_ok(width, height), PGNN_E_INVALID,
+               "render_text: width and height must be 1..4096");
+  PGNN_REQUIRE(scales || (scale >= 1 && scale <= kMaxScale), PGNN_E_INVALID,
+               "render_text: scale must be 1..4");
+  PGNN_REQUIRE(n_strings >= 0 && n_strings < (int64_t)1 << 30, PGNN_E_INVALID,
+               "render_text: n_strings must be 0..2^30-1");
+  PGNN_REQUIRE(n_colors == 1 || n_colors == n_strings, PGNN_E_INVALID,
+               "render_text: n_colors must be 1 or n_strings");
+  PGNN_REQUIRE(n_plate_colors == 0 || n_plate_colors == 1 ||
+                   n_plate_colors == n_strings,
+               PGNN_E_INVALID,
+               "render_text: n_plate_colors must be 0, 1 or n_strings");
+  PGNN_REQUIRE((colors || n_colors == 0) &&
+                   (plate_colors || n_plate_colors == 0),
+               PGNN_E_INVALID, "render_text: null pointer");
+  if (n_strings == 0) return 0;
+  PGNN_REQUIRE(image && offsets && anchors && workspace, PGNN_E_INVALID,
+               "render_text: null pointer");
+  PGNN_REQUIRE(workspace_bytes >= text_key_bytes(width, height),
+               PGNN_E_WORKSPACE,
+               "render_text: workspace too small "
+               "(see pgnn_render_text_workspace_bytes)");
+  uint32_t *keys = (uint32_t *)workspace;
+  int64_t n = (int64_t)width * height;
+  hipLaunchKernelGGL(text_clear_kernel, dim3(grid_of(n)), dim3(kBlock), 0,
+                     stream, keys, n);
+  PGNN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(text_stamp_kernel, dim3(grid_of(n_strings * 64)),
+                     dim3(kBlock), 0, stream, chars, offsets, n_strings,
+                     anchors, scales, (int)scale, (int)(n_plate_colors != 0),
+                     width, height, keys);
+  PGNN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(text_resolve_kernel, dim3(grid_of(n)), dim3(kBlock), 0,
+                     stream, (const uint32_t *)keys, n, colors, n_colors,
+                     plate_colors, n_plate_colors, image);
   PGNN_HIP(hipGetLastError());
   return 0;
   PGNN_GUARD_END

@@ -12,6 +12,11 @@ hard), with 11- and 40-point interpolation.  The protocol is DESIGN.md §9.5.
 
     python -m pointgnn_amd.kitti_eval LABEL_DIR RESULT_DIR [--split FILE] [--json]
         [--aos] [--alpha-from-box] [--min-overlap official|loose|<9 numbers>]
+        [--plot DIR]
+
+    write_pr_data(result, directory)     # <class>_detection.txt, ... 41 lines
+    image = plot_pr(result, '3d', 'Car')  # the three curves, drawn on the device
+    write_pr_plots(result, directory)
 
 A label is the dict of `kitti_dataset.read_label_file`; a detection carries
 `score` as well.
@@ -552,6 +557,166 @@ def evaluate_dataset(dataset, result_dir, classes=CLASSES, device=None,
     return evaluate(gt, det, classes, device, aos, det_alpha, min_overlap)
 
 
+# ---- precision / recall curves: data files and plots -------------------------
+ORIENTATION = 'orientation'     # the fourth file and plot, with has_aos
+CURVE_COLORS = ((0, 160, 0), (0, 0, 255), (255, 0, 0))   # easy, moderate, hard
+PLOT_MIN_SIZE = (160, 120)
+
+
+def _curve_key(metric):
+    """-> 0..2 (METRICS / REPORT_NAMES) or ORIENTATION."""
+    if isinstance(metric, str) and metric.lower() in (ORIENTATION, 'aos'):
+        return ORIENTATION
+    if isinstance(metric, str) and metric.lower() in REPORT_NAMES:
+        return REPORT_NAMES.index(metric.lower())
+    return _index(metric, METRICS, 'metric')
+
+
+def _curves(result, key, c):
+    """([3, 41] curve values, [3] R40 averages, file stem) of one class."""
+    if key == ORIENTATION:
+        if not result.has_aos:
+            raise ValueError("the result carries no orientation similarity")
+        return result.orientation[c], result.aos_r40[c], ORIENTATION
+    return result.precision[key, c], result.ap_r40[key, c], REPORT_NAMES[key]
+
+
+def _curve_keys(result):
+    return (0, 1, 2) + ((ORIENTATION,) if result.has_aos else ())
+
+
+def write_pr_data(result, directory):
+    """One file per class of the report and metric, named as the official
+    tool names them: <class>_detection.txt, _detection_ground.txt,
+    _detection_3d.txt and, when the result carries AOS, _orientation.txt.  41
+    lines "%f %f %f %f": the recall i / 40, then the easy, moderate and hard
+    value the result holds at that sample point (precision; orientation
+    similarity in the fourth file).  Returns the paths."""
+    os.makedirs(directory, exist_ok=True)
+    paths = []
+    for cls in result.classes:
+        c = CLASSES.index(cls)
+        for key in _curve_keys(result):
+            values, _, stem = _curves(result, key, c)
+            path = os.path.join(directory, '%s_%s.txt' % (cls.lower(), stem))
+            with open(path, 'w') as f:
+                for i in range(N_SAMPLE_PTS):
+                    f.write('%f %f %f %f\n' % (
+                        i / (N_SAMPLE_PTS - 1.0), values[0, i], values[1, i],
+                        values[2, i]))
+            paths.append(path)
+    return paths
+
+
+def plot_area(width=640, height=480):
+    """(x0, y0, x1, y1): the pixels of the axis box of a plot_pr image.  A
+    recall r in [0, 1] is drawn in column x(r) = x0 + floor(r * (x1 - x0)), a
+    precision p in row y(p) = y1 - floor(p * (y1 - y0))."""
+    width, height = int(width), int(height)
+    if width < PLOT_MIN_SIZE[0] or height < PLOT_MIN_SIZE[1] or \
+            width > 4096 or height > 4096:
+        raise ValueError("a plot is %d x %d .. 4096 x 4096, got %d x %d" % (
+            PLOT_MIN_SIZE + (width, height)))
+    return 40, 28, width - 16, height - 30
+
+
+def plot_x(area, r):
+    return area[0] + int(np.floor(r * (area[2] - area[0])))
+
+
+def plot_y(area, p):
+    return area[3] - int(np.floor(p * (area[3] - area[1])))
+
+
+def plot_pr(result, metric, cls, width=640, height=480):
+    """The curves of one class and metric ('2d' / 'bev' / '3d', a report name,
+    or 'orientation') as a CUDA uint8 [height, width, 3] image: white ground,
+    the axis box of plot_area with ticks and labels 0.0 .. 1.0 every 0.2, the
+    easy, moderate and hard curve in CURVE_COLORS as polylines through the 41
+    sample points (drawn in that order: hard is on top), a title naming class
+    and metric and, in the lower left of the box, the three R40 averages in
+    percent in their curve's colour.  A NaN value breaks the curve there."""
+    from . import render as R
+    key = _curve_key(metric)
+    c = _index(cls, CLASSES, 'class')
+    values, averages, stem = _curves(result, key, c)
+    area = plot_area(width, height)
+    x0, y0, x1, y1 = area
+    black = (0, 0, 0)
+    segs, cols = [], []
+
+    def line(xa, ya, xb, yb, color):
+        segs.append(((xa, ya, 0.0), (xb, yb, 0.0)))
+        cols.append(color)
+    for xa, ya, xb, yb in ((x0, y0, x1, y0), (x1, y0, x1, y1),
+                           (x1, y1, x0, y1), (x0, y1, x0, y0)):
+        line(xa, ya, xb, yb, black)
+    ticks = [k / 5.0 for k in range(6)]
+    strings, anchors, colors = [], [], []
+
+    def write(string, x, y, color=black, scale=1):
+        strings.append((string, scale))
+        anchors.append((x, y))
+        colors.append(color)
+    for t in ticks:
+        label = '%.1f' % t
+        tw, th = R.text_size(label)
+        x, y = plot_x(area, t), plot_y(area, t)
+        line(x, y1, x, y1 + 4, black)
+        line(x0 - 4, y, x0, y, black)
+        write(label, x - tw // 2, y1 + 7)
+        write(label, x0 - 7 - tw, y - th // 2)
+    for d in range(3):
+        xs = [plot_x(area, i / (N_SAMPLE_PTS - 1.0))
+              for i in range(N_SAMPLE_PTS)]
+        for i in range(N_SAMPLE_PTS - 1):
+            a, b = float(values[d, i]), float(values[d, i + 1])
+            if not (np.isfinite(a) and np.isfinite(b)):
+                continue
+            a, b = min(max(a, 0.0), 1.0), min(max(b, 0.0), 1.0)
+            line(xs[i], plot_y(area, a), xs[i + 1], plot_y(area, b),
+                 CURVE_COLORS[d])
+    image = R.render(R.pixel_view(width, height),
+                     segments=np.array(segs, dtype=np.float64),
+                     segment_colors=np.array(cols, dtype=np.uint8),
+                     background=(255, 255, 255))
+    write('%s %s' % (CLASSES[c], stem), x0, 6, scale=2)
+    write('Precision' if key != ORIENTATION else 'Orientation', 2, y0 - 9)
+    tw, _ = R.text_size('Recall')
+    write('Recall', (x0 + x1 - tw) // 2, y1 + 18)
+    for d in range(3):
+        write('%-8s %6.2f' % (DIFFICULTIES[d], 100.0 * averages[d]),
+              x0 + 8, y1 - 36 + 10 * d, CURVE_COLORS[d])
+    return R.draw_text(image, [s for s, _ in strings], anchors,
+                       colors=np.array(colors, dtype=np.uint8),
+                       scale=np.array([k for _, k in strings], dtype=np.uint8),
+                       anchor='tl')
+
+
+def write_pr_plots(result, directory, fmt='png'):
+    """plot_pr of every class of the report and metric that has ground truth,
+    as <directory>/<class>_<report name>.<fmt>, fmt 'png' or 'ppm'.  Returns
+    the paths."""
+    from . import render as R
+    if fmt not in ('png', 'ppm'):
+        raise ValueError("fmt must be 'png' or 'ppm', got %r" % (fmt,))
+    os.makedirs(directory, exist_ok=True)
+    paths = []
+    for cls in result.classes:
+        c = CLASSES.index(cls)
+        for key in _curve_keys(result):
+            m = 0 if key == ORIENTATION else key
+            if not int(np.sum(result.n_gt[m, c])):
+                continue
+            stem = ORIENTATION if key == ORIENTATION else REPORT_NAMES[key]
+            path = os.path.join(directory, '%s_%s.%s' % (
+                cls.lower(), stem, fmt))
+            image = plot_pr(result, key, c)
+            (R.write_png if fmt == 'png' else R.write_ppm)(path, image)
+            paths.append(path)
+    return paths
+
+
 def parse_args(argv=None):
     import argparse
     ap = argparse.ArgumentParser(
@@ -572,6 +737,10 @@ def parse_args(argv=None):
                     default=None,
                     help="official (default), loose (BEV and 3D at 0.5 / 0.25 "
                          "/ 0.25) or 9 comma-separated numbers [metric][class]")
+    ap.add_argument('--plot', metavar='DIR', default=None,
+                    help="write the precision/recall data files "
+                         "(<class>_detection.txt, ...) and one plot per class "
+                         "and metric into DIR")
     return ap.parse_args(argv)
 
 
@@ -586,6 +755,9 @@ def main(argv=None):
                            det_alpha='box' if args.alpha_from_box else 'file',
                            min_overlap=args.min_overlap)
     print(result.format())
+    if args.plot:
+        write_pr_data(result, args.plot)
+        write_pr_plots(result, args.plot)
     if args.json:
         print(json.dumps(result.to_json()))
     return 0

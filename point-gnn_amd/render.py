@@ -5,15 +5,19 @@ into uint8 RGB images on the device and written as PNG or PPM files.
 The rasteriser (csrc/render.hip, include/pointgnn_hip.h "rendering") has
 defined, integer-exact semantics: points with a depth test, line segments with
 a fixed midpoint rule and the later segment on top, segments over points over
-the background.  Not drawn: text (`cv2.putText`: there is no font) and the
-interactive 3D window.
+the background.  Text (`cv2.putText`) is a pass over a finished image,
+`draw_text`, with the library's own 5 x 7 bitmap font; `render_frame(...,
+text=True)` writes the reference's 'P | 0.873' beside every detection.  Not
+drawn: the interactive 3D window.
 
     view = bev_view()                                 # 800 x 800, forward is up
     img = render(view, points=xyz, point_colors=colorize(inten, 0, 1),
                  segments=box_segments(boxes), segment_colors=(255, 0, 0))
     write_png('frame.png', img)
+    draw_text(img, ['C | 0.912'], [(40, 120)], colors=(0, 255, 0))
     render_results(dataset, result_dir, render_dir, views=('bev', 'camera'))
     python -m pointgnn_amd.render DATASET_DIR RESULT_DIR RENDER_DIR --view bev
+        [--text]
 
 NumPy arrays or CUDA tensors go in, a uint8 [H, W, 3] CUDA tensor comes out.
 """
@@ -46,6 +50,8 @@ GT_COLORS = {
 }
 DETECTION_COLOR = (255, 0, 0)    # boxes_3d_to_line_set's default colour
 RECT_COLOR = (0, 255, 0)         # run.py:411-413
+# cv2.putText's colours of run.py:417 / :421, BGR there: [is a Pedestrian]
+DETECTION_TEXT_COLORS = ((0, 255, 0), (0, 255, 255))
 
 # the twelve edges of a box, kitti_dataset.py:807-810
 BOX_EDGES = np.array([[0, 1], [0, 4], [0, 3], [1, 2], [1, 5], [2, 3],
@@ -284,6 +290,140 @@ def render(view, points=None, point_colors=None, point_size=1, segments=None,
     return image
 
 
+# ---- text ----------------------------------------------------------------------------
+FONT_FIRST, FONT_GLYPHS, FONT_ROWS, FONT_COLS = 0x20, 95, 7, 5
+MAX_SCALE = 4
+_I32_MIN, _I32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def font_table():
+    """The library's font (pgnn_render_font): uint8 [95, 7], one row mask per
+    byte for the codes 0x20..0x7E; bit 4 is the leftmost of the 5 columns,
+    row 0 the top.  Read from the library: there is no copy here."""
+    out = np.zeros((FONT_GLYPHS, FONT_ROWS), dtype=np.uint8)
+    _lib.check(_lib.load().pgnn_render_font(_host_ptr(out)),
+               "pgnn_render_font")
+    return out
+
+
+def _check_scale(scale):
+    if isinstance(scale, bool) or int(scale) != scale or \
+            not 1 <= scale <= MAX_SCALE:
+        raise ValueError("scale must be 1..%d, got %r" % (MAX_SCALE, scale))
+    return int(scale)
+
+
+def text_size(string, scale=1):
+    """(width, height) in pixels of `string` drawn at `scale`:
+    ((6 len - 1) scale, 7 scale); (0, 0) for an empty string."""
+    scale = _check_scale(scale)
+    n = len(string)
+    return ((6 * n - 1) * scale, 7 * scale) if n else (0, 0)
+
+
+def _text_bytes(s):
+    if isinstance(s, (bytes, bytearray)):
+        return bytes(s)
+    if isinstance(s, str):
+        return s.encode('latin-1', errors='replace')
+    raise ValueError("strings are str or bytes, got %r" % (s,))
+
+
+def draw_text(image, strings, anchors, colors=(255, 255, 255), scale=1,
+              plate=None, anchor='bl'):
+    """Draws `strings` into `image` (a CUDA uint8 [H, W, 3] tensor, modified
+    IN PLACE and returned) with the built-in 5 x 7 font, as cv2.putText draws
+    into its image (include/pointgnn_hip.h, "text").  strings: a list of str
+    (encoded latin-1, what it cannot encode becomes '?') or bytes; anchors
+    [n, 2] integer (x, y): with anchor='bl' the bottom left of the text, cv2's
+    `org` (the top left is (x, y - 7 scale)), with 'tl' its top left.  scale:
+    1..4, one value or one per string; colors: one colour or [n, 3]; plate:
+    None, one colour or [n, 3] -- a filled rectangle one `scale` wider than
+    the text on every side, under its glyphs.  Later strings cover earlier
+    ones.  Nothing is read back."""
+    import torch
+    lib = _lib.load()
+    if not (isinstance(image, torch.Tensor) and image.is_cuda and
+            image.dtype == torch.uint8 and image.dim() == 3 and
+            image.shape[2] == 3 and image.is_contiguous()):
+        raise ValueError("image must be a contiguous CUDA uint8 [H, W, 3] "
+                         "tensor, got %r" % (
+                             (image.dtype, tuple(image.shape))
+                             if isinstance(image, torch.Tensor)
+                             else type(image),))
+    h, w = int(image.shape[0]), int(image.shape[1])
+    if not (1 <= w <= MAX_DIM and 1 <= h <= MAX_DIM):
+        raise ValueError("canvas %d x %d: width and height must be 1..%d" % (
+            w, h, MAX_DIM))
+    if anchor not in ('bl', 'tl'):
+        raise ValueError("anchor must be 'bl' or 'tl', got %r" % (anchor,))
+    if isinstance(strings, (str, bytes, bytearray)):
+        raise ValueError("strings must be a list of str or bytes")
+    data = [_text_bytes(s) for s in strings]
+    n = len(data)
+    dev = image.device
+    if isinstance(anchors, torch.Tensor):
+        anc = anchors.to(device=dev, dtype=torch.int64)
+    else:
+        a = np.asarray(anchors)
+        if a.size and a.dtype.kind not in 'iu':
+            raise ValueError("anchors must be integers, got %s" % a.dtype)
+        if a.size and (a.min() < _I32_MIN or a.max() > _I32_MAX):
+            raise ValueError("anchors must fit int32, got %d .. %d" % (
+                a.min(), a.max()))
+        anc = torch.from_numpy(np.ascontiguousarray(
+            a.astype(np.int64))).to(dev)
+    if anc.numel() != 2 * n:
+        raise ValueError("anchors must be [%d, 2], got shape %r" % (
+            n, tuple(anc.shape)))
+    anc = anc.reshape(n, 2)
+    scale_t, scale_1 = None, 1
+    if isinstance(scale, (int, np.integer)):
+        scale_1 = _check_scale(scale)
+    else:
+        if not isinstance(scale, torch.Tensor):
+            a = np.asarray(scale)
+            if a.size and (a.min() < 1 or a.max() > MAX_SCALE):
+                raise ValueError("scale values must be 1..%d, got %d .. %d" % (
+                    MAX_SCALE, a.min(), a.max()))
+            scale = torch.from_numpy(np.ascontiguousarray(a.astype(np.uint8)))
+        scale_t = scale.to(device=dev, dtype=torch.uint8).reshape(
+            -1).contiguous()
+        if int(scale_t.shape[0]) != n:
+            raise ValueError("scale must be one value or [%d], got %d" % (
+                n, int(scale_t.shape[0])))
+    col, n_col = _colors(colors, n, dev, "colors")
+    plate_t, n_plate = None, 0
+    if plate is not None:
+        plate_t, n_plate = _colors(plate, n, dev, "plate")
+    lengths = np.array([len(d) for d in data], dtype=np.int64)
+    total = int(lengths.sum())
+    if total > _I32_MAX:
+        raise ValueError("%d characters: the total must be below 2^31" % total)
+    if n == 0 or total == 0:
+        return image
+    if anchor == 'bl':
+        anc = anc.clone()
+        anc[:, 1] -= FONT_ROWS * (scale_t.to(torch.int64)
+                                  if scale_t is not None else scale_1)
+    # a top edge below int32 is far off the canvas either way
+    anc = anc.clamp(_I32_MIN, _I32_MAX).to(torch.int32).contiguous()
+    offsets = np.zeros(n + 1, dtype=np.int32)
+    np.cumsum(lengths, out=offsets[1:])
+    chars = torch.from_numpy(np.frombuffer(b"".join(data), dtype=np.uint8)
+                             .copy()).to(dev)
+    offsets = torch.from_numpy(offsets).to(dev)
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.pgnn_render_text_workspace_bytes(w, h))
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        _lib.check(lib.pgnn_render_text(
+            _lib.ptr(image), w, h, _lib.ptr(chars), _lib.ptr(offsets), n,
+            _lib.ptr(anc), _lib.ptr(scale_t), scale_1, _lib.ptr(col),
+            n_col, _lib.ptr(plate_t), n_plate, _lib.ptr(ws),
+            ws_bytes, _lib.stream_ptr()), "pgnn_render_text")
+    return image
+
+
 # ---- segments of boxes, rectangles and graphs ----------------------------------
 def box_corners(boxes_3d):
     """[m, 7] (x, y, z, l, h, w, yaw) -> [m, 8, 3] float64, the corners of
@@ -485,9 +625,70 @@ def frame_view(dataset, frame_idx, view, calib=None):
     raise ValueError("view must be 'bev', 'camera' or a View, got %r" % (view,))
 
 
+def detection_string(label):
+    """run.py:414-421: 'P | 0.873' for a Pedestrian, 'C | 0.912' for every
+    other class."""
+    return '%s | %.3f' % ('P' if label['name'] == 'Pedestrian' else 'C',
+                          label['score'])
+
+
+def center_pixel(view, label):
+    """The pixel of a label's box centre (x3d, y3d, z3d) under `view`, by the
+    header's float64 formula (floor(hu / hw), floor(hv / hw)); None when the
+    centre is not visible or its pixel is off the canvas."""
+    x, y, z = float(label['x3d']), float(label['y3d']), float(label['z3d'])
+    rows = np.asarray(view.m, dtype=np.float64).reshape(3, 4).tolist() + \
+        [np.asarray(view.d, dtype=np.float64).reshape(4).tolist()]
+    # Python floats are IEEE float64: the header's sums, in its order
+    hu, hv, hw, dep = (((r[0] * x + r[1] * y) + r[2] * z) + r[3]
+                       for r in rows)
+    if not all(math.isfinite(t) for t in (hu, hv, hw, dep)):
+        return None
+    if not hw >= view.near or hw == 0.0:   # x / 0 is on no canvas
+        return None
+    u, w = hu / hw, hv / hw
+    if not (0.0 <= u < view.width and 0.0 <= w < view.height):
+        return None                        # floor keeps both comparisons
+    return int(math.floor(u)), int(math.floor(w))
+
+
+def frame_text(det_labels, gt_labels, view, camera):
+    """What render_frame(text=True) writes: (strings, anchors [n, 2], colors
+    [n, 3]) for draw_text(anchor='bl').  Ground truth names first (the labels
+    whose wireframe is drawn, in its colour), detections after them (so they
+    win overlaps): detection_string in DETECTION_TEXT_COLORS.  camera: the
+    anchors are the reference's, org = (int(xmin), int(ymin)), a Pedestrian
+    detection's int(xmin / 10) higher (run.py:414-421, vis_draw_2d_box);
+    otherwise center_pixel(view, label), and a label without one gets no
+    string."""
+    det_labels, gt_labels = as_labels(det_labels), as_labels(gt_labels)
+    strings, anchors, colors = [], [], []
+
+    def add(string, label, color, lift):
+        if camera:
+            org = (int(label['xmin']), int(label['ymin']) - lift)
+        else:
+            org = center_pixel(view, label)
+            if org is None:
+                return
+        strings.append(string)
+        anchors.append(org)
+        colors.append(color)
+    for l in gt_labels:
+        if l['name'] in GT_COLORS:
+            add(l['name'], l, GT_COLORS[l['name']], 0)
+    for l in det_labels:
+        ped = l['name'] == 'Pedestrian'
+        add(detection_string(l), l, DETECTION_TEXT_COLORS[ped],
+            int(l['xmin'] / 10) if ped and camera else 0)
+    return (strings, np.array(anchors, dtype=np.int64).reshape(-1, 2),
+            np.array(colors, dtype=np.uint8).reshape(-1, 3))
+
+
 def render_frame(dataset, frame_idx, det_labels=None, gt_labels=None,
                  view='bev', stages=None, color_by='intensity',
-                 show_graph=False, background=None):
+                 show_graph=False, background=None, text=False,
+                 text_plate=None):
     """One frame of `dataset`: the cloud cropped to the camera image (coloured
     by 'intensity', 'height', or by 'class' on the last level's vertices),
     ground truth wireframes in GT_COLORS (labels filtered like run.py:438-444),
@@ -495,8 +696,9 @@ def render_frame(dataset, frame_idx, det_labels=None, gt_labels=None,
     in (0, 255, 0) at thickness 2 (run.py:411-413).  stages: the second result
     of run.detect_frame; it supplies the points and allows color_by='class'
     and show_graph (the last level's edges into the vertices of the kept
-    boxes, run.py:339-350).  Text is not drawn.  -> uint8 [H, W, 3] CUDA
-    tensor."""
+    boxes, run.py:339-350).  text: also the strings of frame_text, drawn last
+    with draw_text (scale 1, anchor='bl'; text_plate: a plate colour under
+    them); without it no text pass runs.  -> uint8 [H, W, 3] CUDA tensor."""
     calib = stages['calib'] if stages is not None else None
     v = frame_view(dataset, frame_idx, view, calib)
     points = stages['points'] if stages is not None else \
@@ -514,6 +716,12 @@ def render_frame(dataset, frame_idx, det_labels=None, gt_labels=None,
                        segments=rect_segments(det_labels),
                        segment_colors=RECT_COLOR, thickness=2,
                        background=image)
+    if text:
+        strings, anchors, colors = frame_text(det_labels, gt_labels, v,
+                                              view == 'camera')
+        if strings:
+            draw_text(image, strings, anchors, colors=colors, scale=1,
+                      plate=text_plate, anchor='bl')
     return image
 
 
@@ -575,14 +783,16 @@ def image_background(dataset):
 
 def render_results(dataset, result_dir, render_dir, views=('bev',),
                    frame_indices=None, fmt='png', with_gt=True,
-                   background_reader=None, time_dict=None):
+                   background_reader=None, time_dict=None, text=False,
+                   text_plate=None):
     """Draws every frame of a result directory (<result_dir>/<name>.txt as
     run.run_dataset writes them under <output_dir>/data, or any other KITTI
     result directory) into <render_dir>/<view>/<name>.<fmt>, fmt 'png' or
     'ppm'.  with_gt: also the labels, when the dataset has a label directory.
     background_reader(frame_idx) -> uint8 RGB [H, W, 3] for the camera view
     (image_background(dataset): the frame's own PNG, decoded on the device).
-    Sequential: one host read per image.  Returns the paths written."""
+    text / text_plate: render_frame's.  Sequential: one host read per image.
+    Returns the paths written."""
     from . import kitti_eval
     import time
     if fmt not in ('png', 'ppm'):
@@ -612,7 +822,8 @@ def render_results(dataset, result_dir, render_dir, views=('bev',),
             if view == 'camera' and background_reader is not None:
                 background = background_reader(frame_idx)
             image = render_frame(dataset, frame_idx, det, gt, view=view,
-                                 stages=stages, background=background)
+                                 stages=stages, background=background,
+                                 text=text, text_plate=text_plate)
             host = image.cpu().numpy()
             t1 = time.time()
             path = os.path.join(render_dir, view, name + '.' + fmt)
@@ -655,6 +866,9 @@ def build_parser():
     ap.add_argument('--image-background', action='store_true',
                     help="camera view: draw on the frame's decoded image "
                          "instead of black")
+    ap.add_argument('--text', action='store_true',
+                    help="write every detection's class letter and score "
+                         "('P | 0.873') and every drawn label's name")
     return ap
 
 
@@ -673,7 +887,8 @@ def main(argv=None):
                            views=tuple(args.view or ('bev',)),
                            fmt='ppm' if args.ppm else 'png',
                            background_reader=image_background(dataset)
-                           if args.image_background else None)
+                           if args.image_background else None,
+                           text=args.text)
     print("wrote %d images to %s" % (len(paths), args.render_dir))
     return 0
 
