@@ -21,9 +21,9 @@ import time
 
 import torch
 
-from . import _lib
+from . import _header, _lib
 
-ID_BYTES = 128   # PGNN_COMM_ID_BYTES
+ID_BYTES = _header.constants()["PGNN_COMM_ID_BYTES"]
 
 __all__ = ["Communicator", "ID_BYTES"]
 

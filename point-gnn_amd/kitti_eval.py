@@ -35,7 +35,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _header, _lib
 from . import kitti_dataset
 
 CLASSES = ('Car', 'Pedestrian', 'Cyclist')
@@ -43,11 +43,10 @@ METRICS = ('2d', 'bev', '3d')
 DIFFICULTIES = ('easy', 'moderate', 'hard')
 # the official tool's names of the three metrics in its report lines
 REPORT_NAMES = ('detection', 'detection_ground', 'detection_3d')
-ROW = 14            # PGNN_KITTI_ROW
-N_SAMPLE_PTS = 41   # PGNN_KITTI_SAMPLE_PTS
-N_COMBOS = 27       # PGNN_KITTI_COMBOS
-MAX_DET = 1024      # PGNN_KITTI_MAX_DET
-MAX_GT = 1024       # PGNN_KITTI_MAX_GT
+_C = _header.constants()
+ROW, N_SAMPLE_PTS, N_COMBOS = (_C["PGNN_KITTI_ROW"], _C["PGNN_KITTI_SAMPLE_PTS"],
+                               _C["PGNN_KITTI_COMBOS"])
+MAX_DET, MAX_GT = _C["PGNN_KITTI_MAX_DET"], _C["PGNN_KITTI_MAX_GT"]
 # MIN_OVERLAP[metric][class] (METRICS, CLASSES); the official table is what
 # pgnn_kitti_eval has compiled in
 OFFICIAL_MIN_OVERLAP = ((0.7, 0.5, 0.5),) * 3

@@ -29,9 +29,9 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _lib
+from . import _header, _lib
 
-MAX_DIM = 4096   # PGNN_RENDER_MAX_DIM
+MAX_DIM = _header.constants()["PGNN_RENDER_MAX_DIM"]
 
 # run.py:176-178 (there divided by 255 for open3d)
 CLASS_COLORS = np.array([(211, 211, 211), (255, 0, 0), (255, 20, 147),

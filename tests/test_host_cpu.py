@@ -187,6 +187,13 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), "missing export: " + name
     # the Python binding covers the header (plus the tuning hook)
     assert declared <= set(L.exported_symbols())
+    # ... through the header reader, which must find the same names as this
+    # cruder parse and whose types are what the loaded functions carry
+    from pointgnn_amd import _header
+    assert declared == set(_header.functions())
+    for name, (res, args) in _header.functions().items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
     assert lib.pgnn_version() >= 100
 
 
