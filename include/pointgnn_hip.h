@@ -1858,6 +1858,59 @@ int pgnn_beam_select(const float *velo_points, int64_t n_points,
                      size_t workspace_bytes, float *out_points,
                      int32_t *out_count, void *stream);
 
+/* ---- farthest-point sampling (dataset/kitti_dataset.py:630-641:
+ * KittiDataset.farthest_first with its helper calc_distances).
+ * For one cloud pts [n, 3] (float32, or _f64 float64), a start index s and a
+ * count k, a pure function of the input bits:
+ *   d_j    = (dx*dx + dy*dy) + dz*dz with dx = p_s.x - p_j.x, ...: float64, one
+ *            rounding per operation, nothing contracted; float32 coordinates
+ *            are widened first (what :631 computes on a [n, 3] array)
+ *   pick_0 = s
+ *   pick_i = smallest j with d_j == max(d)               (np.argmax, :638)
+ *   d_j    = min(d_j, dist(pick_i, j))                   (np.minimum, :639)
+ * k > n, duplicate points and all-equal clouds follow from these rules: once
+ * max(d) == 0 every later pick is index 0, and the kernel stops iterating there
+ * and fills the tail.  num_distinct = the smallest i >= 1 whose round found
+ * max(d) == 0, or k when there is none: picks [0, num_distinct) are pairwise
+ * non-coincident.
+ * Segmented form: offsets int32 [n_segments + 1] (device) over the concatenated
+ * cloud, start int32 [n_segments] (device, indices LOCAL to the segment), one
+ * k.  out_idx int32 [n_segments, k] local indices, out_xyz (nullable)
+ * [n_segments, k, 3] the picked rows copied bit for bit in the input dtype,
+ * num_distinct int32 [n_segments].  An empty segment writes -1, zero rows and
+ * num_distinct 0.  offsets == NULL with n_segments == 1 is the single cloud
+ * [0, n_points).  k == 0 or n_points == 0 write nothing but num_distinct.
+ * A start index outside its segment is the caller's error (the host cannot see
+ * it here); the kernel clamps it into the segment and never reads out of
+ * range.  Rows with a non-finite coordinate are outside the contract, as for
+ * the reference; the kernel terminates and every index it writes lies in
+ * [0, n).
+ * One workgroup of PGNN_FPS_BLOCK threads per segment, persistent over the k
+ * rounds, workgroup barriers only.  A segment of at most PGNN_FPS_RESIDENT
+ * (float32) / PGNN_FPS_RESIDENT_F64 (float64) points keeps coordinates and
+ * running distances on chip (registers, part of the distances in LDS); a
+ * larger one streams its coordinates every round and keeps the distances in
+ * the workspace (pgnn_farthest_first_workspace_bytes: 8 bytes per point of a
+ * cloud above the smaller limit, else 0).  No host read, one launch.
+ * PGNN_E_INVALID: null pointer, negative size, offsets == NULL with
+ * n_segments != 1, n_points >= 2^31. */
+#define PGNN_FPS_BLOCK 512
+#define PGNN_FPS_RESIDENT (40 * PGNN_FPS_BLOCK)
+#define PGNN_FPS_RESIDENT_F64 (20 * PGNN_FPS_BLOCK)
+size_t pgnn_farthest_first_workspace_bytes(int64_t n_points,
+                                           int64_t n_segments, int32_t k);
+int pgnn_farthest_first(const float *points, const int32_t *offsets,
+                        int64_t n_segments, int64_t n_points,
+                        const int32_t *start, int32_t k, void *workspace,
+                        size_t workspace_bytes, int32_t *out_idx,
+                        float *out_xyz, int32_t *num_distinct, void *stream);
+int pgnn_farthest_first_f64(const double *points, const int32_t *offsets,
+                            int64_t n_segments, int64_t n_points,
+                            const int32_t *start, int32_t k, void *workspace,
+                            size_t workspace_bytes, int32_t *out_idx,
+                            double *out_xyz, int32_t *num_distinct,
+                            void *stream);
+
 /* ---- rendering: the frame, its boxes and its graph drawn into an image on
  * the device (run.py -l 1|2: :152-175 the open3d window, :328-359 the cloud and
  * the graph edges into the kept vertices, :410-421 cv2.rectangle per detection,

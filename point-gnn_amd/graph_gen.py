@@ -35,7 +35,7 @@ __all__ = ["gen_disjointed_rnn_local_graph_v3",
            "gen_disjointed_knn_local_graph_v3", "knn_graph_device",
            "gen_multi_level_local_graph_v3", "get_graph_generate_fn",
            "multi_layer_downsampling_select", "multi_layer_downsampling_random",
-           "gen_multi_level_local_graph_v3_one_read",
+           "gen_multi_level_local_graph_v3_one_read", "keypoint_counts",
            "CountHints", "FrameCounts", "merge_frames_dyn"]
 
 
@@ -762,10 +762,54 @@ def kdtree_replica(points):
     return idx, bounds, int(status.item())
 
 
+def keypoint_counts(num_keypoints, levels):
+    """`num_keypoints` of downsample_method='farthest' -> {level index: count}
+    for the pooling levels of `levels` (the graph scales; a level whose scale
+    equals the previous one keeps its vertices): one int for all of them, or
+    one int per pooling level, in level order."""
+    pooling, last_level = [], 0
+    for li, level in enumerate(levels):
+        if not np.isclose(last_level, level):
+            pooling.append(li)
+        last_level = level
+    if num_keypoints is None:
+        raise ValueError("downsample_method='farthest' needs num_keypoints")
+
+    def count(v):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError("num_keypoints must be positive integers, got %r"
+                             % (num_keypoints,))
+        return int(v)
+    if isinstance(num_keypoints, (list, tuple, np.ndarray)):
+        if len(num_keypoints) != len(pooling):
+            raise ValueError("num_keypoints: %d counts for %d pooling levels"
+                             % (len(num_keypoints), len(pooling)))
+        return {li: count(v) for li, v in zip(pooling, num_keypoints)}
+    return {li: count(num_keypoints) for li in pooling}
+
+
+def _farthest_keypoints(base, count):
+    """One pooling level of downsample_method='farthest': min(count, n)
+    farthest-first picks of `base` (kitti_dataset.py:633-641 on the device,
+    sampling.py), truncated where the picks start to coincide.  The start index
+    is drawn from NumPy's global RNG, as the 'random' method draws its seeds.
+    Host-sized form: one read (num_distinct)."""
+    from . import sampling
+    n = int(base.shape[0])
+    k = min(int(count), n)
+    start = np.random.randint(n) if n > 0 else 0
+    st = torch.tensor([start], dtype=torch.int32, device=base.device)
+    idx, xyz, num = sampling.launch(base.contiguous(), None, st, k)
+    nd = int(num.item())   # the one host read
+    return xyz[0, :nd], idx[0, :nd].reshape(nd, 1)
+
+
 def _multi_layer_downsampling(points_xyz, base_voxel_size, levels, add_rnd3d,
                               method, num_out=None, k_hint=0,
-                              fork_kdtree=False):
+                              fork_kdtree=False, num_keypoints=None):
     p, was_np = _to_dev(points_xyz)
+    counts = keypoint_counts(num_keypoints, levels) \
+        if method == 'farthest' else {}
     coords = [p]
     kp_list = []
     # 'random': the origin jitters of the pooling levels are drawn from NumPy's
@@ -795,6 +839,11 @@ def _multi_layer_downsampling(points_xyz, base_voxel_size, levels, add_rnd3d,
             kp_list.append(_lib.tag_count(
                 _identity_indices(int(base.shape[0]), base.device),
                 _lib.count_of(base)))
+        elif method == 'farthest':
+            # the level's voxel size is unused; indices refer to `base`
+            c, i = _farthest_keypoints(base, counts[li])
+            coords.append(c)
+            kp_list.append(i)
         else:
             # (a pooling level above the first: the cloud still anchors the
             # voxel grid, graph_gen.py:41-45 / :108-110; the previous level's
@@ -852,9 +901,17 @@ def multi_layer_downsampling_random(points_xyz, base_voxel_size, levels=[1],
 
 def gen_multi_level_local_graph_v3(points_xyz, base_voxel_size, level_configs,
                                    add_rnd3d=False, downsample_method='center',
-                                   deferred_counts=None, overlap_build=False):
+                                   deferred_counts=None, overlap_build=False,
+                                   num_keypoints=None):
     """graph_gen.py:155-195.  Returns (vertex_coord_list,
     keypoint_indices_list, edges_list).
+
+    downsample_method='farthest' (extension) with `num_keypoints`, an int or
+    one int per pooling level: a pooling level keeps min(num_keypoints, N)
+    farthest-first picks of the previous level's vertices
+    (kitti_dataset.py:633-641, sampling.py) instead of one vertex per occupied
+    voxel; its voxel size is unused and `add_rnd3d` has no voxel origin to
+    jitter.  Host-sized form only.
 
     `deferred_counts` (extension; a CountHints, device tensors only): the
     capacity form.  Nothing is read back while the graph is built -- the
@@ -872,14 +929,24 @@ def gen_multi_level_local_graph_v3(points_xyz, base_voxel_size, level_configs,
     if isinstance(base_voxel_size, list):
         base_voxel_size = np.array(base_voxel_size)
     scales = [cfg['graph_scale'] for cfg in level_configs]
-    if downsample_method not in ('center', 'random'):
+    if downsample_method not in ('center', 'random', 'farthest'):
         raise ValueError("unknown downsample_method %r" % (downsample_method,))
+    if downsample_method == 'farthest':
+        keypoint_counts(num_keypoints, scales)   # ValueError before any work
+        if deferred_counts is not None:
+            raise NotImplementedError(
+                "deferred_counts: downsample_method 'farthest' has no "
+                "capacity form")
+    elif num_keypoints is not None:
+        raise ValueError("num_keypoints belongs to downsample_method="
+                         "'farthest', not %r" % (downsample_method,))
     if deferred_counts is not None:
         return _multi_level_graph_deferred(
             points_xyz, base_voxel_size, level_configs, scales, add_rnd3d,
             downsample_method, deferred_counts, overlap_build)
     coords, kps, was_np = _multi_layer_downsampling(
-        points_xyz, base_voxel_size, scales, add_rnd3d, downsample_method)
+        points_xyz, base_voxel_size, scales, add_rnd3d, downsample_method,
+        num_keypoints=num_keypoints)
     edges_list = []
     batched = not was_np and all(
         cfg['graph_gen_method'] == 'disjointed_rnn_local_graph_v3' and

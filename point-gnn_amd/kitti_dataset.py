@@ -348,6 +348,33 @@ class KittiDataset(object):
             cam = downsample_by_average_voxel(cam, downsample_voxel_size)
         return cam
 
+    def calc_distances(self, p0, points):
+        """kitti_dataset.py:630-631 on the host: squared distance of every
+        row of `points` to `p0` (the arithmetic the sampling kernel restates:
+        (dx*dx + dy*dy) + dz*dz in the promoted dtype)."""
+        diff = np.asarray(p0) - np.asarray(points)
+        return (diff * diff).sum(axis=1)
+
+    def farthest_first(self, pts, K, start=None, return_indices=False):
+        """kitti_dataset.py:633-641 on the device (sampling.py): K rows of
+        `pts` [n,3], each the farthest from those picked before it -> float64
+        [K,3] like the reference.  `start` (extension): the index of the first
+        pick; None draws exactly one np.random.randint(len(pts)), the
+        reference's draw, so the result after np.random.seed(s) is the
+        reference's.  `return_indices` (extension): -> (rows, idx int32 [K]).
+        float32 clouds stay float32 on the device (the kernel widens them as
+        NumPy's promotion does), every other dtype goes through float64."""
+        from . import sampling
+        K = sampling.check_count(K, "K")
+        pts = np.asarray(pts)
+        if pts.dtype != np.float32:
+            pts = pts.astype(np.float64)
+        if start is None:
+            start = np.random.randint(len(pts))
+        idx, xyz, _ = sampling.farthest_first_device(pts, K, start=start)
+        rows = xyz.astype(np.float64)
+        return (rows, idx) if return_indices else rows
+
     def get_cam_points_in_image(self, frame_idx, downsample_voxel_size=None,
                                 calib=None, xyz_range=None):
         if calib is None:
