@@ -723,6 +723,50 @@ int pgnn_edge_mlp_scatter_max_f16x2_fwd(
     float *out, int64_t ld_out, int32_t *status, const pgnn_dyn_count *n_edges,
     const pgnn_dyn_count *num_vertices, void *stream);
 
+/* The fp32 stage on SCALED operands (csrc/edge_ws.h, pk_sub_clamp): P, Q hold
+ * 2^-scale_exp x the operands of pgnn_edge_mlp_scatter_max_fwd(_dyn) -- write
+ * them with the per-vertex entries from weight images scaled by the same power
+ * of two, which is exact.  The gather's packed subtraction then carries the
+ * `clamp` modifier (to [0, 1]) and IS the ReLU: a third of the gather's VALU
+ * instructions.  A power-of-two scale commutes with every rounding of the
+ * chain, with ReLU and with max, and the kernel multiplies each closed
+ * segment's maximum by 2^scale_exp before the bias add: `out` is, bit for
+ * bit, what the plain entry writes for 2^scale_exp x P, 2^scale_exp x Q --
+ * unless an intermediate of the plain chain is non-zero and below about
+ * 2^(scale_exp - 102) in magnitude (the scaled value would be subnormal).
+ * Guard: bit 0 of *status (device int32, nullable; the caller zeroes it) is
+ * raised when an element of the first num_vertices rows of P or Q exceeds 0.5
+ * in magnitude or is not a number (checked in the kernel's prologue; all
+ * within 0.5 => no difference exceeds 1 and the clamp's upper bound never
+ * acts).  The kernel still runs to the end then; `out` is finite but
+ * unspecified: rerun the stage through the plain entry on unscaled operands.
+ * scale_exp: 0..24.  n_edges / num_vertices: both NULL (the capacities are
+ * the counts) or both given (capacity form).  layers / sched_ws / edges_sorted
+ * as for the plain entry.  Returns PGNN_E_UNSUPPORTED, having done nothing,
+ * where the weights-stationary kernel does not serve the launch -- exactly
+ * where pgnn_edge_ws_applies says 0 for the expected edge count
+ * (n_edges->hint, else edges_cap).
+ *
+ * pgnn_edge_ws_applies: *applies = 1 when a launch of the fp32 edge stage with
+ * these layers, about `edges_expected` edges, on `stream` (its CU mask counts)
+ * takes the weights-stationary kernel -- one 300x300 or 256x256 layer, ~65k
+ * edges and more, a CU count the partition serves --, else 0.  Host only.    */
+int pgnn_edge_ws_applies(const pgnn_fc_layer *layers_host, int32_t n_layers,
+                         int32_t width, int64_t edges_expected, void *stream,
+                         int32_t *applies);
+int pgnn_edge_mlp_scatter_max_scaled_fwd(
+    const float *P, const float *Q, int64_t ld_pq, int32_t width,
+    const int32_t *edges, int64_t edges_cap, int32_t vertices_cap,
+    const pgnn_fc_layer *layers_host, int32_t n_layers, int32_t edges_sorted,
+    float *out, int64_t ld_out, int32_t *sched_ws, int32_t scale_exp,
+    int32_t *status, const pgnn_dyn_count *n_edges,
+    const pgnn_dyn_count *num_vertices, void *stream);
+/* Diagnostic: out[2i], out[2i+1] = the clamped packed subtraction above applied
+ * to (a[2i], a[2i+1]) - (b[2i], b[2i+1]) for i < n_pairs <= 64, one wave
+ * (device pointers): what the hardware makes of the modifier.               */
+int pgnn_debug_pk_sub_clamp(const float *a, const float *b, float *out,
+                            int32_t n_pairs, void *stream);
+
 /* PointSetPooling (gnn.py:256-277) in the same SECONDARY arithmetic, for the
  * car point MLP 4 -> 32 -> 64 -> 128 -> 300 (csrc/pool_ws_f16.h): the three
  * narrow layers stay fp32 MFMA, the last layer's [E, 128] x [128, 300] product

@@ -106,6 +106,12 @@ struct EdgeWsArgs {
   // edge_ws_split.h, F16x2 only: the vertex count of a capacity-form call (nullable;
   // min(*nv_dev, num_segments) rows of P / Q exist) for the range guard
   const int32_t *nv_dev;
+  // SCALED kernels only (see pk_sub_clamp): P, Q hold 2^-k x the plain
+  // operands; `unscale` = 2^k; bit 0 of *status (nullable) is raised when an
+  // element of the first min(*nv_dev, num_segments) rows of P or Q is above
+  // 0.5 in magnitude or not a number
+  float unscale;
+  int32_t *status;
 };
 
 // max(a, b) as ONE instruction: fmaxf() first canonicalises operands the
@@ -130,6 +136,26 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2f pk_sub(v2f a, v2f b) {
   v2f d;
   asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]"
+      : "=v"(d)
+      : "v"(a), "v"(b));
+  return d;
+}
+
+// ReLU(a - b) on two floats with the SAME instruction, for operands scaled
+// into [-0.5, 0.5]: the `clamp` modifier clamps the result to [0, 1], and
+// |a|, |b| <= 0.5 => fl(a - b) <= 1, so the upper bound never acts and the
+// clamp is the ReLU (gfx950 has no packed fp32 max: the plain gather spends
+// four v_med3_f32 per float4 on it, 76 of its 114 VALU instructions at
+// KQ = 19).  The SCALED kernels run on P' = 2^-k P, Q' = 2^-k Q: scaling by a
+// power of two is exact and commutes with the subtraction's rounding, with
+// ReLU, with every rounding of the MFMA chain and with max, so the
+// accumulators hold 2^-k x the plain kernel's -- bit for bit, as long as no
+// intermediate of the plain chain is non-zero and below ~2^(k - 102) in
+// magnitude, where the scaled value would be a subnormal with fewer bits --
+// and ws_flush multiplies the closed segment's maximum by 2^k (exact).
+__device__ __forceinline__ v2f pk_sub_clamp(v2f a, v2f b) {
+  v2f d;
+  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1] clamp"
       : "=v"(d)
       : "v"(a), "v"(b));
   return d;
@@ -165,7 +191,9 @@ __device__ __forceinline__ float ws_v(const v4f (&v)[NTG], int i) {
 // out[d][16 (t0 + t) + 4 g + r] <- act(max over rows + bias): plainly when the
 // run is a whole segment, with float atomic-max otherwise.
 // `bias_lds`: the group's 16 * NTG bias values.
-template <int NTG, class ARGS>
+// SCALED: the maxima are 2^-k x the plain kernel's; a.unscale = 2^k undoes it
+// (exact) in front of the bias add.
+template <int NTG, class ARGS, bool SCALED = false>
 __device__ __forceinline__ void ws_flush(const ARGS &a, const float *bias_lds,
                                          int t0, int lane, int d,
                                          const v4f (&v)[NTG], bool whole,
@@ -206,7 +234,9 @@ __device__ __forceinline__ void ws_flush(const ARGS &a, const float *bias_lds,
     if (i < 4 * NTG) {
       const int c = 16 * (i >> 2) + 4 * g + (i & 3);  // column inside the group
       // max_r act(a_r + b) == act(max_r a_r + b): +b and ReLU are monotone
-      float x = D[m] + bias_lds[c];
+      float dm = D[m];
+      if constexpr (SCALED) dm *= a.unscale;
+      float x = dm + bias_lds[c];
       if (16 * t0 + c >= a.relu_from) x = x > 0.0f ? x : 0.0f;
       if (whole)
         orow[c] = x;
@@ -229,7 +259,7 @@ struct WsRun {
 // row n); starts: bit r set where row r does not continue the run of the edge
 // before it; my_d: lane (., n) holds dst of row n.  fin: the virtual tile
 // behind the range (starts = 1): close the open run against d_after.
-template <int NTG, class ARGS>
+template <int NTG, class ARGS, bool SCALED = false>
 __device__ __forceinline__ void ws_epilogue(const ARGS &a, const float *bias_lds,
                                             int t0, int lane,
                                             const v4f (&acc)[NTG],
@@ -265,7 +295,7 @@ __device__ __forceinline__ void ws_epilogue(const ARGS &a, const float *bias_lds
     // the open run ends in front of row `pos`: the next edge has another dst
     // (virtual tile: the next edge is the one behind the range)
     if (cur_has)
-      ws_flush<NTG>(a, bias_lds, t0, lane, cur_d, carry,
+      ws_flush<NTG, ARGS, SCALED>(a, bias_lds, t0, lane, cur_d, carry,
                     a.sorted && cur_left_closed &&
                         (!fin || d_after != cur_d),
                     inf);
@@ -305,7 +335,12 @@ namespace pgnn {
 //
 // POL: what is kept of a segment's rows -- WsMax: their maximum (ws_epilogue);
 // WsSum: their sum (ws_sum.h), the open run's identity 0 instead of lowest().
-template <int KQ, int NTG, bool EMIT, bool ROWS = false, class POL = WsMax>
+//
+// SCALED (WsMax, no EMIT, no ROWS): P, Q hold 2^-k x the operands, the gather's
+// subtraction is its ReLU (pk_sub_clamp) and ws_flush undoes the scale; the
+// MFMA loop, the fragment schedule and the epilogue are the plain body's.
+template <int KQ, int NTG, bool EMIT, bool ROWS = false, class POL = WsMax,
+          bool SCALED = false>
 __device__ __forceinline__ void edge_ws_body(const EdgeWsArgs &a,
                                              const v4f *__restrict__ wl, int t0,
                                              const float *bias_lds,
@@ -313,6 +348,8 @@ __device__ __forceinline__ void edge_ws_body(const EdgeWsArgs &a,
                                              int64_t tile_last, int lane,
                                              long long *tsw, int &stamped,
                                              const int64_t E) {
+  static_assert(!SCALED || (!EMIT && !ROWS && !POL::kSum),
+                "the scaled form exists for the plain max kernel only");
   if (tile_first >= tile_last) return;
   const int n = lane & 15;
   const int64_t e_first = tile_first * 16;
@@ -430,6 +467,14 @@ __device__ __forceinline__ void edge_ws_body(const EdgeWsArgs &a,
       // what this kernel is short of next to the partner wave's MFMA stream)
 #pragma unroll
       for (int q = 0; q < KQ; ++q) {
+        if constexpr (SCALED) {
+          const v2f lo = pk_sub_clamp((v2f){in[q][0], in[q][1]},
+                                      (v2f){pq[q][0], pq[q][1]});
+          const v2f hi = pk_sub_clamp((v2f){in[q][2], in[q][3]},
+                                      (v2f){pq[q][2], pq[q][3]});
+          in[q] = (v4f){lo[0], lo[1], hi[0], hi[1]};
+          continue;
+        }
         const v2f lo = pk_sub((v2f){in[q][0], in[q][1]}, (v2f){pq[q][0], pq[q][1]});
         const v2f hi = pk_sub((v2f){in[q][2], in[q][3]}, (v2f){pq[q][2], pq[q][3]});
         in[q][0] = max_nc(lo[0], 0.0f, inf);
@@ -543,6 +588,9 @@ __device__ __forceinline__ void edge_ws_body(const EdgeWsArgs &a,
     if constexpr (POL::kSum)
       ws_epilogue_sum<NTG>(a, bias_lds, t0, lane, acc, carry, starts, my_d, st,
                            fin, d_after, inf);
+    else if constexpr (SCALED)
+      ws_epilogue<NTG, EdgeWsArgs, true>(a, bias_lds, t0, lane, acc, carry,
+                                         starts, my_d, st, fin, d_after, inf);
     else
       ws_epilogue<NTG>(a, bias_lds, t0, lane, acc, carry, starts, my_d, st, fin,
                        d_after, inf);
@@ -702,8 +750,42 @@ __device__ __forceinline__ void ws_pool_rearm(int32_t *sched, int n_counters,
   }
 }
 
+// The SCALED form's guard, before the weights go to LDS (its loads overlap
+// theirs; edge_ws_split_kernel's pass for f16x2 with another bound): workgroup
+// b scans rows b, b + gridDim.x, ... of the first min(*nv_dev, num_segments)
+// rows of P and Q.  No |P|, |Q| above 0.5 => every fl(P[s] - Q[d]) <= 1, the
+// clamp's upper bound never acts.
+__device__ __forceinline__ void ws_scaled_guard(const EdgeWsArgs &a) {
+  if (!a.status) return;
+  int nv = a.num_segments;
+  if (a.nv_dev) {
+    const int d = *a.nv_dev;
+    nv = d < nv ? d : nv;
+  }
+  const v4f *__restrict__ P4 = reinterpret_cast<const v4f *>(a.P);
+  const v4f *__restrict__ Q4 = reinterpret_cast<const v4f *>(a.Q);
+  float m = 0.0f;
+  bool bad = false;
+  const int mine = nv > (int)blockIdx.x
+                       ? (nv - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x
+                       : 0;   // rows blockIdx.x + j * gridDim.x, j < mine
+  for (int it = threadIdx.x; it < mine * a.ldv4; it += 64 * kWsWaves) {
+    const int j = it / a.ldv4, c = it - j * a.ldv4;
+    const size_t at = ((size_t)blockIdx.x + (size_t)j * gridDim.x) * a.ldv4 + c;
+    const v4f p = P4[at], q = Q4[at];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      m = fmaxf(m, fmaxf(fabsf(p[i]), fabsf(q[i])));
+      bad |= !(p[i] == p[i]) || !(q[i] == q[i]);   // NaN: fmaxf drops it
+    }
+  }
+  if (bad || !(m <= 0.5f)) atomicOr(a.status, 1);
+}
+
+// SCALED is the LAST parameter: the kernel's name still begins
+// `edge_ws_kernel<KQ, NTMAX, ...`, which is what the profile tools look for.
 template <int KQ, int NTMAX, bool EMIT = false, bool ROWS = false,
-          class POL = WsMax>
+          class POL = WsMax, bool SCALED = false>
 __global__ __launch_bounds__(64 * kWsWaves) void edge_ws_kernel(EdgeWsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   v4f *wl = reinterpret_cast<v4f *>(smem);
@@ -712,6 +794,7 @@ __global__ __launch_bounds__(64 * kWsWaves) void edge_ws_kernel(EdgeWsArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int slice = blockIdx.x % a.xcds;
   const int local = blockIdx.x / a.xcds;
+  if constexpr (SCALED) ws_scaled_guard(a);
   // profiling builds only: when this wave entered the kernel (constant
   // 100 MHz clock), i.e. before the weights go to LDS
   const long long rt_entry = a.ts ? (long long)__builtin_amdgcn_s_memrealtime() : 0;
@@ -775,13 +858,13 @@ __global__ __launch_bounds__(64 * kWsWaves) void edge_ws_kernel(EdgeWsArgs a) {
   int32_t *counter = a.sched ? a.sched + 2 + slice * kWsMaxGroups + grp : nullptr;
   for (;;) {
     if (ntg == NTMAX)
-      edge_ws_body<KQ, NTMAX, EMIT, ROWS, POL>(a, wl, t0, bias_lds, tile_first,
-                                          tile_last, lane, tsw, stamped,
-                                          n_edges);
+      edge_ws_body<KQ, NTMAX, EMIT, ROWS, POL, SCALED>(
+          a, wl, t0, bias_lds, tile_first, tile_last, lane, tsw, stamped,
+          n_edges);
     else
-      edge_ws_body<KQ, NTMAX - 1, EMIT, ROWS, POL>(a, wl, t0, bias_lds, tile_first,
-                                              tile_last, lane, tsw, stamped,
-                                              n_edges);
+      edge_ws_body<KQ, NTMAX - 1, EMIT, ROWS, POL, SCALED>(
+          a, wl, t0, bias_lds, tile_first, tile_last, lane, tsw, stamped,
+          n_edges);
     if (pool == 0) break;
     const int c = ws_pool_claim(counter, a.chunk, lane);
     if (c >= pool) break;

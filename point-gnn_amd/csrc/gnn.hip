@@ -1373,7 +1373,96 @@ int edge_fwd_impl(const float *P, const float *Q, int64_t ld_pq, int32_t width,
   return launch_fused<2, PRO_EDGE>(p, n_edges, ra, pa, ea, sa, stream, sched_ws,
                                    de.dev);
 }
+
+// v_pk_add_f32 ... clamp on n_pairs <= 64 pairs (pgnn_debug_pk_sub_clamp)
+__global__ void pk_sub_clamp_probe_kernel(const float *a, const float *b,
+                                          float *out, int n_pairs) {
+  const int i = threadIdx.x;
+  if (i >= n_pairs) return;
+  const v2f d = pk_sub_clamp((v2f){a[2 * i], a[2 * i + 1]},
+                             (v2f){b[2 * i], b[2 * i + 1]});
+  out[2 * i] = d[0];
+  out[2 * i + 1] = d[1];
+}
 }  // namespace
+
+extern "C" int pgnn_debug_pk_sub_clamp(const float *a, const float *b,
+                                       float *out, int32_t n_pairs,
+                                       void *stream_) {
+  PGNN_GUARD_BEGIN
+  PGNN_REQUIRE(a && b && out && n_pairs >= 0 && n_pairs <= 64, PGNN_E_INVALID,
+               "debug_pk_sub_clamp: 0..64 pairs, no null pointer");
+  if (n_pairs == 0) return 0;
+  hipLaunchKernelGGL(pk_sub_clamp_probe_kernel, dim3(1), dim3(64), 0,
+                     (hipStream_t)stream_, a, b, out, n_pairs);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_edge_ws_applies(const pgnn_fc_layer *layers, int32_t n_layers,
+                                    int32_t width, int64_t edges_expected,
+                                    void *stream_, int32_t *applies) {
+  PGNN_GUARD_BEGIN
+  PGNN_REQUIRE(applies && width > 0 && edges_expected >= 0, PGNN_E_INVALID,
+               "edge_ws_applies: bad argument");
+  *applies = 0;
+  Plan p;
+  const int rc = make_plan(layers, n_layers, width, p);
+  if (rc) return rc;
+  *applies = edge_ws_applies(p, edges_expected, ws_cus((hipStream_t)stream_));
+  return 0;
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_edge_mlp_scatter_max_scaled_fwd(
+    const float *P, const float *Q, int64_t ld_pq, int32_t width,
+    const int32_t *edges, int64_t edges_cap, int32_t vertices_cap,
+    const pgnn_fc_layer *layers, int32_t n_layers, int32_t edges_sorted,
+    float *out, int64_t ld_out, int32_t *sched_ws, int32_t scale_exp,
+    int32_t *status, const pgnn_dyn_count *n_edges,
+    const pgnn_dyn_count *num_vertices, void *stream_) {
+  PGNN_GUARD_BEGIN
+  hipStream_t stream = (hipStream_t)stream_;
+  PGNN_REQUIRE(edges_cap >= 0 && vertices_cap >= 0 && width > 0,
+               PGNN_E_INVALID, "edge_mlp_scaled: bad sizes");
+  PGNN_REQUIRE(scale_exp >= 0 && scale_exp <= 24, PGNN_E_INVALID,
+               "edge_mlp_scaled: scale_exp outside 0..24");
+  PGNN_REQUIRE((n_edges == nullptr) == (num_vertices == nullptr) &&
+                   (!n_edges || (n_edges->dev && num_vertices->dev)),
+               PGNN_E_INVALID, "edge_mlp_scaled: counts come as a pair");
+  const Dyn de = dyn_of(n_edges), dk = dyn_of(num_vertices);
+  Plan p;
+  int rc = make_plan(layers, n_layers, width, p);
+  if (rc) return rc;
+  PGNN_REQUIRE(ld_pq == 16 * p.chain.l[0].kq, PGNN_E_INVALID,
+               "edge_mlp_scaled: ld_pq must equal the padded width 16*ceil(width/16)");
+  PGNN_REQUIRE(ld_out >= 16 * p.chain.l[n_layers - 1].nt, PGNN_E_INVALID,
+               "edge_mlp_scaled: ld_out < padded output width");
+  const int cus = ws_cus(stream);
+  // the weights-stationary partition's own answer (pgnn_edge_ws_applies)
+  if (edges_cap == 0 || vertices_cap == 0 ||
+      !edge_ws_applies(p, expected(de, edges_cap), cus))
+    return PGNN_E_UNSUPPORTED;  // (no message: an expected answer)
+  PGNN_REQUIRE(out && P && Q && edges, PGNN_E_INVALID,
+               "edge_mlp_scaled: null pointer");
+  PGNN_REQUIRE(((uintptr_t)P % 16 == 0) && ((uintptr_t)Q % 16 == 0),
+               PGNN_E_INVALID, "edge_mlp_scaled: P/Q must be 16-byte aligned");
+  if (!(edges_sorted & 2)) {  // bit 1: caller already filled `out` with lowest()
+    rc = fill_lowest_rows(out, ld_out, vertices_cap, dk, stream);
+    if (rc) return rc;
+  }
+  const EdgeArgs ea = {P, Q, ld_pq, edges};
+  const SegArgs sa = {out, ld_out, vertices_cap, edges_sorted & 1};
+  if (p.chain.l[0].nt == 19)
+    return launch_edge_ws_scaled<19, 7>(p.chain.l[0], ea, edges_cap, sa, cus,
+                                        sched_ws, stream, de.dev, dk.dev,
+                                        scale_exp, status);
+  return launch_edge_ws_scaled<16, 8>(p.chain.l[0], ea, edges_cap, sa, cus,
+                                      sched_ws, stream, de.dev, dk.dev,
+                                      scale_exp, status);
+  PGNN_GUARD_END
+}
 
 extern "C" int pgnn_edge_mlp_scatter_max_bf16x3_fwd(
     const float *P, const float *Q, int64_t ld_pq, int32_t width,

@@ -86,13 +86,14 @@ int plan_edge_ws(EdgeWsArgs &a, const LayerDev &L, const EdgeArgs &ea,
   return 0;
 }
 
-template <int KQ, int NTMAX, bool ROWS, class POL = WsMax>
+template <int KQ, int NTMAX, bool ROWS, class POL = WsMax, bool SCALED = false>
 int run_edge_ws(const EdgeWsArgs &a, int cus, hipStream_t stream) {
   static_assert(!POL::kSum || !ROWS, "the sum kernels read no ready rows");
+  static_assert(!SCALED || (!POL::kSum && !ROWS), "scaled: the plain max kernel only");
   PGNN_HIP((hipError_t)arm_sched(a.sched, stream));
   const size_t lds = (size_t)KQ * NTMAX * 1024 + 16 * NTMAX * sizeof(float);
-  auto kern = edge_ws_kernel<KQ, NTMAX, false, ROWS, POL>;
-  if constexpr (!ROWS && !POL::kSum) {  // training forward: the rows are written as well
+  auto kern = edge_ws_kernel<KQ, NTMAX, false, ROWS, POL, SCALED>;
+  if constexpr (!ROWS && !POL::kSum && !SCALED) {  // training forward: the rows are written as well
     if (a.rows_out) kern = edge_ws_kernel<KQ, NTMAX, true>;
   }
   return launch_lds(kern, dim3((unsigned)(cus / a.xcds * a.xcds)),
@@ -109,6 +110,24 @@ int launch_edge_ws(const LayerDev &L, const EdgeArgs &ea, int64_t n_edges,
   const int rc = plan_edge_ws<KQ, NTMAX>(a, L, ea, n_edges, sa, cus, sched,
                                          rows_out, ld_rows, h1_out, n_dev);
   return rc ? rc : run_edge_ws<KQ, NTMAX, false, POL>(a, cus, stream);
+}
+
+// The SCALED form of the same launch (edge_ws.h, pk_sub_clamp): ea.P, ea.Q hold
+// 2^-scale_exp x the operands; status / nv_dev: the guard's flag and the
+// capacity form's vertex count (both nullable).
+template <int KQ, int NTMAX>
+int launch_edge_ws_scaled(const LayerDev &L, const EdgeArgs &ea, int64_t n_edges,
+                          const SegArgs &sa, int cus, int32_t *sched,
+                          hipStream_t stream, const int32_t *n_dev,
+                          const int32_t *nv_dev, int scale_exp, int32_t *status) {
+  EdgeWsArgs a;
+  const int rc = plan_edge_ws<KQ, NTMAX>(a, L, ea, n_edges, sa, cus, sched,
+                                         nullptr, 0, nullptr, n_dev);
+  if (rc) return rc;
+  a.nv_dev = nv_dev;
+  a.unscale = (float)((int64_t)1 << scale_exp);
+  a.status = status;
+  return run_edge_ws<KQ, NTMAX, false, WsMax, true>(a, cus, stream);
 }
 
 // the shapes edge_ws.h is instantiated for: one square layer of 19 (C = 300)

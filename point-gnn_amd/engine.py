@@ -114,6 +114,13 @@ class DeferredFrame(object):
         self.counts = counts
         self.pair = pair
         self._out = None
+        # the scaled edge stage's guard: the flag row of the pass that computed
+        # this frame (InferenceEngine._begin_pass); in_batch: the batch entry
+        # point reads the rows of all its frames together; rebuilt: the pass's
+        # outputs were not used (its flags mean nothing)
+        self.scale_row = engine._pass_row
+        self.in_batch = False
+        self.rebuilt = False
 
     def result(self, host_counts=None):
         if self._out is not None:
@@ -130,10 +137,14 @@ class DeferredFrame(object):
             # hints now hold 2 x this frame's sizes): rebuild the frame
             # with host-read sizes
             eng.deferred_overflows += 1
+            self.rebuilt = True
+            eng.model.edge_scale_discard(self.scale_row)
             self._out = eng.run_frame(self.xyz, self.intensity)
         elif self.pair is not None and any(p.overflowed for p in self.pair):
             # the other half of the pass lost rows, so the pass's edge lists
             # are not this frame's either
+            self.rebuilt = True
+            eng.model.edge_scale_discard(self.scale_row)
             self._out = eng.run_frame(self.xyz, self.intensity)
         else:
             eng.frame_shapes.append((k,) + tuple(edges))
@@ -141,6 +152,11 @@ class DeferredFrame(object):
             if self.pair is not None and self.pair[0] is not c:
                 r0 = self.pair[0].k
             self._out = (self.logits[r0:r0 + k], self.boxes[r0:r0 + k])
+            if not self.in_batch and \
+                    not eng.model.edge_scale_ok([self.scale_row]):
+                del eng.frame_shapes[-1]
+                self._out = eng._rerun_plain(
+                    lambda: eng.run_frame(self.xyz, self.intensity))
         return self._out
 
 
@@ -176,6 +192,7 @@ class CapturedFrame(object):
         out = DeferredFrame(self.engine, xyz, intensity, f.logits, f.boxes,
                             graph_gen.FrameCounts(f.counts.tensor,
                                                   f.counts.edge_caps))
+        out.scale_row = f.scale_row     # (the captured kernels' flag row)
         return out
 
 
@@ -203,6 +220,28 @@ class InferenceEngine(object):
         # are expected to be, learnt from the frames finished so far
         self._hints = None
         self.deferred_overflows = 0
+        # the scaled edge stage (gnn.EDGE_SCALE_HEADROOM): the guard's flags
+        # are kept per forward pass
+        self._pass_row = 0
+        self.edge_scale_reruns = 0
+
+    def _begin_pass(self):
+        """Before every model.predict whose results are looked at on their
+        own: a row of guard flags for it (DeferredFrame.scale_row)."""
+        self._pass_row = self.model.edge_scale_begin_pass()
+        return self._pass_row
+
+    def _rerun_plain(self, run):
+        """`run()` with the scaled edge stage off; `edge_scale_reruns` counts
+        how often (the tripped layers' exponents were raised when the guard
+        was read)."""
+        self.edge_scale_reruns += 1
+        was = self.model.edge_scaled
+        self.model.edge_scaled = False
+        try:
+            return run()
+        finally:
+            self.model.edge_scaled = was
 
     def _note_shape(self, graph):
         coords, _, edges = graph
@@ -238,6 +277,7 @@ class InferenceEngine(object):
             return f
         graph = self.build_graph_deferred(xyz, overlap_build)
         coords, kps, edges = graph
+        self._begin_pass()
         logits, boxes = self.model.predict(intensity, coords, kps, edges,
                                            is_training=False)
         self.last_graph = graph
@@ -288,6 +328,7 @@ class InferenceEngine(object):
         ga = self.build_graph_deferred(xa)
         gb = self.build_graph_deferred(xb)
         feats, coords, kps, edges = graph_gen.merge_frames_dyn(ga, ia, gb, ib)
+        self._begin_pass()
         logits, boxes = self.model.predict(feats, coords, kps, edges,
                                            is_training=False)
         self.last_graph = gb
@@ -473,6 +514,7 @@ class InferenceEngine(object):
                         t.record_stream(h)     # allocated on b, read on h
                     frame = edges[0]._pgnn_count.frame
                     frame.tensor.record_stream(h)
+                    self._begin_pass()
                     logits, boxes = self.model.predict(
                         intensity, coords, kps, edges, is_training=False)
                     # the next build on b may not overtake this frame's GNN by
@@ -515,12 +557,21 @@ class InferenceEngine(object):
             # (every record before the first result: a half of a pair looks
             # at the other half's record too)
             f.counts._host = [int(v) for v in h]
+        for f in pending:
+            f.in_batch = True
         outs = [f.result() for f in pending]
         for lg, bx in outs:     # allocated on a side stream, used by the caller
             lg.record_stream(cur)
             bx.record_stream(cur)
         if not self._edge_range_clean():
             return self._rerun_batch_f32(
+                lambda: self.run_frames_on_streams(frames, n_streams,
+                                                   gnn_priority,
+                                                   frames_per_pass))
+        rows = sorted({f.scale_row for f in pending
+                       if not f.rebuilt and f.counts is not None})
+        if rows and not self.model.edge_scale_ok(rows):
+            return self._rerun_batch_plain(
                 lambda: self.run_frames_on_streams(frames, n_streams,
                                                    gnn_priority,
                                                    frames_per_pass))
@@ -572,6 +623,7 @@ class InferenceEngine(object):
             self.run_frame(*frames[0])
             self.frame_shapes.pop()
             self._warm = True
+        rows = []
         sg, scs = self._pipeline_streams(graph_cus)
         scs = scs[:max(1, min(4, int(compute_streams)))]
         sgs = [sg]
@@ -642,6 +694,7 @@ class InferenceEngine(object):
                     if deferred:
                         counts = edges[0]._pgnn_count.frame
                         counts.tensor.record_stream(sc)
+                    rows.append(self._begin_pass())
                     out = self.model.predict(frames[i][1], coords, kps,
                                              edges, is_training=False)
                     outs.append(DeferredFrame(self, frames[i][0], frames[i][1],
@@ -667,12 +720,19 @@ class InferenceEngine(object):
         if deferred:
             # the one host read, for all frames together (waits for them)
             host = torch.stack([f.counts.tensor for f in outs]).tolist()
+            for f in outs:
+                f.in_batch = True
             outs = [f.result(h) for f, h in zip(outs, host)]
             for lg, bx in outs:
                 lg.record_stream(cur)
                 bx.record_stream(cur)
         if not self._edge_range_clean():
             return self._rerun_batch_f32(
+                lambda: self.run_frames_pipelined(
+                    frames, compute_streams, graph_cus, lookahead, deferred,
+                    graph_streams))
+        if rows and not self.model.edge_scale_ok(sorted(set(rows))):
+            return self._rerun_batch_plain(
                 lambda: self.run_frames_pipelined(
                     frames, compute_streams, graph_cus, lookahead, deferred,
                     graph_streams))
@@ -698,6 +758,15 @@ class InferenceEngine(object):
             return outs
         finally:
             self.model.edge_arith = 'f16x2'
+
+    def _rerun_batch_plain(self, run):
+        """The scaled edge stage's guard tripped somewhere in a batch: the
+        batch again with the plain edge kernel (_rerun_plain)."""
+        shapes = len(self.frame_shapes)
+        outs = self._rerun_plain(run)
+        # (the first pass noted the batch's shapes already)
+        del self.frame_shapes[shapes:]
+        return outs
 
     def check_edge_range(self):
         """edge_arith 'f16x2' only: raises when an activation of a frame run
@@ -726,8 +795,12 @@ class InferenceEngine(object):
             torch.cuda.synchronize()
             t1 = time.perf_counter()
         coords, kps, edges = graph
+        row = self._begin_pass()
         out = self.model.predict(intensity, coords, kps, edges,
                                  is_training=False)
+        if not self.model.edge_scale_ok([row]):
+            out = self._rerun_plain(lambda: self.model.predict(
+                intensity, coords, kps, edges, is_training=False))
         if timed:
             torch.cuda.synchronize()
             t2 = time.perf_counter()

@@ -55,6 +55,10 @@ class ParamStore(object):
         self.device = device
         self._cache = {}
         self._edge_arith = 'f32'
+        # EDGE_SCALED below: a model turns it on for its store (models.py);
+        # `inference` is what predict() was last called for
+        self.edge_scaled = False
+        self.inference = True
 
     @property
     def edge_arith(self):
@@ -86,6 +90,107 @@ class ParamStore(object):
         if not ok:
             st.zero_()
         return ok
+
+    # ---- scaled operands of the fp32 edge stage (EDGE_SCALED below) ----------
+    def edge_scale_exp(self, scope):
+        """The exponent k layer `scope` runs with, or None while it is not
+        calibrated.  A calibration frame's maxima are read here, at the first
+        call that needs them: one small device-to-host read per model (never
+        while a stream is being captured: the layer stays on the plain path
+        then)."""
+        scales = self.__dict__.setdefault('_edge_scale', {})
+        pend = self.__dict__.setdefault('_edge_scale_pending', {})
+        if scope not in scales and scope in pend and \
+                not torch.cuda.is_current_stream_capturing():
+            names = list(pend)
+            got = [pend.pop(n) for n in names]
+            for _, done in got:      # (written on another stream, perhaps)
+                done.synchronize()
+            for name, m in zip(names,
+                               torch.stack([t for t, _ in got]).tolist()):
+                scales[name] = edge_scale_exp_for(m)
+        return scales.get(scope)
+
+    def note_edge_range(self, scope, p, q):
+        """Calibration: max(|P|, |Q|) of a host-sized frame that ran the plain
+        kernel, kept on the device until edge_scale_exp() needs it."""
+        if torch.cuda.is_current_stream_capturing():
+            return
+        pend = self.__dict__.setdefault('_edge_scale_pending', {})
+        m = torch.maximum(p.abs().max(), q.abs().max())
+        done = torch.cuda.Event()
+        done.record()
+        pend[scope] = (m, done)
+
+    # The guard's flags are a PASS's, not the model's: [EDGE_SCALE_ROWS rows,
+    # EDGE_SCALE_SLOTS layers] int32.  Whoever runs a forward pass whose results
+    # it will look at on its own takes a row first (edge_scale_begin_pass) and
+    # asks about that row afterwards, so a pass whose outputs are thrown away
+    # -- a frame that overflowed a capacity -- taints nobody else.  Rows are
+    # handed out round robin; more than EDGE_SCALE_ROWS passes in flight share
+    # rows (a trip then reruns all that share it).
+    def edge_scale_begin_pass(self):
+        """The flag row of the forward pass about to be enqueued."""
+        self._edge_scale_row = (self.__dict__.get('_edge_scale_row', 0) + 1) \
+            % EDGE_SCALE_ROWS
+        return self._edge_scale_row
+
+    def edge_scale_status(self, scope):
+        """Pointer to the device int32 the scaled kernel of layer `scope`
+        raises, in the current pass's row, when an operand left [-0.5, 0.5]."""
+        slots = self.__dict__.setdefault('_edge_scale_slots', {})
+        if getattr(self, '_edge_scale_flags', None) is None:
+            self._edge_scale_flags = torch.zeros(
+                (EDGE_SCALE_ROWS, EDGE_SCALE_SLOTS), dtype=torch.int32,
+                device=self._dev())
+        if scope not in slots:
+            if len(slots) >= EDGE_SCALE_SLOTS:
+                raise NotImplementedError("more than %d scaled edge layers"
+                                          % EDGE_SCALE_SLOTS)
+            slots[scope] = len(slots)
+        row = self.__dict__.get('_edge_scale_row', 0)
+        return self._edge_scale_flags.data_ptr() + \
+            4 * (row * EDGE_SCALE_SLOTS + slots[scope])
+
+    def edge_scale_ok(self, rows=None):
+        """Reads (and clears) the flags of the passes `rows` (None: all): one
+        small device-to-host read, none before the first scaled launch.  True
+        when no operand left [-0.5, 0.5]; else the tripped layers' exponents
+        are raised by 2 and the caller reruns those passes with `edge_scaled`
+        off."""
+        flags = getattr(self, '_edge_scale_flags', None)
+        if flags is None:
+            return True
+        host = flags.tolist()
+        rows = range(EDGE_SCALE_ROWS) if rows is None else rows
+        return self.edge_scale_tripped({r: host[r] for r in rows})
+
+    def edge_scale_flags(self):
+        """The flags' device tensor [rows, layers] (None before the first
+        scaled launch), for a caller that reads a row with other words of its
+        own."""
+        return getattr(self, '_edge_scale_flags', None)
+
+    def edge_scale_tripped(self, host, count=True):
+        """edge_scale_ok() on rows the caller has read (`host`: {row: its
+        values}); count=False only clears them (the pass's results are not
+        used)."""
+        bad = [r for r, v in host.items() if any(v)]
+        if not bad:
+            return True
+        for r in bad:
+            self._edge_scale_flags[r].zero_()
+        if count:
+            for s, i in self._edge_scale_slots.items():
+                if any(host[r][i] for r in bad):
+                    self._edge_scale[s] = min(24, self._edge_scale.get(s, 0) + 2)
+        return False
+
+    def edge_scale_discard(self, row):
+        """Clears a row unread: its pass's results are not used."""
+        flags = getattr(self, '_edge_scale_flags', None)
+        if flags is not None:
+            flags[row].zero_()
 
     def _dev(self):
         if self.device is None:
@@ -752,6 +857,34 @@ EDGE_INPUT_TAP = None
 # 'bf16x3' and 'f16x2' too.
 EDGE_ARITHS = ('f32', 'bf16x3', 'f16x2')
 
+# Scaled operands of the 'f32' edge stage (csrc/edge_ws.h, pk_sub_clamp;
+# pgnn_edge_mlp_scatter_max_scaled_fwd), an attribute of the MODEL
+# (`model.edge_scaled`, default on; off for a bare ParamStore): where the
+# weights-stationary kernel serves the launch (pgnn_edge_ws_applies), the
+# per-vertex stage writes P' = 2^-k P, Q' = 2^-k Q -- from a second image of the
+# vertex-side first layer, w1, b1 and wx times 2^-k, which is exact -- and the
+# edge kernel's packed subtraction, clamped to [0, 1], is its own ReLU.  The
+# results are those of the plain kernel bit for bit.  k is the layer's: the
+# first host-sized inference frame runs the plain kernel and leaves
+# max(|P|, |Q|) on the device; k is the smallest exponent that brings it to
+# 0.125 or below (4x headroom under the kernel's guard at 0.5).  A tripped guard
+# (`model.edge_scale_ok()` False, read by the engine with a batch's results)
+# means: rerun those frames with `edge_scaled` off; the layer's k has been
+# raised by 2.  Sum / mean aggregation, the 16-bit arithmetics and training take
+# the plain path.
+EDGE_SCALE_HEADROOM = 0.125
+EDGE_SCALE_ROWS, EDGE_SCALE_SLOTS = 64, 16    # ParamStore.edge_scale_begin_pass
+
+
+def edge_scale_exp_for(max_abs):
+    """Smallest k >= 0 with max_abs * 2^-k <= EDGE_SCALE_HEADROOM (24 at the
+    most: the kernel's range; an infinite or NaN maximum gets 24 and trips the
+    guard)."""
+    k = 0
+    while k < 24 and not max_abs * 2.0 ** -k <= EDGE_SCALE_HEADROOM:
+        k += 1
+    return k
+
 
 class GraphNetAutoCenter(object):
     """gnn.py:285-373."""
@@ -823,6 +956,37 @@ class GraphNetAutoCenter(object):
             raise NotImplementedError("edge MLP needs at least two layers")
         assert h.shape[1] >= c, "vertex features narrower than edge MLP input"
 
+        # scaled operands (EDGE_SCALED above): decided before the per-vertex
+        # stage, which writes them, by the launcher's own partition query
+        scale_k, calibrate = None, False
+        if store.edge_scaled and store.inference and rest.n == 1 and \
+                store.edge_arith == 'f32' and \
+                self._aggregation == _lib.AGG_MAX:
+            n_exp = int(e.shape[0])
+            if cnt_e is not None and 0 < cnt_e.hint < n_exp:
+                n_exp = cnt_e.hint
+            applies = ctypes.c_int32(0)
+            _lib.check(lib.pgnn_edge_ws_applies(
+                rest.array, rest.n, int(rest.k_in), n_exp, st,
+                ctypes.byref(applies)), "pgnn_edge_ws_applies")
+            if applies.value:
+                scale_k = store.edge_scale_exp(edge_scope)
+                calibrate = scale_k is None and cnt_k is None
+        if scale_k is not None:
+            def build_scaled():
+                w1, b1 = store.mlp(edge_scope, len(edge_widths))[0]
+                s = np.float32(2.0 ** -scale_k)
+                wx = np.zeros((3, padded_width(w1.shape[1])), np.float32)
+                wx[:, :w1.shape[1]] = w1[c:c + 3] * s
+                made = (Chain(store, [(w1 * s, b1 * s, w1.shape[1])]),
+                        torch.from_numpy(wx).to(store._dev()))
+                # (other streams will read the images without an event)
+                torch.cuda.current_stream().synchronize()
+                return made
+            p_chain, wx_dev = store.cached(
+                ('edge_scaled', edge_scope, tuple(edge_widths), scale_k),
+                build_scaled)
+
         # per vertex, one launch (gnn.py:341-356): [optional] coordinate offset
         # delta = MLP(h) (auto-registration), Q = (x + delta) @ W1[C:],
         # P = [h, x] @ W1 + b1, and the lowest() fill of the aggregation buffer
@@ -871,6 +1035,8 @@ class GraphNetAutoCenter(object):
         else:
             _lib.check(lib.pgnn_vertex_pre_edge_fwd_dyn(
                 *pre_args, cnt_k.arg(), st), "pgnn_vertex_pre_edge_fwd_dyn")
+        if calibrate:
+            store.note_edge_range(edge_scope, p, q)
         if EDGE_INPUT_TAP is not None:   # measurement hook (bench.py)
             EDGE_INPUT_TAP.append((p, q))
         # per-edge: ReLU(P[src] - Q[dst]) -> remaining edge layers -> max
@@ -891,6 +1057,15 @@ class GraphNetAutoCenter(object):
             done = self._edge_split(lib, store, edge_scope, edge_widths, p, q,
                                     wq, rest, e, k, edges, agg, cnt_e, cnt_k,
                                     st)
+        elif scale_k is not None:
+            # (p, q are scaled: the plain entry would be wrong from here on,
+            # and the query above was this entry's own decision)
+            _lib.check(lib.pgnn_edge_mlp_scatter_max_scaled_fwd(
+                *edge_args, scale_k, store.edge_scale_status(edge_scope),
+                cnt_e.arg() if cnt_e is not None else None,
+                cnt_k.arg() if cnt_k is not None else None, st),
+                "pgnn_edge_mlp_scatter_max_scaled_fwd")
+            done = True
         if done:
             pass
         elif cnt_k is None:

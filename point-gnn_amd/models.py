@@ -165,12 +165,62 @@ class MultiLayerFastLocalGraphModelV2(object):
         One small device-to-host read; always True for the other arithmetics."""
         return self._store is None or self._store.edge_range_ok()
 
+    @property
+    def edge_scaled(self):
+        """Scaled operands of the fp32 edge stage (gnn.EDGE_SCALE_HEADROOM and
+        the comment above it): on by default, same results bit for bit.  Not
+        part of the reference's surface."""
+        return getattr(self, '_edge_scaled', True)
+
+    @edge_scaled.setter
+    def edge_scaled(self, value):
+        self._edge_scaled = bool(value)
+        if self._store is not None:
+            self._store.edge_scaled = self._edge_scaled
+
+    def edge_scale_begin_pass(self):
+        """Takes a row of guard flags for the forward pass about to be
+        enqueued (gnn.ParamStore.edge_scale_begin_pass) and returns it: ask
+        edge_scale_ok([row]) when the pass's results are taken."""
+        return 0 if self._store is None else \
+            self._store.edge_scale_begin_pass()
+
+    def edge_scale_ok(self, rows=None):
+        """False when a scaled edge kernel of the passes `rows` (None: any)
+        found an operand outside [-0.5, 0.5]: their results are unspecified,
+        rerun them with `edge_scaled` off (the tripped layers' exponents have
+        been raised by 2).  One small device-to-host read, none before the
+        first scaled launch."""
+        return self._store is None or self._store.edge_scale_ok(rows)
+
+    def edge_scale_flags(self):
+        """The guard flags as a device tensor [rows, layers] (or None), for a
+        caller that reads a row with a host copy of its own and hands the
+        values to edge_scale_tripped()."""
+        return None if self._store is None else self._store.edge_scale_flags()
+
+    def edge_scale_tripped(self, host, count=True):
+        """edge_scale_ok() on rows the caller has read ({row: values})."""
+        return self._store.edge_scale_tripped(host, count)
+
+    def edge_scale_discard(self, row):
+        """Clears a row unread: its pass's results are not used."""
+        if self._store is not None:
+            self._store.edge_scale_discard(row)
+
+    def edge_scale_exps(self):
+        """{layer scope: k} of the layers calibrated so far."""
+        if self._store is None:
+            return {}
+        return dict(self._store.__dict__.get('_edge_scale', {}))
+
     # ---- weights ----------------------------------------------------------
     def load_state_dict(self, params, device=None):
         """params: {TF variable name: ndarray} (extra keys such as the
         global-step `Variable` are ignored)."""
         self._store = gnn.ParamStore(params, device)
         self._store.edge_arith = self._edge_arith
+        self._store.edge_scaled = self.edge_scaled
         return self
 
     def init_weights(self, config, seed=0, **kw):
@@ -233,6 +283,8 @@ class MultiLayerFastLocalGraphModelV2(object):
         # `model.fuse_vertex_stages = False`: every operator launches its own
         # per-vertex stages (the unfused reference form the tests compare with)
         fuse = getattr(self, 'fuse_vertex_stages', True)
+        # (gnn.EDGE_SCALE_HEADROOM: the scaled edge stage is for inference)
+        self._store.inference = not is_training
         with gnn.parameters(self._store), gnn.fuse_vertex_stages(fuse):
             feats = t_initial_vertex_features
             *body, head = self._layer_configs

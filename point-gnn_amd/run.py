@@ -88,6 +88,7 @@ def detect_frame(dataset, frame_idx, model, config, use_box_merge=True,
     coords, kps, edges = fn(points.xyz, **config['runtime_graph_gen_kwargs'])
     t = lap('gen graph', t)
     input_v = _input_features(config, points)
+    scale_row = model.edge_scale_begin_pass()
     logits, box_encodings = model.predict(input_v, coords, kps, edges, False)
     if model.edge_arith == 'f16x2' and not model.edge_range_ok():
         # an activation left fp16's safe range (gnn.EDGE_ARITHS): this frame
@@ -99,6 +100,17 @@ def detect_frame(dataset, frame_idx, model, config, use_box_merge=True,
                                                   False)
         finally:
             model.edge_arith = 'f16x2'
+    if not model.edge_scale_ok([scale_row]):
+        # the scaled edge stage's guard (gnn.EDGE_SCALE_HEADROOM): this frame
+        # with the plain kernel
+        td['edge scale reruns'] = td.get('edge scale reruns', 0) + 1
+        was = model.edge_scaled
+        model.edge_scaled = False
+        try:
+            logits, box_encodings = model.predict(input_v, coords, kps, edges,
+                                                  False)
+        finally:
+            model.edge_scaled = was
     probs = model.postprocess(logits)
     t = lap('gnn inference', t)
     label_map = kitti_output.LABEL_MAPS[config['label_method']]
@@ -207,7 +219,7 @@ class _Frame(object):
     """One frame on its way through FramePipeline."""
     __slots__ = ("idx", "points", "calib", "stream", "ev", "graph", "probs",
                  "box_enc", "cand", "host_a", "n_rec", "host_b", "n_cand",
-                 "rerun", "t_fetch")
+                 "rerun", "t_fetch", "scale_row")
 
 
 class FramePipeline(object):
@@ -286,6 +298,7 @@ class FramePipeline(object):
                 **cfg['runtime_graph_gen_kwargs'])
             ev[1].record()
             coords, kps, edges = graph
+            f.scale_row = model.edge_scale_begin_pass()
             logits, box_enc = model.predict(_input_features(cfg, f.points),
                                             coords, kps, edges, False)
             probs = model.postprocess(logits)
@@ -293,9 +306,18 @@ class FramePipeline(object):
             frame = edges[0]._pgnn_count.frame
             cand = nms.select_candidates_dyn(probs, frame.tensor[0:1])
             n_rec = int(frame.tensor.numel())
-            host = torch.empty(n_rec + 1, dtype=torch.int32, pin_memory=True)
+            # (behind them this pass's row of the scaled edge kernels' flags,
+            # in the same read)
+            flags = model.edge_scale_flags()
+            if flags is not None:
+                flags = flags[f.scale_row]
+            n_fl = 0 if flags is None else int(flags.numel())
+            host = torch.empty(n_rec + 1 + n_fl, dtype=torch.int32,
+                               pin_memory=True)
             host[:n_rec].copy_(frame.tensor, non_blocking=True)
-            host[n_rec:].copy_(cand[2], non_blocking=True)
+            host[n_rec:n_rec + 1].copy_(cand[2], non_blocking=True)
+            if n_fl:
+                host[n_rec + 1:].copy_(flags, non_blocking=True)
             ev[3].record()
         f.graph, f.probs, f.box_enc, f.cand = graph, probs, box_enc, cand
         f.host_a, f.n_rec, f.ev = host, n_rec, ev
@@ -322,6 +344,14 @@ class FramePipeline(object):
             f.rerun = True
             for g in self._in_a:
                 g.rerun = True
+        if any(rec[f.n_rec + 1:]) and not self.model.edge_scale_tripped(
+                {f.scale_row: rec[f.n_rec + 1:]}, count=not f.rerun):
+            # likewise the scaled edge stage's guard, whose flags are this
+            # pass's: the frame with the plain kernel (stage C)
+            if not f.rerun:
+                self.td['edge scale reruns'] = \
+                    self.td.get('edge scale reruns', 0) + 1
+            f.rerun = True
         f.n_cand = rec[f.n_rec]
         if f.rerun:
             return
@@ -362,6 +392,8 @@ class FramePipeline(object):
             edge_arith = self.model.edge_arith
             self.model.edge_arith = 'f32' if edge_arith == 'f16x2' \
                 else edge_arith
+            edge_scaled = self.model.edge_scaled
+            self.model.edge_scaled = False
             try:
                 _frame_sequential(self.dataset, f.idx, self.model, self.config,
                                   self.output_dir, self.use_box_merge,
@@ -370,6 +402,7 @@ class FramePipeline(object):
                                   self.write_alpha)
             finally:
                 self.model.edge_arith = edge_arith
+                self.model.edge_scaled = edge_scaled
             return
         f.ev[1].synchronize()
         self._add('decode box + nms', f.ev[0].elapsed_time(f.ev[1]) * 1e-3)
