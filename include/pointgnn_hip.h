@@ -2151,6 +2151,72 @@ int pgnn_png_unfilter(const uint8_t *raw, int64_t width, int64_t height,
                       int32_t palette_entries, int32_t bgr, void *workspace,
                       size_t workspace_bytes, uint8_t *image, void *stream);
 
+/* ---- PNG encode: a device image -> a zlib stream ("pgnn deflate v1") --------
+ * The compressed half of writing an 8-bit RGB PNG (the file around it, and the
+ * IDAT CRC, stay on the host: pointgnn_amd/png.py).  Only the compressed bytes
+ * leave the device.  The output is defined to the bit and is a pure function
+ * of (image, chunk_bytes); tests/_deflate_cases.py restates it in Python.
+ *
+ * input    image: device uint8 [height, width, 3], R, G, B; row y starts at
+ *   image + y * row_stride_bytes (row_stride_bytes >= 3 * width; the 3 * width
+ *   bytes of a row are contiguous).  height, width >= 1.
+ *   S is the PNG scanline stream: every row is one filter byte 0 followed by
+ *   its 3 * width bytes.  R = 3 * width + 1 is its row stride, n = height * R
+ *   its length.  (What render.png_bytes hands zlib: filter type 0 on every
+ *   row.)
+ * chunks   C = chunk_bytes, a multiple of 256 with 256 <= C <= 32768.  Chunk c
+ *   covers S[c C, min(n, (c + 1) C)); K = ceil(n / C) chunks, compressed
+ *   independently of each other.
+ * tokens   of a chunk [a, e): parse greedily from i = a.  The candidate
+ *   distances, in this order, are D = (1, 3, R); R is dropped when R > 32768.
+ *   Candidate d is valid at i only if i - d >= a (a match never reads before
+ *   its own chunk).  L_d(i) is the largest L <= min(258, e - i) with
+ *   S[i + j] == S[i + j - d] for all j < L (sources may overlap the match, as
+ *   in deflate); 0 for a candidate that is not valid.  Take the largest L_d,
+ *   ties to the earlier entry of D.  If it is >= 3 emit the match (L, d) and
+ *   advance i by L; otherwise emit the literal S[i] and advance i by 1.
+ * bits     each chunk is ONE block with the fixed Huffman codes of RFC 1951
+ *   3.2.6 (BTYPE = 01): literals 0..143 in 8 bits, 144..255 in 9, length
+ *   codes 257..285 with their extra bits (258 is code 285), 5-bit distance
+ *   codes with their extra bits, end-of-block = code 256.  BFINAL is 1 on the
+ *   last chunk only.  After every chunk but the last comes an empty stored
+ *   block: the header bits 000, zero bits to the next byte boundary, the bytes
+ *   00 00 FF FF -- so every chunk starts on a byte boundary.  The last chunk
+ *   is padded with zero bits to a byte boundary.
+ * wrapper  the bytes 78 01, the blocks, the Adler-32 of S, big-endian.  With
+ *   (A, B) of a chunk started at (1, 0), two neighbours combine as
+ *     A = (A1 + A2 - 1) mod 65521,  B = (B1 + B2 + len2 * (A1 - 1)) mod 65521
+ *   and the trailer is B << 16 | A of the whole stream.
+ * capacity a chunk of len stream bytes takes at most
+ *     slot(len) = floor((9 len + 20) / 8) + 4 bytes
+ *   (3 header bits, at most 9 bits per byte -- the dearest match, length 3 at
+ *   a distance with 13 extra bits, is 25 bits --, 7 bits of end-of-block, 3
+ *   bits of stored header, padding, 4 bytes), so with n = q C + r, 0 <= r < C,
+ *     out_capacity = 6 + q slot(C) + (r > 0 ? slot(r) : 0)
+ *   bytes always suffice; the entry requires at least that many.
+ * out      device uint8 [out_capacity], 4-byte aligned; *out_bytes_dev (device
+ *   int64) receives the stream's length, out[0 .. length) the stream; no byte
+ *   at or beyond `length` is written.  The length exists on the device only:
+ *   nothing is read back here.
+ * Three launches on `stream`: one workgroup per chunk, at most one per CU, the
+ * rest of the chunks taken in turn (the chunk in LDS, match
+ * lengths from 32-byte compare masks, the greedy chain through per-segment
+ * exits, bits packed in LDS and stored as whole slots), one workgroup that
+ * scans the chunks' byte counts and Adler pairs, one that packs the slots into
+ * `out` a dword per lane (csrc/png_encode.hip).
+ * PGNN_E_INVALID (nothing enqueued): height or width < 1, a stream length
+ * beyond int64 or more than 2^31 - 1 chunks; chunk_bytes not a multiple of 256
+ * in 256..32768; row_stride_bytes < 3 * width; a null pointer; `out` not
+ * 4-byte or `workspace` not 16-byte aligned; out_capacity below the formula.
+ * PGNN_E_WORKSPACE: workspace_bytes below
+ * pgnn_png_encode_workspace_bytes (which is 0 for arguments out of range).    */
+size_t pgnn_png_encode_workspace_bytes(int64_t height, int64_t width,
+                                       int32_t chunk_bytes);
+int pgnn_png_encode(const uint8_t *image, int64_t height, int64_t width,
+                    int64_t row_stride_bytes, int32_t chunk_bytes,
+                    void *workspace, size_t workspace_bytes, uint8_t *out,
+                    int64_t out_capacity, int64_t *out_bytes_dev, void *stream);
+
 /* ---- diagnostics (not part of the reference-facing surface) -------------- */
 /* Process-wide knobs for benchmarks and tests; see "Conventions".  Keys:
  *   launch shape   scatter_rows_per_wave, scatter_nt, mlp_blocks_per_cu,

@@ -692,13 +692,15 @@ def plot_pr(result, metric, cls, width=640, height=480):
                        anchor='tl')
 
 
-def write_pr_plots(result, directory, fmt='png'):
+def write_pr_plots(result, directory, fmt='png', png_encoder='zlib'):
     """plot_pr of every class of the report and metric that has ground truth,
-    as <directory>/<class>_<report name>.<fmt>, fmt 'png' or 'ppm'.  Returns
-    the paths."""
+    as <directory>/<class>_<report name>.<fmt>, fmt 'png' or 'ppm'.
+    png_encoder: 'zlib' (host) or 'device', render.write_png's `encoder`.
+    Returns the paths."""
     from . import render as R
     if fmt not in ('png', 'ppm'):
         raise ValueError("fmt must be 'png' or 'ppm', got %r" % (fmt,))
+    R._check_encoder(png_encoder)
     os.makedirs(directory, exist_ok=True)
     paths = []
     for cls in result.classes:
@@ -711,7 +713,10 @@ def write_pr_plots(result, directory, fmt='png'):
             path = os.path.join(directory, '%s_%s.%s' % (
                 cls.lower(), stem, fmt))
             image = plot_pr(result, key, c)
-            (R.write_png if fmt == 'png' else R.write_ppm)(path, image)
+            if fmt == 'png':
+                R.write_png(path, image, encoder=png_encoder)
+            else:
+                R.write_ppm(path, image)
             paths.append(path)
     return paths
 
@@ -740,6 +745,10 @@ def parse_args(argv=None):
                     help="write the precision/recall data files "
                          "(<class>_detection.txt, ...) and one plot per class "
                          "and metric into DIR")
+    ap.add_argument('--png-encoder', choices=('zlib', 'device'),
+                    default='zlib',
+                    help="with --plot: compress the plots on the host (zlib) "
+                         "or on the GPU (device: faster, larger files)")
     return ap.parse_args(argv)
 
 
@@ -756,7 +765,7 @@ def main(argv=None):
     print(result.format())
     if args.plot:
         write_pr_data(result, args.plot)
-        write_pr_plots(result, args.plot)
+        write_pr_plots(result, args.plot, png_encoder=args.png_encoder)
     if args.json:
         print(json.dumps(result.to_json()))
     return 0

@@ -17,6 +17,17 @@ Supported: bit depth 8, no interlace, colour types 0 (grey), 2 (RGB), 3
 (palette), 4 (grey + alpha), 6 (RGBA).  Alpha is dropped, not composited, and
 tRNS is ignored, as `cv2.imread`'s default flag does.  Anything else raises
 ValueError naming the property.
+
+And device images -> PNG files, cut the other way round: deflate is where the
+time goes (render.png_bytes: one host thread in zlib), so that half runs on
+the device and only the compressed bytes come back.
+
+    data = deflate_device(image)  # the zlib stream 'pgnn deflate v1'   (device)
+    data = encode_png(image)      # signature, IHDR, IDAT + CRC, IEND   (host)
+
+8-bit RGB, filter type 0 on every row, fixed Huffman codes: larger files than
+zlib's, written many times faster (csrc/png_encode.hip, include/pointgnn_hip.h
+"PNG encode"; the stream is defined to the bit there).
 """
 import struct
 import zlib
@@ -167,6 +178,101 @@ def unfilter(raw, info, order='bgr', device=None):
             entries, int(order == 'bgr'), _lib.ptr(ws), ws_bytes,
             _lib.ptr(image), _lib.stream_ptr()), "pgnn_png_unfilter")
     return image
+
+
+# ---- encode: device image -> zlib stream -> file ---------------------------------
+DEFAULT_CHUNK_BYTES = 32768
+
+
+def _check_chunk(chunk_bytes):
+    if isinstance(chunk_bytes, bool) or int(chunk_bytes) != chunk_bytes or \
+            chunk_bytes % 256 or not 256 <= chunk_bytes <= 32768:
+        raise ValueError("chunk_bytes must be a multiple of 256 in "
+                         "256..32768, got %r" % (chunk_bytes,))
+    return int(chunk_bytes)
+
+
+def deflate_capacity(height, width, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """out_capacity of pgnn_png_encode (the header's formula): the most
+    bytes the stream of a height x width image can take."""
+    c = _check_chunk(chunk_bytes)
+    slot = lambda length: (9 * length + 20) // 8 + 4
+    full, rest = divmod(int(height) * (3 * int(width) + 1), c)
+    return 6 + full * slot(c) + (slot(rest) if rest else 0)
+
+
+def _device_image(image):
+    """-> a CUDA uint8 [H, W, 3] tensor whose rows are dense (the rows
+    themselves may be strided); anything else is uploaded or copied."""
+    import torch
+    if not isinstance(image, torch.Tensor):
+        image = torch.from_numpy(np.ascontiguousarray(image))
+    if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3:
+        raise ValueError("image must be uint8 [H, W, 3], got %s %r" % (
+            image.dtype, tuple(image.shape)))
+    h, w = int(image.shape[0]), int(image.shape[1])
+    if h < 1 or w < 1:
+        raise ValueError("image must be at least 1 x 1, got %d x %d" % (w, h))
+    if not image.is_cuda:
+        image = image.to(torch.device("cuda", torch.cuda.current_device()))
+    if not (image.stride(2) == 1 and image.stride(1) == 3 and
+            (h == 1 or image.stride(0) >= 3 * w)):
+        image = image.contiguous()
+    return image
+
+
+def _deflate_enqueue(image, chunk_bytes):
+    """pgnn_png_encode on the current stream -> (out uint8 [capacity], the
+    stream's length as an int64 [1] tensor); nothing is read back."""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    c = _check_chunk(chunk_bytes)
+    image = _device_image(image)
+    h, w = int(image.shape[0]), int(image.shape[1])
+    row_stride = int(image.stride(0)) if h > 1 else 3 * w
+    dev = image.device
+    with torch.cuda.device(dev):
+        capacity = deflate_capacity(h, w, c)
+        out = torch.empty((capacity,), dtype=torch.uint8, device=dev)
+        n_out = torch.empty((1,), dtype=torch.int64, device=dev)
+        ws_bytes = int(lib.pgnn_png_encode_workspace_bytes(h, w, c))
+        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.pgnn_png_encode(
+            _lib.ptr(image), h, w, row_stride, c, _lib.ptr(ws), ws_bytes,
+            _lib.ptr(out), capacity, _lib.ptr(n_out), _lib.stream_ptr()),
+            "pgnn_png_encode")
+    return out, n_out
+
+
+def deflate_device(image, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """uint8 [H, W, 3] RGB (a CUDA tensor; anything else is uploaded) -> the
+    zlib stream of its PNG scanlines, filter type 0 on every row, compressed
+    on the device ('pgnn deflate v1', include/pointgnn_hip.h "PNG encode").
+    The device is read twice: the length, then that many bytes; the image is
+    never copied to the host."""
+    out, n_out = _deflate_enqueue(image, chunk_bytes)
+    n = int(n_out.item())
+    return out[:n].cpu().numpy().tobytes()
+
+
+def _chunk(kind, data):
+    body = kind + data
+    return struct.pack(">I", len(data)) + body + struct.pack(
+        ">I", zlib.crc32(body) & 0xffffffff)
+
+
+def encode_png(image, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """The PNG file of a uint8 [H, W, 3] RGB image, compressed on the device
+    (deflate_device): signature, IHDR (8-bit RGB), one IDAT, IEND -- the
+    layout render.png_bytes writes; the IDAT CRC is zlib.crc32 on the host."""
+    image = _device_image(image)
+    h, w = int(image.shape[0]), int(image.shape[1])
+    return b"".join([
+        SIGNATURE,
+        _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)),
+        _chunk(b"IDAT", deflate_device(image, chunk_bytes)),
+        _chunk(b"IEND", b"")])
 
 
 def read_png(path_or_bytes, order='bgr', device=None):

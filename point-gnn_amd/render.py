@@ -13,7 +13,7 @@ drawn: the interactive 3D window.
     view = bev_view()                                 # 800 x 800, forward is up
     img = render(view, points=xyz, point_colors=colorize(inten, 0, 1),
                  segments=box_segments(boxes), segment_colors=(255, 0, 0))
-    write_png('frame.png', img)
+    write_png('frame.png', img)           # encoder='device': deflate on the GPU
     draw_text(img, ['C | 0.912'], [(40, 120)], colors=(0, 255, 0))
     render_results(dataset, result_dir, render_dir, views=('bev', 'camera'))
     python -m pointgnn_amd.render DATASET_DIR RESULT_DIR RENDER_DIR --view bev
@@ -736,8 +736,25 @@ def _host_image(image):
     return image
 
 
-def png_bytes(image, compress_level=6):
-    """8-bit RGB PNG, filter type 0 on every row, one IDAT chunk."""
+PNG_ENCODERS = ('zlib', 'device')
+
+
+def _check_encoder(encoder):
+    if encoder not in PNG_ENCODERS:
+        raise ValueError("encoder must be 'zlib' or 'device', got %r"
+                         % (encoder,))
+
+
+def png_bytes(image, compress_level=6, encoder='zlib'):
+    """8-bit RGB PNG, filter type 0 on every row, one IDAT chunk.  encoder
+    'zlib': the image goes to the host and through zlib.compress at
+    compress_level.  'device': png.encode_png -- compressed on the device
+    (fixed Huffman codes, larger files), only the compressed bytes come back;
+    compress_level is not used."""
+    _check_encoder(encoder)
+    if encoder == 'device':
+        from . import png
+        return png.encode_png(image)
     image = _host_image(image)
     h, w = image.shape[:2]
     raw = np.zeros((h, 1 + 3 * w), dtype=np.uint8)
@@ -754,8 +771,8 @@ def png_bytes(image, compress_level=6):
         chunk(b"IEND", b"")])
 
 
-def write_png(path, image, compress_level=6):
-    data = png_bytes(image, compress_level)
+def write_png(path, image, compress_level=6, encoder='zlib'):
+    data = png_bytes(image, compress_level, encoder)
     with open(path, "wb") as f:
         f.write(data)
 
@@ -784,19 +801,25 @@ def image_background(dataset):
 def render_results(dataset, result_dir, render_dir, views=('bev',),
                    frame_indices=None, fmt='png', with_gt=True,
                    background_reader=None, time_dict=None, text=False,
-                   text_plate=None):
+                   text_plate=None, png_encoder='zlib'):
     """Draws every frame of a result directory (<result_dir>/<name>.txt as
     run.run_dataset writes them under <output_dir>/data, or any other KITTI
     result directory) into <render_dir>/<view>/<name>.<fmt>, fmt 'png' or
     'ppm'.  with_gt: also the labels, when the dataset has a label directory.
     background_reader(frame_idx) -> uint8 RGB [H, W, 3] for the camera view
     (image_background(dataset): the frame's own PNG, decoded on the device).
-    text / text_plate: render_frame's.  Sequential: one host read per image.
-    Returns the paths written."""
+    text / text_plate: render_frame's.  png_encoder: png_bytes' `encoder`;
+    with 'device' the image stays on the device and only its compressed bytes
+    are read (time_dict's 'encode png' then holds that encode, 'render' ends
+    at a synchronise).  Sequential: one host read per image (two short ones
+    with 'device').  Returns the paths written."""
     from . import kitti_eval
     import time
+    import torch
     if fmt not in ('png', 'ppm'):
         raise ValueError("fmt must be 'png' or 'ppm', got %r" % (fmt,))
+    _check_encoder(png_encoder)
+    on_device = fmt == 'png' and png_encoder == 'device'
     views = (views,) if isinstance(views, str) else tuple(views)
     for view in views:
         if view not in ('bev', 'camera'):
@@ -824,12 +847,16 @@ def render_results(dataset, result_dir, render_dir, views=('bev',),
             image = render_frame(dataset, frame_idx, det, gt, view=view,
                                  stages=stages, background=background,
                                  text=text, text_plate=text_plate)
-            host = image.cpu().numpy()
+            if on_device:
+                torch.cuda.synchronize(image.device)   # 'render' ends here
+                host = image
+            else:
+                host = image.cpu().numpy()
             t1 = time.time()
             path = os.path.join(render_dir, view, name + '.' + fmt)
             os.makedirs(os.path.dirname(path), exist_ok=True)
             if fmt == 'png':
-                data = png_bytes(host)
+                data = png_bytes(host, encoder=png_encoder)
                 t2 = time.time()
                 with open(path, "wb") as f:
                     f.write(data)
@@ -863,6 +890,10 @@ def build_parser():
                     help="frame names, one per line (default: every scan)")
     ap.add_argument('--ppm', action='store_true',
                     help="write binary PPM files instead of PNG")
+    ap.add_argument('--png-encoder', choices=PNG_ENCODERS, default='zlib',
+                    help="zlib: compress on the host (level 6); device: "
+                         "compress on the GPU, only the compressed bytes are "
+                         "read back (faster, larger files)")
     ap.add_argument('--image-background', action='store_true',
                     help="camera view: draw on the frame's decoded image "
                          "instead of black")
@@ -888,7 +919,7 @@ def main(argv=None):
                            fmt='ppm' if args.ppm else 'png',
                            background_reader=image_background(dataset)
                            if args.image_background else None,
-                           text=args.text)
+                           text=args.text, png_encoder=args.png_encoder)
     print("wrote %d images to %s" % (len(paths), args.render_dir))
     return 0
 

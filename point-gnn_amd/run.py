@@ -142,7 +142,7 @@ def run_dataset(dataset, config, checkpoint_dir, output_dir,
                 frame_indices=None, use_box_merge=True, use_box_score=True,
                 params=None, log=None, image_reader=None, edge_arith='f32',
                 pipelined=True, in_flight=3, prefetch=4, write_alpha=False,
-                render_dir=None, render_views=('bev',)):
+                render_dir=None, render_views=('bev',), png_encoder='zlib'):
     """run.py:203-433 over `frame_indices` (default: the whole dataset).
     Writes `<output_dir>/data/<frame name>.txt` in the reference's format and
     returns the accumulated `time_dict` (seconds per stage under run.py's
@@ -166,7 +166,8 @@ def run_dataset(dataset, config, checkpoint_dir, output_dir,
     `<render_dir>/<view>/<frame name>.png` for each of render_views ('bev',
     'camera'): render.render_results on the files just written, what
     run.py -l 1|2 shows in its windows.  The txt files do not depend on it;
-    its time is time_dict['render'], outside 'wall'."""
+    its time is time_dict['render'], outside 'wall'.  png_encoder: 'zlib'
+    (host) or 'device', render.png_bytes' `encoder`."""
     model = build_model(config, checkpoint_dir, params, edge_arith)
     if frame_indices is None:
         frame_indices = range(dataset.num_files)
@@ -192,7 +193,8 @@ def run_dataset(dataset, config, checkpoint_dir, output_dir,
         t_render = time.time()
         render.render_results(dataset, os.path.join(output_dir, 'data'),
                               render_dir, views=render_views,
-                              frame_indices=frame_indices)
+                              frame_indices=frame_indices,
+                              png_encoder=png_encoder)
         time_dict['render'] = time.time() - t_render
     return time_dict
 
