@@ -1800,6 +1800,92 @@ int pgnn_kitti_pair_orientation(const int32_t *gt_offsets /* host */,
                                 size_t workspace_bytes, double *sim,
                                 void *stream);
 
+/* pgnn_kitti_match: what the matching of ONE (metric, class, difficulty)
+ * decides at ONE score threshold, per box, for a whole frame set (DESIGN.md
+ * section 9.13).  Inputs, caps, error codes and argument checks are those of
+ * pgnn_kitti_eval_ex; also PGNN_E_INVALID: metric, cls or difficulty outside
+ * 0..2, a score_threshold that is not finite, a loc_floor that is not in
+ * [0, 1].  The cleaning flags and the overlaps come from the evaluation's own
+ * kernels, the matching is section 9.5's with compute_fp, at score_threshold,
+ * with min_overlap[metric][cls] (NULL = the official table).  The number of
+ * launches does not depend on n_frames and nothing is read back.
+ *
+ *   det_outcome  [n_det] int32, a PGNN_KITTI_DET_* code; the rules are tested
+ *                in the order of the codes (idj = the detection's cleaning
+ *                result, ig = a ground truth's):
+ *     OTHER            idj == -1
+ *     BELOW            score < score_threshold
+ *     TP               assigned, ig == 0 and idj == 0
+ *     MATCHED_IGNORED  assigned, ig == 1 or idj == 1
+ *     IGNORED_SMALL    idj == 1, not assigned
+ *     DONTCARE         2D metric only: absorbed by a DontCare row (the first
+ *                      row, in file order, whose detection-criterion overlap
+ *                      with it is > min_overlap)
+ *     FP_*             a false positive.  b = its largest overlap with a
+ *                      ground truth of ig >= 0, x = with one of ig == -1 that
+ *                      is no DontCare (smallest index on ties; an overlap of
+ *                      0 names no ground truth):
+ *       FP_DUPLICATE     b > min_overlap (that ground truth went elsewhere)
+ *       FP_CONFUSION     else x >= loc_floor and x > b
+ *       FP_LOCALISATION  else b >= loc_floor
+ *       FP_BACKGROUND    else
+ *   gt_outcome   [n_gt] int32, a PGNN_KITTI_GT_* code:
+ *     OTHER            ig == -1
+ *     IGNORED / IGNORED_MATCHED   ig == 1, not assigned / assigned
+ *     TP / MATCHED_SMALL          ig == 0, assigned, idj == 0 / idj == 1
+ *     FN_LOW_SCORE     not assigned; a detection of idj != -1 and score <
+ *                      score_threshold overlaps it by more than min_overlap
+ *     FN_LOCALISATION  else a detection of idj == 0 and score >=
+ *                      score_threshold has loc_floor <= overlap <= min_overlap
+ *     FN_MISSED        else
+ *   gt_partner, det_partner   int32, an index within the frame or -1: the
+ *                assigned pair (TP, MATCHED_IGNORED, IGNORED_MATCHED,
+ *                MATCHED_SMALL); the ground truth of b (FP_DUPLICATE,
+ *                FP_LOCALISATION) or of x (FP_CONFUSION); the absorbing row
+ *                (DONTCARE); for FN_LOW_SCORE / FN_LOCALISATION the detection
+ *                of the largest overlap among those the rule names (smallest
+ *                index on ties)
+ *   det_overlap  [n_det] float64: the overlap with the partner, a copy of the
+ *                overlap table's entry (DONTCARE: the detection-criterion
+ *                overlap); 0 without a partner
+ *   totals       [PGNN_KITTI_MATCH_TOTALS] int64: boxes per detection code,
+ *                then per ground-truth code
+ * Every output is an integer or a copy: the same bits on every run and every
+ * stream.  Outcome pointers may be NULL when their count is 0.              */
+#define PGNN_KITTI_DET_OTHER 0
+#define PGNN_KITTI_DET_BELOW 1
+#define PGNN_KITTI_DET_TP 2
+#define PGNN_KITTI_DET_MATCHED_IGNORED 3
+#define PGNN_KITTI_DET_IGNORED_SMALL 4
+#define PGNN_KITTI_DET_DONTCARE 5
+#define PGNN_KITTI_DET_FP_DUPLICATE 6
+#define PGNN_KITTI_DET_FP_CONFUSION 7
+#define PGNN_KITTI_DET_FP_LOCALISATION 8
+#define PGNN_KITTI_DET_FP_BACKGROUND 9
+#define PGNN_KITTI_DET_CODES 10
+#define PGNN_KITTI_GT_OTHER 0
+#define PGNN_KITTI_GT_IGNORED 1
+#define PGNN_KITTI_GT_IGNORED_MATCHED 2
+#define PGNN_KITTI_GT_TP 3
+#define PGNN_KITTI_GT_MATCHED_SMALL 4
+#define PGNN_KITTI_GT_FN_LOW_SCORE 5
+#define PGNN_KITTI_GT_FN_LOCALISATION 6
+#define PGNN_KITTI_GT_FN_MISSED 7
+#define PGNN_KITTI_GT_CODES 8
+#define PGNN_KITTI_MATCH_TOTALS (PGNN_KITTI_DET_CODES + PGNN_KITTI_GT_CODES)
+size_t pgnn_kitti_match_workspace_bytes(int64_t n_frames, int64_t n_gt,
+                                        int64_t n_det, int64_t n_pairs);
+int pgnn_kitti_match(const int32_t *gt_offsets /* host */,
+                     const int32_t *det_offsets /* host */, int64_t n_frames,
+                     const double *gt_boxes, const int32_t *gt_names,
+                     const double *det_boxes, const int32_t *det_names,
+                     const double *min_overlap /* host */, int32_t metric,
+                     int32_t cls, int32_t difficulty, double score_threshold,
+                     double loc_floor, void *workspace, size_t workspace_bytes,
+                     int32_t *gt_outcome, int32_t *gt_partner,
+                     int32_t *det_outcome, int32_t *det_partner,
+                     double *det_overlap, int64_t *totals, void *stream);
+
 size_t pgnn_kitti_ingest_workspace_bytes(int64_t n_points);
 int pgnn_kitti_cam_points_in_image(
     const float *velo_points, int64_t n_points, const float *velo_to_cam_3x4,

@@ -37,6 +37,10 @@
 // conflicts), ceil(max detections / 64) words per lane, at most 32 KiB per
 // workgroup of four waves.  Waves stride over frames and add their counts once
 // at the end, so a counter sees one atomic per wave, not one per frame.
+//
+// pgnn_kitti_match keeps what the matching of one
+// combination at one threshold decides, box by box: prep, scan and pairs as
+// above, then kitti_match_kernel, described where it stands.
 #include "box_overlap.h"
 
 namespace pgnn {
@@ -845,6 +849,320 @@ bool sizes_in_range(int64_t n_frames, int64_t n_gt, int64_t n_det,
            n_pairs > n_gt * n_det);
 }
 
+// ---- per-box outcomes of one combination at one threshold ----
+//
+// One wave per frame, the lanes over the frame's boxes: lane l owns the
+// detections j = l, l + 64, ... and the ground truths i = l, l + 64, ...
+// Everything a box's later steps need to know about it (is this detection
+// taken, which ground truth took it, which detection did this ground truth
+// take) is written and read by its owning lane only: the taken set is 16 bits
+// of a register, the partners live in the output arrays themselves.
+//
+//   matching   serial over the ground truths of ig >= 0, as match_frame<true>
+//              walks them.  The serial inner loop's choice is the valid
+//              (idj == 0) candidate of the largest overlap, the smallest index
+//              on ties, else the first idj == 1 candidate: each lane finds
+//              that among its own detections, six xor-shuffles find it for the
+//              wave.
+//   detections lane = detection.  A left-over one walks its column of the
+//              frame's pair block once (the lanes read neighbouring doubles):
+//              the first absorbing DontCare row, b and x.
+//   truths     lane = ground truth.  An unmatched one walks its row once.
+//   totals     an LDS histogram per workgroup, one int64 atomic per code.
+constexpr int kDetCodes = PGNN_KITTI_DET_CODES;
+constexpr int kMatchTotals = PGNN_KITTI_MATCH_TOTALS;
+static_assert(kMaxDet <= 64 * 32, "the taken set is one 32-bit register");
+
+struct MatchOut {
+  int32_t *gt_outcome, *gt_partner, *det_outcome, *det_partner;
+  double *det_overlap;
+  int64_t *totals;
+};
+
+__global__ __launch_bounds__(64 * kWaves) void kitti_match_kernel(
+    const int32_t *__restrict__ gt_off, const int32_t *__restrict__ det_off,
+    const int64_t *__restrict__ pair_off, int64_t n_frames,
+    const int32_t *__restrict__ gt_flags, const int32_t *__restrict__ det_flags,
+    const double *__restrict__ det, const double *__restrict__ ov_metric,
+    const double *__restrict__ ov_dontcare, int s, double min_ov, double thresh,
+    double loc_floor, bool is_2d, const MatchOut out) {
+  __shared__ unsigned hist[kMatchTotals];
+  const int lane = threadIdx.x;
+  const int tid = threadIdx.y * 64 + lane;
+  if (tid < kMatchTotals) hist[tid] = 0u;
+  __syncthreads();
+  for (int64_t f = (int64_t)blockIdx.x * kWaves + threadIdx.y; f < n_frames;
+       f += (int64_t)gridDim.x * kWaves) {
+    const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
+    const int d0 = det_off[f], nd = det_off[f + 1] - d0;
+    const int32_t *gfl = gt_flags + g0, *dfl = det_flags + d0;
+    const double *drow = det + (int64_t)d0 * kRow;
+    const double *fo = ov_metric + pair_off[f];
+    const double *fdc = ov_dontcare + pair_off[f];
+    int32_t *gp = out.gt_partner + g0, *dp = out.det_partner + d0;
+
+    // this lane's detections: bit k speaks of detection k * 64 + lane
+    unsigned open = 0u;   // idj >= 0 and score >= thresh: may be assigned
+    unsigned valid = 0u;  // idj == 0
+    unsigned taken = 0u;
+    for (int j = lane, k = 0; j < nd; j += 64, ++k) {
+      const int idj = flag_of(dfl[j], s);
+      if (idj >= 0 && !(drow[(int64_t)j * kRow + SCORE] < thresh))
+        open |= 1u << k;
+      if (idj == 0) valid |= 1u << k;
+      dp[j] = -1;
+    }
+    for (int i = lane; i < ng; i += 64) gp[i] = -1;
+
+    // §9.5 "Matching", compute_fp
+    for (int i = 0; i < ng; ++i) {
+      if (flag_of(gfl[i], s) < 0) continue;  // the same in every lane
+      const double *row = fo + (int64_t)i * nd;
+      double best = 0.0;  // a candidate's overlap is > min_ov >= 0
+      int best_j = INT32_MAX, small_j = INT32_MAX;
+      for (int j = lane, k = 0; j < nd; j += 64, ++k) {
+        if (!(((open & ~taken) >> k) & 1u)) continue;
+        const double o = row[j];
+        if (!(o > min_ov)) continue;
+        if ((valid >> k) & 1u) {
+          if (o > best) {
+            best = o;
+            best_j = j;
+          }
+        } else if (j < small_j) {
+          small_j = j;
+        }
+      }
+#pragma unroll
+      for (int m = 32; m > 0; m >>= 1) {
+        const double o2 = __shfl_xor(best, m);
+        const int j2 = __shfl_xor(best_j, m);
+        const int s2 = __shfl_xor(small_j, m);
+        if (o2 > best || (o2 == best && j2 < best_j)) {
+          best = o2;
+          best_j = j2;
+        }
+        small_j = s2 < small_j ? s2 : small_j;
+      }
+      const int det_idx = best_j != INT32_MAX ? best_j : small_j;
+      if (det_idx == INT32_MAX) continue;
+      if ((det_idx & 63) == lane) {
+        taken |= 1u << (det_idx >> 6);
+        dp[det_idx] = i;
+      }
+      if ((i & 63) == lane) gp[i] = det_idx;
+    }
+
+    // detections
+    for (int j = lane, k = 0; j < nd; j += 64, ++k) {
+      const int idj = flag_of(dfl[j], s);
+      int code, partner = -1;
+      double with = 0.0;
+      if (idj < 0) {
+        code = PGNN_KITTI_DET_OTHER;
+      } else if (!((open >> k) & 1u)) {
+        code = PGNN_KITTI_DET_BELOW;
+      } else if ((taken >> k) & 1u) {
+        partner = dp[j];
+        code = (flag_of(gfl[partner], s) == 0 && idj == 0)
+                   ? PGNN_KITTI_DET_TP
+                   : PGNN_KITTI_DET_MATCHED_IGNORED;
+        with = fo[(int64_t)partner * nd + j];
+      } else if (idj == 1) {
+        code = PGNN_KITTI_DET_IGNORED_SMALL;
+      } else {
+        // b: over the ground truths of ig >= 0; x: over those of ig == -1
+        // that are no DontCare; an overlap of 0 names no ground truth
+        double b = 0.0, x = 0.0;
+        int b_i = -1, x_i = -1, dc_i = -1;
+        for (int i = 0; i < ng; ++i) {
+          const int32_t w = gfl[i];
+          const double o = fo[(int64_t)i * nd + j];
+          if (flag_of(w, s) >= 0) {
+            if (o > b) {
+              b = o;
+              b_i = i;
+            }
+          } else if (w & kDontCareBit) {
+            if (is_2d && dc_i < 0 && fdc[(int64_t)i * nd + j] > min_ov)
+              dc_i = i;
+          } else if (o > x) {
+            x = o;
+            x_i = i;
+          }
+        }
+        if (dc_i >= 0) {
+          code = PGNN_KITTI_DET_DONTCARE;
+          partner = dc_i;
+          with = fdc[(int64_t)dc_i * nd + j];
+        } else if (b > min_ov) {
+          code = PGNN_KITTI_DET_FP_DUPLICATE;
+          partner = b_i;
+          with = b;
+        } else if (x >= loc_floor && x > b) {
+          code = PGNN_KITTI_DET_FP_CONFUSION;
+          partner = x_i;
+          with = x;
+        } else if (b >= loc_floor) {
+          code = PGNN_KITTI_DET_FP_LOCALISATION;
+          partner = b_i;
+          with = b;
+        } else {
+          code = PGNN_KITTI_DET_FP_BACKGROUND;
+        }
+      }
+      out.det_outcome[d0 + j] = code;
+      dp[j] = partner;
+      out.det_overlap[d0 + j] = with;
+      atomicAdd(&hist[code], 1u);
+    }
+
+    // ground truths
+    for (int i = lane; i < ng; i += 64) {
+      const int ig = flag_of(gfl[i], s);
+      int code, partner = gp[i];
+      if (ig < 0) {
+        code = PGNN_KITTI_GT_OTHER;
+      } else if (ig == 1) {
+        code = partner >= 0 ? PGNN_KITTI_GT_IGNORED_MATCHED
+                            : PGNN_KITTI_GT_IGNORED;
+      } else if (partner >= 0) {
+        code = flag_of(dfl[partner], s) == 0 ? PGNN_KITTI_GT_TP
+                                             : PGNN_KITTI_GT_MATCHED_SMALL;
+      } else {
+        const double *row = fo + (int64_t)i * nd;
+        double low = 0.0, loc = 0.0;
+        int low_j = -1, loc_j = -1;
+        for (int j = 0; j < nd; ++j) {
+          const int idj = flag_of(dfl[j], s);
+          if (idj < 0) continue;
+          const double o = row[j];
+          if (drow[(int64_t)j * kRow + SCORE] < thresh) {
+            if (o > min_ov && o > low) {
+              low = o;
+              low_j = j;
+            }
+          } else if (idj == 0 && o >= loc_floor && o <= min_ov &&
+                     (loc_j < 0 || o > loc)) {
+            loc = o;
+            loc_j = j;
+          }
+        }
+        if (low_j >= 0) {
+          code = PGNN_KITTI_GT_FN_LOW_SCORE;
+          partner = low_j;
+        } else if (loc_j >= 0) {
+          code = PGNN_KITTI_GT_FN_LOCALISATION;
+          partner = loc_j;
+        } else {
+          code = PGNN_KITTI_GT_FN_MISSED;
+        }
+      }
+      out.gt_outcome[g0 + i] = code;
+      gp[i] = partner;
+      atomicAdd(&hist[kDetCodes + code], 1u);
+    }
+  }
+  __syncthreads();  // every thread arrives: no return above
+  if (tid < kMatchTotals && hist[tid])
+    atomicAdd((unsigned long long *)out.totals + tid,
+              (unsigned long long)hist[tid]);
+}
+
+// the workspace of pgnn_kitti_match: the offsets, flags and four pair planes
+// of an evaluation, and the words kitti_prep_kernel clears beside the flags
+struct MatchWorkspace {
+  Workspace w;
+  int64_t *counters, *n_gt;
+};
+
+MatchWorkspace carve_match(void *base, size_t size, int64_t n_frames,
+                           int64_t n_gt, int64_t n_det, int64_t n_pairs) {
+  Arena arena(base, base ? size : 0);
+  MatchWorkspace m;
+  Workspace &w = m.w;
+  w.gt_off = arena.take<int32_t>((size_t)n_frames + 1);
+  w.det_off = arena.take<int32_t>((size_t)n_frames + 1);
+  w.pair_off = arena.take<int64_t>((size_t)n_frames + 1);
+  w.gt_flags = arena.take<int32_t>((size_t)(n_gt > 0 ? n_gt : 1));
+  w.det_flags = arena.take<int32_t>((size_t)(n_det > 0 ? n_det : 1));
+  w.n_rec = arena.take<int32_t>(kCombos);
+  w.ov = arena.take<double>((size_t)(n_pairs > 0 ? n_pairs : 1) * 4);
+  w.wave_sim = nullptr;
+  w.keys = nullptr;
+  m.counters = arena.take<int64_t>((size_t)kCombos * kPts * 3);
+  m.n_gt = arena.take<int64_t>(kCombos);
+  w.bytes = align_up(arena.used, 256);
+  return m;
+}
+
+int match_entry(const int32_t *gt_offsets, const int32_t *det_offsets,
+                int64_t n_frames, const double *gt_boxes,
+                const int32_t *gt_names, const double *det_boxes,
+                const int32_t *det_names, const double *min_overlap_host,
+                int32_t metric, int32_t cls, int32_t difficulty,
+                double score_threshold, double loc_floor, void *workspace,
+                size_t workspace_bytes, const MatchOut &o, hipStream_t stream) {
+  const char *who = "kitti_match";
+  Sizes sz;
+  if (int rc = check_offsets(who, gt_offsets, det_offsets, n_frames, &sz))
+    return rc;
+  PGNN_REQUIRE((sz.n_gt == 0 || (gt_boxes && gt_names)) &&
+                   (sz.n_det == 0 || (det_boxes && det_names)),
+               PGNN_E_INVALID, "kitti_match: null box or name pointer");
+  PGNN_REQUIRE(workspace && o.totals &&
+                   (sz.n_gt == 0 || (o.gt_outcome && o.gt_partner)) &&
+                   (sz.n_det == 0 ||
+                    (o.det_outcome && o.det_partner && o.det_overlap)),
+               PGNN_E_INVALID, "kitti_match: null workspace or output pointer");
+  PGNN_REQUIRE(metric >= 0 && metric < 3 && cls >= 0 && cls < 3 &&
+                   difficulty >= 0 && difficulty < 3,
+               PGNN_E_INVALID,
+               "kitti_match: metric, cls and difficulty are 0, 1 or 2");
+  PGNN_REQUIRE(score_threshold - score_threshold == 0.0,  // no NaN, no inf
+               PGNN_E_INVALID,
+               "kitti_match: score_threshold is not finite");
+  PGNN_REQUIRE(loc_floor >= 0.0 && loc_floor <= 1.0,  // false for a NaN
+               PGNN_E_INVALID, "kitti_match: loc_floor is not in [0, 1]");
+  OverlapTable table;
+  if (int rc = overlap_table(who, min_overlap_host, &table)) return rc;
+  const MatchWorkspace m = carve_match(workspace, workspace_bytes, sz.n_frames,
+                                       sz.n_gt, sz.n_det, sz.n_pairs);
+  const Workspace &w = m.w;
+  PGNN_REQUIRE(w.bytes <= workspace_bytes, PGNN_E_WORKSPACE,
+               "kitti_match: workspace too small");
+
+  // the evaluation's own prep and pair launches: the same flags and overlaps
+  int64_t total = (int64_t)kCombos * kPts * 3;
+  if (sz.n_gt > total) total = sz.n_gt;
+  if (sz.n_det > total) total = sz.n_det;
+  const int64_t prep_blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(kitti_prep_kernel,
+                     dim3((unsigned)(prep_blocks < 4096 ? prep_blocks : 4096)),
+                     dim3(256), 0, stream, gt_boxes, gt_names, sz.n_gt,
+                     det_boxes, det_names, sz.n_det, w.gt_flags, w.det_flags,
+                     (unsigned long long *)nullptr, (int64_t)0, m.counters,
+                     m.n_gt, w.n_rec, total);
+  PGNN_HIP(hipGetLastError());
+  PGNN_HIP(hipMemsetAsync(o.totals, 0, kMatchTotals * sizeof(int64_t), stream));
+  if (int rc = upload_and_pairs<kPairOverlaps>(
+          w, sz, gt_offsets, det_offsets, gt_boxes, gt_names, det_boxes, w.ov,
+          nullptr, nullptr, nullptr, stream))
+    return rc;
+  int64_t groups = (sz.n_frames + kWaves - 1) / kWaves;
+  if (groups < 1) groups = 1;
+  hipLaunchKernelGGL(kitti_match_kernel,
+                     dim3((unsigned)(groups < 2048 ? groups : 2048)),
+                     dim3(64, kWaves), 0, stream, w.gt_off, w.det_off,
+                     w.pair_off, sz.n_frames, w.gt_flags, w.det_flags,
+                     det_boxes, w.ov + metric * sz.n_pairs,
+                     w.ov + kOvDontCare * sz.n_pairs, cls * 3 + difficulty,
+                     table.v[metric * 3 + cls], score_threshold, loc_floor,
+                     metric == 0, o);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
 }  // namespace pgnn
 
@@ -952,5 +1270,31 @@ extern "C" int pgnn_kitti_eval_ex(
                           gt_boxes, gt_names, det_boxes, det_names, workspace,
                           workspace_bytes, gt_alpha, det_alpha, min_overlap,
                           out, (hipStream_t)stream_);
+  PGNN_GUARD_END
+}
+
+extern "C" size_t pgnn_kitti_match_workspace_bytes(int64_t n_frames,
+                                                   int64_t n_gt, int64_t n_det,
+                                                   int64_t n_pairs) {
+  if (!pgnn::sizes_in_range(n_frames, n_gt, n_det, n_pairs)) return 0;
+  return pgnn::carve_match(nullptr, 0, n_frames, n_gt, n_det, n_pairs).w.bytes;
+}
+
+extern "C" int pgnn_kitti_match(
+    const int32_t *gt_offsets, const int32_t *det_offsets, int64_t n_frames,
+    const double *gt_boxes, const int32_t *gt_names, const double *det_boxes,
+    const int32_t *det_names, const double *min_overlap, int32_t metric,
+    int32_t cls, int32_t difficulty, double score_threshold, double loc_floor,
+    void *workspace, size_t workspace_bytes, int32_t *gt_outcome,
+    int32_t *gt_partner, int32_t *det_outcome, int32_t *det_partner,
+    double *det_overlap, int64_t *totals, void *stream_) {
+  PGNN_GUARD_BEGIN
+  const pgnn::MatchOut out = {gt_outcome,  gt_partner,  det_outcome,
+                              det_partner, det_overlap, totals};
+  return pgnn::match_entry(gt_offsets, det_offsets, n_frames, gt_boxes,
+                           gt_names, det_boxes, det_names, min_overlap, metric,
+                           cls, difficulty, score_threshold, loc_floor,
+                           workspace, workspace_bytes, out,
+                           (hipStream_t)stream_);
   PGNN_GUARD_END
 }

@@ -27,6 +27,18 @@ Two additions go through `pgnn_kitti_eval_ex`, and only when asked for:
     result.aos('Car', 'moderate')                   # AOS_R40, beside the 2D AP
     result = evaluate(gt, det, aos=True, det_alpha='box')   # alpha from the box
     result = evaluate(gt, det, min_overlap='loose')  # BEV / 3D at .5 / .25 / .25
+
+Which boxes cost the AP, and why (pgnn_kitti_match): the
+matching of one combination at one score threshold, box by box.
+
+    t = best_f1_threshold(result, '3d', 'Car', 'moderate')
+    errors = match(gt, det, '3d', 'Car', 'moderate', score_threshold=t)
+    errors.fp, errors.totals['DET_FP_LOCALISATION'], errors.frame(0)
+    print(errors.format())
+
+    python -m pointgnn_amd.kitti_eval LABEL_DIR RESULT_DIR --errors
+        [--error-metric 3d] [--error-class Car] [--error-difficulty moderate]
+        [--at-threshold f1|<float>]
 """
 import ctypes
 import json
@@ -556,6 +568,215 @@ def evaluate_dataset(dataset, result_dir, classes=CLASSES, device=None,
     return evaluate(gt, det, classes, device, aos, det_alpha, min_overlap)
 
 
+# ---- per-box outcomes at one threshold ----------------------
+def _codes(prefix):
+    """The header's outcome codes of one side, names in code order."""
+    n = _C[prefix + 'CODES']
+    by_code = {v: k[len(prefix):] for k, v in _C.items()
+               if k.startswith(prefix) and k != prefix + 'CODES'}
+    return tuple(by_code[k] for k in range(n))
+
+
+DET_OUTCOMES = _codes('PGNN_KITTI_DET_')     # DET_OUTCOMES[code] = 'TP', ...
+GT_OUTCOMES = _codes('PGNN_KITTI_GT_')
+DET_FP_KINDS = ('FP_DUPLICATE', 'FP_CONFUSION', 'FP_LOCALISATION',
+                'FP_BACKGROUND')
+GT_FN_KINDS = ('FN_LOW_SCORE', 'FN_LOCALISATION', 'FN_MISSED')
+
+
+def run_match_packed(gt, det, metric, cls, difficulty, score_threshold,
+                     min_overlap=None, loc_floor=0.1, device=None):
+    """pgnn_kitti_match on packed labels (`pack_labels` triples) and indices
+    0..2 -> dict of CUDA tensors: gt_outcome, gt_partner [n_gt] int32,
+    det_outcome, det_partner [n_det] int32, det_overlap [n_det] float64,
+    totals [18] int64.  Nothing has been read back."""
+    lib = _lib.load()
+    gt_off, gt_rows, gt_names = gt
+    det_off, det_rows, det_names = det
+    if len(gt_off) != len(det_off):
+        raise ValueError("ground truth and detections cover %d and %d frames"
+                         % (len(gt_off) - 1, len(det_off) - 1))
+    table = min_overlap_table(min_overlap)
+    dev = _device(device)
+    n_frames, n_gt, n_det = len(gt_off) - 1, len(gt_rows), len(det_rows)
+    ws_bytes = int(lib.pgnn_kitti_match_workspace_bytes(
+        n_frames, n_gt, n_det, _pair_count(gt_off, det_off)))
+    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+    d_gt = torch.from_numpy(gt_rows).to(dev)
+    d_gt_names = torch.from_numpy(gt_names).to(dev)
+    d_det = torch.from_numpy(det_rows).to(dev)
+    d_det_names = torch.from_numpy(det_names).to(dev)
+    out = {'gt_outcome': torch.empty(n_gt, dtype=torch.int32, device=dev),
+           'gt_partner': torch.empty(n_gt, dtype=torch.int32, device=dev),
+           'det_outcome': torch.empty(n_det, dtype=torch.int32, device=dev),
+           'det_partner': torch.empty(n_det, dtype=torch.int32, device=dev),
+           'det_overlap': torch.empty(n_det, dtype=torch.float64, device=dev),
+           'totals': torch.empty(_C['PGNN_KITTI_MATCH_TOTALS'],
+                                 dtype=torch.int64, device=dev)}
+
+    def dptr(t):
+        return _lib.ptr(t if t.numel() else None)
+
+    gt_off = np.ascontiguousarray(gt_off, np.int32)
+    det_off = np.ascontiguousarray(det_off, np.int32)
+    with torch.cuda.device(dev):
+        _lib.check(lib.pgnn_kitti_match(
+            _host_ptr(gt_off), _host_ptr(det_off), n_frames, dptr(d_gt),
+            dptr(d_gt_names), dptr(d_det), dptr(d_det_names),
+            _host_ptr(table), int(metric), int(cls), int(difficulty),
+            float(score_threshold), float(loc_floor), _lib.ptr(ws),
+            ws.numel(), dptr(out['gt_outcome']), dptr(out['gt_partner']),
+            dptr(out['det_outcome']), dptr(out['det_partner']),
+            dptr(out['det_overlap']), _lib.ptr(out['totals']),
+            _lib.stream_ptr()), "pgnn_kitti_match")
+        # the host offsets and the device inputs must outlive the launches
+        torch.cuda.current_stream().synchronize()
+    return out
+
+
+class KittiMatchResult(object):
+    """The outcome of every box of a frame set under one (metric, class,
+    difficulty) at one score threshold, on the host.  Packed over the frames,
+    frame f owning gt_offsets[f] .. gt_offsets[f + 1] (det_offsets likewise):
+    det_outcome, det_partner (int32), det_overlap (float64), gt_outcome,
+    gt_partner (int32); codes index DET_OUTCOMES / GT_OUTCOMES, partners are
+    indices within the frame or -1.  `totals`: boxes per code, keyed 'DET_TP',
+    'GT_FN_MISSED', ...  `tp`, `fp`, `fn`: what the protocol counts at this
+    threshold (fp: the four FP kinds, fn: the three FN kinds)."""
+
+    def __init__(self, arrays, gt_offsets, det_offsets, metric, cls,
+                 difficulty, score_threshold, loc_floor, min_overlap=None,
+                 frame_names=None):
+        for key in ('det_outcome', 'det_partner', 'det_overlap', 'gt_outcome',
+                    'gt_partner'):
+            setattr(self, key, arrays[key])
+        self.gt_offsets = np.asarray(gt_offsets, np.int32)
+        self.det_offsets = np.asarray(det_offsets, np.int32)
+        self.metric, self.cls, self.difficulty = metric, cls, difficulty
+        self.score_threshold = float(score_threshold)
+        self.loc_floor = float(loc_floor)
+        self.min_overlap = min_overlap_table(min_overlap)
+        self.frame_names = None if frame_names is None else list(frame_names)
+        counts = [int(x) for x in arrays['totals']]
+        self.totals = dict(
+            [('DET_' + n, counts[k]) for k, n in enumerate(DET_OUTCOMES)] +
+            [('GT_' + n, counts[len(DET_OUTCOMES) + k])
+             for k, n in enumerate(GT_OUTCOMES)])
+        self.tp = self.totals['GT_TP']
+        self.fp = sum(self.totals['DET_' + k] for k in DET_FP_KINDS)
+        self.fn = sum(self.totals['GT_' + k] for k in GT_FN_KINDS)
+
+    @property
+    def n_frames(self):
+        return len(self.gt_offsets) - 1
+
+    def frame(self, f):
+        """(det_outcome, det_partner, det_overlap, gt_outcome, gt_partner) of
+        frame f: what render_frame's `outcomes` takes."""
+        if not 0 <= f < self.n_frames:
+            raise IndexError("frame %d of %d" % (f, self.n_frames))
+        d = slice(self.det_offsets[f], self.det_offsets[f + 1])
+        g = slice(self.gt_offsets[f], self.gt_offsets[f + 1])
+        return (self.det_outcome[d], self.det_partner[d], self.det_overlap[d],
+                self.gt_outcome[g], self.gt_partner[g])
+
+    def format(self):
+        """A small table: the combination and threshold, tp / fp / fn, then
+        the false positives and the false negatives by kind, then the other
+        codes that occur."""
+        lines = ['%s %s %s at score >= %.6f: tp %d fp %d fn %d' % (
+            CLASSES[self.cls].lower(), REPORT_NAMES[self.metric],
+            DIFFICULTIES[self.difficulty], self.score_threshold, self.tp,
+            self.fp, self.fn)]
+
+        def share(key, of):
+            n = self.totals[key]
+            lines.append('  %-20s %7d %6.1f%%' % (
+                key.split('_', 1)[1].lower(), n, 100.0 * n / of if of else 0.0))
+        lines.append('false positives')
+        for kind in DET_FP_KINDS:
+            share('DET_' + kind, self.fp)
+        lines.append('false negatives')
+        for kind in GT_FN_KINDS:
+            share('GT_' + kind, self.fn)
+        rest = [k for k in self.totals if self.totals[k] and
+                k.split('_', 1)[1] not in DET_FP_KINDS + GT_FN_KINDS]
+        lines.append('other boxes')
+        for key in rest:
+            lines.append('  %-20s %7d' % (key.lower(), self.totals[key]))
+        return '\n'.join(lines)
+
+    def to_json(self):
+        return {'metric': METRICS[self.metric], 'class': CLASSES[self.cls],
+                'difficulty': DIFFICULTIES[self.difficulty],
+                'score_threshold': self.score_threshold,
+                'loc_floor': self.loc_floor,
+                'min_overlap': float(self.min_overlap[self.metric, self.cls]),
+                'tp': self.tp, 'fp': self.fp, 'fn': self.fn,
+                'totals': dict(self.totals)}
+
+
+def _combination(metric, cls, difficulty):
+    if isinstance(metric, str) and metric.lower() in REPORT_NAMES:
+        m = REPORT_NAMES.index(metric.lower())
+    else:
+        m = _index(metric, METRICS, 'metric')
+    return (m, _index(cls, CLASSES, 'class'),
+            _index(difficulty, DIFFICULTIES, 'difficulty'))
+
+
+def match(gt_labels, det_labels, metric='3d', cls='Car', difficulty='moderate',
+          score_threshold=0.0, min_overlap=None, loc_floor=0.1, device=None,
+          frame_names=None):
+    """The official matching of one (metric, class, difficulty) at one score
+    threshold over a frame set, box by box (pgnn_kitti_match; the outcome
+    codes and the error kinds are DESIGN.md §9.13).  gt_labels / det_labels as
+    `evaluate`'s; metric / cls / difficulty: names or 0..2; min_overlap as
+    `evaluate`'s; loc_floor: the overlap from which a miss counts as a
+    localisation error.  One read of each output.  Returns a
+    KittiMatchResult."""
+    if len(gt_labels) != len(det_labels):
+        raise ValueError("ground truth and detections cover %d and %d frames"
+                         % (len(gt_labels), len(det_labels)))
+    m, c, d = _combination(metric, cls, difficulty)
+    gt, det = pack_labels(gt_labels), pack_labels(det_labels)
+    out = run_match_packed(gt, det, m, c, d, score_threshold, min_overlap,
+                           loc_floor, device)
+    arrays = {key: t.cpu().numpy() for key, t in out.items()}
+    return KittiMatchResult(arrays, gt[0], det[0], m, c, d, score_threshold,
+                            loc_floor, min_overlap, frame_names)
+
+
+def match_dirs(label_dir, result_dir, frame_names=None, **kwargs):
+    """`match` of two directories of KITTI txt files, read as `evaluate_dirs`
+    reads them; the result carries the frame names."""
+    names, gt, det = read_dirs(label_dir, result_dir, frame_names)
+    return match(gt, det, frame_names=names, **kwargs)
+
+
+def best_f1_threshold(result, metric, cls, difficulty):
+    """The stored threshold of a KittiEvalResult's combination at which
+    2 tp / (2 tp + fp + fn) of its counters is largest; of equal values the
+    higher threshold.  The comparison is on integers (cross products), so no
+    rounding decides.  ValueError when the combination has no threshold.  On
+    the host."""
+    m, c, d = _combination(metric, cls, difficulty)
+    n = int(result.n_thresholds[m, c, d])
+    if n == 0:
+        raise ValueError("%s %s %s has no threshold: no ground truth was "
+                         "matched" % (METRICS[m], CLASSES[c], DIFFICULTIES[d]))
+    best, best_num, best_den = None, 0, 1
+    for t in range(n):
+        tp, fp, fn = (int(x) for x in result.counters[m, c, d, t])
+        num, den = 2 * tp, 2 * tp + fp + fn
+        thr = float(result.thresholds[m, c, d, t])
+        # num / den against best_num / best_den; 0 / 0 counts as 0
+        left, right = num * max(best_den, 1), best_num * max(den, 1)
+        if best is None or left > right or (left == right and thr > best):
+            best, best_num, best_den = thr, num, den
+    return best
+
+
 # ---- precision / recall curves: data files and plots -------------------------
 ORIENTATION = 'orientation'     # the fourth file and plot, with has_aos
 CURVE_COLORS = ((0, 160, 0), (0, 0, 255), (255, 0, 0))   # easy, moderate, hard
@@ -749,7 +970,48 @@ def parse_args(argv=None):
                     default='zlib',
                     help="with --plot: compress the plots on the host (zlib) "
                          "or on the GPU (device: faster, larger files)")
+    add_error_arguments(ap, "also print, for one combination at one score "
+                            "threshold, the false positives and false "
+                            "negatives by kind")
     return ap.parse_args(argv)
+
+
+def threshold_argument(value):
+    """'f1' or a float: the --at-threshold of the command lines."""
+    if str(value).lower() == 'f1':
+        return 'f1'
+    try:
+        return float(value)
+    except ValueError:
+        raise ValueError("a threshold is 'f1' or a number, not %r" % (value,))
+
+
+def add_error_arguments(ap, errors_help):
+    ap.add_argument('--errors', action='store_true', help=errors_help)
+    ap.add_argument('--error-metric', choices=METRICS, default='3d')
+    ap.add_argument('--error-class', choices=CLASSES, default='Car')
+    ap.add_argument('--error-difficulty', choices=DIFFICULTIES,
+                    default='moderate')
+    ap.add_argument('--at-threshold', metavar='f1|SCORE',
+                    type=threshold_argument, default='f1',
+                    help="with --errors: a score, or f1 (default): the "
+                         "stored threshold of the combination with the best "
+                         "F1")
+
+
+def resolve_threshold(score_threshold, result, metric, cls, difficulty):
+    """'f1' -> best_f1_threshold of `result` (a KittiEvalResult; 0.0 where the
+    combination has no threshold: every detection is kept); a number ->
+    itself."""
+    if isinstance(score_threshold, str):
+        if score_threshold.lower() != 'f1':
+            raise ValueError("score_threshold is a number or 'f1', not %r"
+                             % (score_threshold,))
+        try:
+            return best_f1_threshold(result, metric, cls, difficulty)
+        except ValueError:
+            return 0.0
+    return float(score_threshold)
 
 
 def main(argv=None):
@@ -766,8 +1028,20 @@ def main(argv=None):
     if args.plot:
         write_pr_data(result, args.plot)
         write_pr_plots(result, args.plot, png_encoder=args.png_encoder)
+    errors = None
+    if args.errors:
+        combo = (args.error_metric, args.error_class, args.error_difficulty)
+        errors = match_dirs(
+            args.label_dir, args.result_dir, names, metric=combo[0],
+            cls=combo[1], difficulty=combo[2], min_overlap=args.min_overlap,
+            score_threshold=resolve_threshold(args.at_threshold, result,
+                                              *combo))
+        print(errors.format())
     if args.json:
-        print(json.dumps(result.to_json()))
+        js = result.to_json()
+        if errors is not None:
+            js['errors'] = errors.to_json()
+        print(json.dumps(js))
     return 0
 
 

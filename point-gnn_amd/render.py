@@ -19,6 +19,15 @@ drawn: the interactive 3D window.
     python -m pointgnn_amd.render DATASET_DIR RESULT_DIR RENDER_DIR --view bev
         [--text]
 
+Every box in the colour of its outcome in the KITTI matching (kitti_eval.match,
+DESIGN.md section 9.13; tags and colours: OUTCOME_TAGS, OUTCOME_COLORS):
+
+    errors = kitti_eval.match(gt, det, '3d', 'Car', 'moderate', score_threshold=t)
+    render_frame(dataset, f, det[f], gt[f], outcomes=errors.frame(f), text=True)
+    render_results(dataset, result_dir, render_dir, errors={'cls': 'Car'})
+    python -m pointgnn_amd.render ... --errors [--at-threshold f1|<float>]
+        [--show-below]
+
 NumPy arrays or CUDA tensors go in, a uint8 [H, W, 3] CUDA tensor comes out.
 """
 import math
@@ -541,10 +550,13 @@ def graph_segments(coords, edges, level, dst_mask=None):
 
 # ---- a frame -------------------------------------------------------------------------
 def frame_layers(points, det_labels=None, gt_labels=None, stages=None,
-                 color_by='intensity', show_graph=False):
+                 color_by='intensity', show_graph=False, det_colors=None,
+                 gt_colors=None):
     """What render_frame draws, before any view: dict(points, point_colors,
     segments, segment_colors) of CUDA tensors (segments float64).  Stacking
-    order of the segments: graph edges, ground truth, detections."""
+    order of the segments: graph edges, ground truth, detections.  det_colors
+    / gt_colors: one RGB per label instead of DETECTION_COLOR / GT_COLORS
+    (every label given is then drawn, whatever its name)."""
     import torch
     det_labels, gt_labels = as_labels(det_labels), as_labels(gt_labels)
     xyz = points.xyz
@@ -596,13 +608,19 @@ def frame_layers(points, det_labels=None, gt_labels=None, stages=None,
         scols.append(vert_colors[e[:, 1].long()])            # run.py:347-348
     u8 = lambda rows: torch.from_numpy(np.asarray(rows, dtype=np.uint8).reshape(
         -1, 3)).to(dev)
-    if gt_labels:
+    if gt_labels and gt_colors is not None:
+        segs.append(torch.from_numpy(label_segments(gt_labels)).to(dev))
+        scols.append(u8(gt_colors).repeat_interleave(12, dim=0))
+    elif gt_labels:
         gt = [l for l in gt_labels if l['name'] in GT_COLORS]  # run.py:438-444
         if gt:
             segs.append(torch.from_numpy(label_segments(gt)).to(dev))
             scols.append(u8([GT_COLORS[l['name']] for l in gt]
                             ).repeat_interleave(12, dim=0))
-    if det_labels:
+    if det_labels and det_colors is not None:
+        segs.append(torch.from_numpy(label_segments(det_labels)).to(dev))
+        scols.append(u8(det_colors).repeat_interleave(12, dim=0))
+    elif det_labels:
         segs.append(torch.from_numpy(label_segments(det_labels)).to(dev))
         scols.append(u8([DETECTION_COLOR]).repeat(12 * len(det_labels), 1))
     return {
@@ -685,10 +703,135 @@ def frame_text(det_labels, gt_labels, view, camera):
             np.array(colors, dtype=np.uint8).reshape(-1, 3))
 
 
+# ---- outcomes of the KITTI matching on the boxes -------------
+# A box's tag by its outcome code (kitti_eval.DET_OUTCOMES / GT_OUTCOMES); a
+# box tagged None (code OTHER: another class's) is not drawn.  A detection
+# under the threshold and the ground truth it would have found share 'LOW'; the
+# ignored kinds share 'IGN'.
+OUTCOME_TAGS = {
+    'det': {'OTHER': None, 'BELOW': 'LOW', 'TP': 'TP',
+            'MATCHED_IGNORED': 'IGN', 'IGNORED_SMALL': 'IGN',
+            'DONTCARE': 'IGN', 'FP_DUPLICATE': 'DUP', 'FP_CONFUSION': 'CONF',
+            'FP_LOCALISATION': 'LOC', 'FP_BACKGROUND': 'BG'},
+    'gt': {'OTHER': None, 'IGNORED': 'IGN', 'IGNORED_MATCHED': 'IGN',
+           'TP': 'TP', 'MATCHED_SMALL': 'IGN', 'FN_LOW_SCORE': 'LOW',
+           'FN_LOCALISATION': 'LOC', 'FN_MISSED': 'MISS'}}
+# one RGB per tag, the same for a detection and a ground truth
+OUTCOME_COLORS = {'TP': (0, 220, 0), 'DUP': (255, 165, 0),
+                  'LOC': (255, 255, 0), 'CONF': (255, 0, 255),
+                  'BG': (255, 0, 0), 'LOW': (0, 200, 255),
+                  'MISS': (255, 105, 180), 'IGN': (128, 128, 128)}
+
+
+def outcome_tags(side, codes):
+    """'det' / 'gt' and outcome codes -> the tags, None for a box that is not
+    drawn."""
+    from . import kitti_eval
+    names = kitti_eval.DET_OUTCOMES if side == 'det' else \
+        kitti_eval.GT_OUTCOMES
+    return [OUTCOME_TAGS[side][names[int(c)]] for c in codes]
+
+
+def frame_outcomes(det_labels, gt_labels, outcomes, show_below=False,
+                   with_text=True):
+    """What render_frame(outcomes=...) draws of a frame: dict(det, gt: the
+    labels drawn, in their order; det_colors, gt_colors: uint8 [n, 3];
+    det_strings, gt_strings).  outcomes: KittiMatchResult.frame(f), for these
+    labels.  Not drawn: boxes of code OTHER and, without show_below,
+    detections under the threshold.  A string is the tag, then two decimals:
+    a detection's overlap with its partner, its score where it has none (BG,
+    LOW, an unmatched IGN); a ground truth's overlap with its partner where
+    that detection's partner is this ground truth (TP, the matched IGN, most
+    LOC), else the partner's score (LOW, the other LOC); MISS and an unmatched
+    IGN stand alone."""
+    det_labels, gt_labels = as_labels(det_labels), as_labels(gt_labels)
+    det_outcome, det_partner, det_overlap, gt_outcome, gt_partner = outcomes
+    if len(det_outcome) != len(det_labels) or len(gt_outcome) != len(gt_labels):
+        raise ValueError("outcomes are for %d detections and %d labels, the "
+                         "frame has %d and %d" % (
+                             len(det_outcome), len(gt_outcome),
+                             len(det_labels), len(gt_labels)))
+    out = {'det': [], 'gt': [], 'det_strings': [], 'gt_strings': []}
+    colors = {'det': [], 'gt': []}
+    for j, tag in enumerate(outcome_tags('det', det_outcome)):
+        if tag is None or (tag == 'LOW' and not show_below):
+            continue
+        value = float(det_overlap[j]) if det_partner[j] >= 0 else \
+            float(det_labels[j]['score'])
+        out['det'].append(det_labels[j])
+        colors['det'].append(OUTCOME_COLORS[tag])
+        out['det_strings'].append('%s %.2f' % (tag, value))
+    for i, tag in enumerate(outcome_tags('gt', gt_outcome)):
+        if tag is None:
+            continue
+        p = int(gt_partner[i])
+        if p < 0:
+            string = tag
+        elif det_partner[p] == i:
+            string = '%s %.2f' % (tag, float(det_overlap[p]))
+        else:
+            string = '%s %.2f' % (tag, float(det_labels[p]['score']))
+        out['gt'].append(gt_labels[i])
+        colors['gt'].append(OUTCOME_COLORS[tag])
+        out['gt_strings'].append(string)
+    for side in ('det', 'gt'):
+        out[side + '_colors'] = np.array(colors[side],
+                                         dtype=np.uint8).reshape(-1, 3)
+    return out
+
+
+def outcome_text(drawn, view, camera):
+    """(strings, anchors, colors) of frame_outcomes' result for draw_text
+    (anchor='bl'): ground truths first, each string in its box's colour at
+    frame_text's anchor (no lift)."""
+    strings, anchors, colors = [], [], []
+    for side in ('gt', 'det'):
+        for label, string, color in zip(drawn[side], drawn[side + '_strings'],
+                                        drawn[side + '_colors']):
+            org = (int(label['xmin']), int(label['ymin'])) if camera else \
+                center_pixel(view, label)
+            if org is None:
+                continue
+            strings.append(string)
+            anchors.append(org)
+            colors.append(color)
+    return (strings, np.array(anchors, dtype=np.int64).reshape(-1, 2),
+            np.array(colors, dtype=np.uint8).reshape(-1, 3))
+
+
+def _render_frame_outcomes(dataset, frame_idx, det_labels, gt_labels, view,
+                           stages, color_by, show_graph, background, text,
+                           text_plate, outcomes, show_below):
+    calib = stages['calib'] if stages is not None else None
+    v = frame_view(dataset, frame_idx, view, calib)
+    points = stages['points'] if stages is not None else \
+        dataset.get_cam_points_in_image_with_rgb(frame_idx, calib=calib)
+    drawn = frame_outcomes(det_labels, gt_labels, outcomes, show_below)
+    layers = frame_layers(points, drawn['det'], drawn['gt'], stages, color_by,
+                          show_graph, det_colors=drawn['det_colors'],
+                          gt_colors=drawn['gt_colors'])
+    image = render(v, points=layers['points'],
+                   point_colors=layers['point_colors'],
+                   segments=layers['segments'],
+                   segment_colors=layers['segment_colors'],
+                   background=background)
+    if view == 'camera' and drawn['det']:
+        image = render(pixel_view(v.width, v.height),
+                       segments=rect_segments(drawn['det']),
+                       segment_colors=np.repeat(drawn['det_colors'], 4, axis=0),
+                       thickness=2, background=image)
+    if text:
+        strings, anchors, colors = outcome_text(drawn, v, view == 'camera')
+        if strings:
+            draw_text(image, strings, anchors, colors=colors, scale=1,
+                      plate=text_plate, anchor='bl')
+    return image
+
+
 def render_frame(dataset, frame_idx, det_labels=None, gt_labels=None,
                  view='bev', stages=None, color_by='intensity',
                  show_graph=False, background=None, text=False,
-                 text_plate=None):
+                 text_plate=None, outcomes=None, show_below=False):
     """One frame of `dataset`: the cloud cropped to the camera image (coloured
     by 'intensity', 'height', or by 'class' on the last level's vertices),
     ground truth wireframes in GT_COLORS (labels filtered like run.py:438-444),
@@ -698,7 +841,16 @@ def render_frame(dataset, frame_idx, det_labels=None, gt_labels=None,
     and show_graph (the last level's edges into the vertices of the kept
     boxes, run.py:339-350).  text: also the strings of frame_text, drawn last
     with draw_text (scale 1, anchor='bl'; text_plate: a plate colour under
-    them); without it no text pass runs.  -> uint8 [H, W, 3] CUDA tensor."""
+    them); without it no text pass runs.  outcomes: the frame's five arrays
+    of a kitti_eval.match (KittiMatchResult.frame): every box then takes its
+    outcome's colour (OUTCOME_TAGS, OUTCOME_COLORS) -- wireframes, rectangles
+    and strings -- boxes of another class are not drawn, detections under the
+    threshold only with show_below, and with `text` the strings are
+    frame_outcomes' ('LOC 0.41').  -> uint8 [H, W, 3] CUDA tensor."""
+    if outcomes is not None:
+        return _render_frame_outcomes(
+            dataset, frame_idx, det_labels, gt_labels, view, stages, color_by,
+            show_graph, background, text, text_plate, outcomes, show_below)
     calib = stages['calib'] if stages is not None else None
     v = frame_view(dataset, frame_idx, view, calib)
     points = stages['points'] if stages is not None else \
@@ -801,7 +953,8 @@ def image_background(dataset):
 def render_results(dataset, result_dir, render_dir, views=('bev',),
                    frame_indices=None, fmt='png', with_gt=True,
                    background_reader=None, time_dict=None, text=False,
-                   text_plate=None, png_encoder='zlib'):
+                   text_plate=None, png_encoder='zlib', errors=None,
+                   show_below=False):
     """Draws every frame of a result directory (<result_dir>/<name>.txt as
     run.run_dataset writes them under <output_dir>/data, or any other KITTI
     result directory) into <render_dir>/<view>/<name>.<fmt>, fmt 'png' or
@@ -812,7 +965,13 @@ def render_results(dataset, result_dir, render_dir, views=('bev',),
     with 'device' the image stays on the device and only its compressed bytes
     are read (time_dict's 'encode png' then holds that encode, 'render' ends
     at a synchronise).  Sequential: one host read per image (two short ones
-    with 'device').  Returns the paths written."""
+    with 'device').  errors: a dict of kitti_eval.match's keyword arguments
+    (metric, cls, difficulty, score_threshold, min_overlap, loc_floor; {} for
+    its defaults but score_threshold, which defaults to 'f1': the
+    combination's best_f1_threshold, from one evaluation of the frame set).
+    The frame set is then matched once and every frame is drawn with its
+    outcomes (render_frame's `outcomes`, `show_below`); needs the labels.
+    Returns the paths written."""
     from . import kitti_eval
     import time
     import torch
@@ -828,13 +987,19 @@ def render_results(dataset, result_dir, render_dir, views=('bev',),
         frame_indices = range(dataset.num_files)
     td = time_dict if time_dict is not None else {}
     paths = []
-    for frame_idx in frame_indices:
+    matched = None
+    if errors is not None:
+        frame_indices = list(frame_indices)
+        matched = _match_frames(dataset, result_dir, frame_indices, errors)
+    for k, frame_idx in enumerate(frame_indices):
         name = dataset.get_filename(frame_idx)
         det = kitti_eval.read_result_file(
             os.path.join(result_dir, name + '.txt'))
         gt = None
-        if with_gt and dataset._label_dir:
+        if (with_gt or matched is not None) and dataset._label_dir:
             gt = dataset.get_label(frame_idx)
+        more = {} if matched is None else {'outcomes': matched.frame(k),
+                                           'show_below': show_below}
         calib = dataset.get_calib(frame_idx)
         points = dataset.get_cam_points_in_image_with_rgb(frame_idx,
                                                           calib=calib)
@@ -846,7 +1011,7 @@ def render_results(dataset, result_dir, render_dir, views=('bev',),
                 background = background_reader(frame_idx)
             image = render_frame(dataset, frame_idx, det, gt, view=view,
                                  stages=stages, background=background,
-                                 text=text, text_plate=text_plate)
+                                 text=text, text_plate=text_plate, **more)
             if on_device:
                 torch.cuda.synchronize(image.device)   # 'render' ends here
                 host = image
@@ -869,8 +1034,30 @@ def render_results(dataset, result_dir, render_dir, views=('bev',),
     return paths
 
 
+def _match_frames(dataset, result_dir, frame_indices, errors):
+    """kitti_eval.match of the frames render_results draws, in their order."""
+    from . import kitti_eval
+    if not dataset._label_dir:
+        raise ValueError("errors needs the labels: the dataset has no label "
+                         "directory")
+    kwargs = dict(errors)
+    gt = [dataset.get_label(i) for i in frame_indices]
+    det = [kitti_eval.read_result_file(os.path.join(
+        result_dir, dataset.get_filename(i) + '.txt')) for i in frame_indices]
+    combo = [kwargs.setdefault(key, value) for key, value in
+             (('metric', '3d'), ('cls', 'Car'), ('difficulty', 'moderate'))]
+    threshold = kwargs.pop('score_threshold', 'f1')
+    if isinstance(threshold, str):
+        evaluated = kitti_eval.evaluate(
+            gt, det, min_overlap=kwargs.get('min_overlap'),
+            device=kwargs.get('device'))
+        threshold = kitti_eval.resolve_threshold(threshold, evaluated, *combo)
+    return kitti_eval.match(gt, det, score_threshold=threshold, **kwargs)
+
+
 def build_parser():
     import argparse
+    from . import kitti_eval
     ap = argparse.ArgumentParser(
         prog="python -m pointgnn_amd.render",
         description="Draw every frame of a KITTI result directory: the "
@@ -900,6 +1087,13 @@ def build_parser():
     ap.add_argument('--text', action='store_true',
                     help="write every detection's class letter and score "
                          "('P | 0.873') and every drawn label's name")
+    kitti_eval.add_error_arguments(
+        ap, "colour every box by its outcome in the KITTI matching of one "
+            "combination at one score threshold (with --text: tag and "
+            "overlap, 'LOC 0.41'); needs the labels")
+    ap.add_argument('--show-below', action='store_true',
+                    help="with --errors: also draw the detections under the "
+                         "threshold")
     return ap
 
 
@@ -919,7 +1113,13 @@ def main(argv=None):
                            fmt='ppm' if args.ppm else 'png',
                            background_reader=image_background(dataset)
                            if args.image_background else None,
-                           text=args.text, png_encoder=args.png_encoder)
+                           text=args.text, png_encoder=args.png_encoder,
+                           errors=dict(metric=args.error_metric,
+                                       cls=args.error_class,
+                                       difficulty=args.error_difficulty,
+                                       score_threshold=args.at_threshold)
+                           if args.errors else None,
+                           show_below=args.show_below)
     print("wrote %d images to %s" % (len(paths), args.render_dir))
     return 0
 
