@@ -747,6 +747,19 @@ int pgnn_edge_mlp_scatter_max_f16x2_fwd(
  * where pgnn_edge_ws_applies says 0 for the expected edge count
  * (n_edges->hint, else edges_cap).
  *
+ * PGNN_EDGE_K300_ORDER in `edges_sorted` (width = 300, a layer of 300 input
+ * features): columns 288..303 of P and Q and rows 288..303 of the layer's image
+ * come in the order of pgnn_k300_source -- position p holds feature
+ * pgnn_k300_source(p); 291, 295, 299 and 303 are the zero padding -- as
+ * pgnn_pack_fc_k300 writes the image; write P and Q from weight images whose
+ * output columns are permuted the same way.  The padding is then the whole of
+ * the last K group's fourth MFMA step, which the kernel does not issue: 7 of
+ * every 532 MFMAs.  The real products keep their order in the fmaf chain and a
+ * dropped one is fma(0, 0, acc), so `out` is what the entry writes without the
+ * flag for the operands in natural order, bit for bit.  With the flag and any
+ * other width or layer the entry returns PGNN_E_UNSUPPORTED, having done
+ * nothing.  pgnn_pack_fc_k300 returns it for k_in != 300.
+ *
  * pgnn_edge_ws_applies: *applies = 1 when a launch of the fp32 edge stage with
  * these layers, about `edges_expected` edges, on `stream` (its CU mask counts)
  * takes the weights-stationary kernel -- one 300x300 or 256x256 layer, ~65k
@@ -754,6 +767,10 @@ int pgnn_edge_mlp_scatter_max_f16x2_fwd(
 int pgnn_edge_ws_applies(const pgnn_fc_layer *layers_host, int32_t n_layers,
                          int32_t width, int64_t edges_expected, void *stream,
                          int32_t *applies);
+#define PGNN_EDGE_K300_ORDER 4
+int32_t pgnn_k300_source(int32_t position);
+int pgnn_pack_fc_k300(const float *w_host, const float *b_host, int32_t k_in,
+                      int32_t n_out, float *packed_host);
 int pgnn_edge_mlp_scatter_max_scaled_fwd(
     const float *P, const float *Q, int64_t ld_pq, int32_t width,
     const int32_t *edges, int64_t edges_cap, int32_t vertices_cap,

@@ -58,6 +58,8 @@ E_UNSUPPORTED = _C["PGNN_E_UNSUPPORTED"]
 AGG_MAX, AGG_SUM, AGG_MEAN = (_C["PGNN_AGG_MAX"], _C["PGNN_AGG_SUM"],
                               _C["PGNN_AGG_MEAN"])
 SCHED_WS_INTS = _C["PGNN_SCHED_WS_INTS"]
+# `edges_sorted` of pgnn_edge_mlp_scatter_max_scaled_fwd
+EDGE_K300_ORDER = _C["PGNN_EDGE_K300_ORDER"]
 
 
 class PointGnnHipError(RuntimeError):

@@ -464,23 +464,55 @@ extern "C" int pgnn_pack_fc_f16x2_acc(const float *w, const float *b,
   PGNN_GUARD_END
 }
 
-extern "C" int pgnn_pack_fc(const float *w, const float *b, int32_t k_in,
-                            int32_t n_out, float *packed) {
-  PGNN_GUARD_BEGIN
-  PGNN_REQUIRE(w && packed && k_in > 0 && n_out > 0, PGNN_E_INVALID,
-               "pack_fc: bad argument");
+namespace {
+// pgnn_pack_fc / pgnn_pack_fc_k300: slot (q, lane (g, n), s) of the image holds
+// row src(16q + 4g + s) of the weights
+template <class SRC>
+void pack_fc_rows(const float *w, const float *b, int32_t k_in, int32_t n_out,
+                  float *packed, SRC src) {
   const int kq = (k_in + 15) / 16, nt = (n_out + 15) / 16;
   for (int q = 0; q < kq; ++q)
     for (int t = 0; t < nt; ++t)
       for (int lane = 0; lane < 64; ++lane)
         for (int s = 0; s < 4; ++s) {
-          const int k = 16 * q + 4 * (lane >> 4) + s;
+          const int k = src(16 * q + 4 * (lane >> 4) + s);
           const int n = 16 * t + (lane & 15);
           packed[(((size_t)q * nt + t) * 64 + lane) * 4 + s] =
               (k < k_in && n < n_out) ? w[(size_t)k * n_out + n] : 0.0f;
         }
   float *bias = packed + (size_t)kq * nt * 256;
   for (int n = 0; n < nt * 16; ++n) bias[n] = (b && n < n_out) ? b[n] : 0.0f;
+}
+}  // namespace
+
+extern "C" int pgnn_pack_fc(const float *w, const float *b, int32_t k_in,
+                            int32_t n_out, float *packed) {
+  PGNN_GUARD_BEGIN
+  PGNN_REQUIRE(w && packed && k_in > 0 && n_out > 0, PGNN_E_INVALID,
+               "pack_fc: bad argument");
+  pack_fc_rows(w, b, k_in, n_out, packed, [](int k) { return k; });
+  return 0;
+  PGNN_GUARD_END
+}
+
+// Position 288 + 4g + s (lane group g, MFMA step s of the last K group) holds
+// element j = 4s + g of the sequence in which the steps consume the twelve real
+// features of the group in the natural layout -- step by step, lane groups 0..2:
+// 288, 292, 296, 289, ... -- and step 3 the padding.
+extern "C" int32_t pgnn_k300_source(int32_t position) {
+  if (position < 288 || position >= 304) return position;
+  const int g = (position - 288) >> 2, s = (position - 288) & 3, j = 4 * s + g;
+  return j < 12 ? 288 + 4 * (j % 3) + j / 3 : 300 + g;
+}
+
+extern "C" int pgnn_pack_fc_k300(const float *w, const float *b, int32_t k_in,
+                                 int32_t n_out, float *packed) {
+  PGNN_GUARD_BEGIN
+  PGNN_REQUIRE(w && packed && n_out > 0, PGNN_E_INVALID,
+               "pack_fc_k300: bad argument");
+  PGNN_REQUIRE(k_in == 300, PGNN_E_UNSUPPORTED,
+               "pack_fc_k300: the order exists for 300 input features only");
+  pack_fc_rows(w, b, k_in, n_out, packed, pgnn_k300_source);
   return 0;
   PGNN_GUARD_END
 }

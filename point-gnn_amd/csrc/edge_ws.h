@@ -339,8 +339,20 @@ namespace pgnn {
 // SCALED (WsMax, no EMIT, no ROWS): P, Q hold 2^-k x the operands, the gather's
 // subtraction is its ReLU (pk_sub_clamp) and ws_flush undoes the scale; the
 // MFMA loop, the fragment schedule and the epilogue are the plain body's.
+//
+// K300 (SCALED, KQ = 19): the operands' columns 288 .. 303 and the rows
+// 288 .. 303 of the weight image come in the order of pgnn_k300_source, in
+// which the four padding features of K = 300 are element 3 of every lane group
+// of the last K group -- the whole of its MFMA step 3, which is not issued.
+// The other steps run the real products in the order they had (an MFMA is a
+// k-ordered fmaf chain: instruction by instruction, lane groups ascending) and
+// a dropped product is fma(0, 0, acc) = acc: the accumulator starts at +0 and a
+// round-to-nearest sum is never -0.  (The first K group's fragments are still
+// requested behind the gather: requested in front of its subtractions they
+// cost 253 VGPRs, one behind each of the first NTG subtractions 237, against
+// 227 here -- profiles/edge_k300.md.)
 template <int KQ, int NTG, bool EMIT, bool ROWS = false, class POL = WsMax,
-          bool SCALED = false>
+          bool SCALED = false, bool K300 = false>
 __device__ __forceinline__ void edge_ws_body(const EdgeWsArgs &a,
                                              const v4f *__restrict__ wl, int t0,
                                              const float *bias_lds,
@@ -350,6 +362,8 @@ __device__ __forceinline__ void edge_ws_body(const EdgeWsArgs &a,
                                              const int64_t E) {
   static_assert(!SCALED || (!EMIT && !ROWS && !POL::kSum),
                 "the scaled form exists for the plain max kernel only");
+  static_assert(!K300 || (SCALED && KQ == 19),
+                "the K = 300 form exists for the scaled kernel of 19 K groups");
   if (tile_first >= tile_last) return;
   const int n = lane & 15;
   const int64_t e_first = tile_first * 16;
@@ -524,8 +538,9 @@ __device__ __forceinline__ void edge_ws_body(const EdgeWsArgs &a,
                                      [(((q + 1) * NTG + t) & 63) * 64];
 #endif
         }
+        // (K300: step 3 of the last group multiplies the padding alone)
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
+        for (int s = 0; s < (K300 && q == KQ - 1 ? 3 : 4); ++s)
 #pragma unroll
           for (int t = 0; t < NTG; ++t)
             acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(
@@ -541,7 +556,8 @@ __device__ __forceinline__ void edge_ws_body(const EdgeWsArgs &a,
         }
         // (three MFMAs per request: the last fragment is then requested a
         // quarter of a group -- ~200 cycles -- before the group boundary's wait)
-        __builtin_amdgcn_sched_group_barrier(0x8 /*MFMA*/, NTG, 0);
+        if (!(K300 && q == KQ - 1))
+          __builtin_amdgcn_sched_group_barrier(0x8 /*MFMA*/, NTG, 0);
 #else
         if (q + 1 < KQ)
           __builtin_amdgcn_sched_group_barrier(0x100 /*DS read*/, NTG, 0);
@@ -782,10 +798,10 @@ __device__ __forceinline__ void ws_scaled_guard(const EdgeWsArgs &a) {
   if (bad || !(m <= 0.5f)) atomicOr(a.status, 1);
 }
 
-// SCALED is the LAST parameter: the kernel's name still begins
+// SCALED and K300 are the LAST parameters: the kernel's name still begins
 // `edge_ws_kernel<KQ, NTMAX, ...`, which is what the profile tools look for.
 template <int KQ, int NTMAX, bool EMIT = false, bool ROWS = false,
-          class POL = WsMax, bool SCALED = false>
+          class POL = WsMax, bool SCALED = false, bool K300 = false>
 __global__ __launch_bounds__(64 * kWsWaves) void edge_ws_kernel(EdgeWsArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   v4f *wl = reinterpret_cast<v4f *>(smem);
@@ -858,11 +874,11 @@ __global__ __launch_bounds__(64 * kWsWaves) void edge_ws_kernel(EdgeWsArgs a) {
   int32_t *counter = a.sched ? a.sched + 2 + slice * kWsMaxGroups + grp : nullptr;
   for (;;) {
     if (ntg == NTMAX)
-      edge_ws_body<KQ, NTMAX, EMIT, ROWS, POL, SCALED>(
+      edge_ws_body<KQ, NTMAX, EMIT, ROWS, POL, SCALED, K300>(
           a, wl, t0, bias_lds, tile_first, tile_last, lane, tsw, stamped,
           n_edges);
     else
-      edge_ws_body<KQ, NTMAX - 1, EMIT, ROWS, POL, SCALED>(
+      edge_ws_body<KQ, NTMAX - 1, EMIT, ROWS, POL, SCALED, K300>(
           a, wl, t0, bias_lds, tile_first, tile_last, lane, tsw, stamped,
           n_edges);
     if (pool == 0) break;

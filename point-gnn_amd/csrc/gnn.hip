@@ -1440,9 +1440,12 @@ extern "C" int pgnn_edge_mlp_scatter_max_scaled_fwd(
   PGNN_REQUIRE(ld_out >= 16 * p.chain.l[n_layers - 1].nt, PGNN_E_INVALID,
                "edge_mlp_scaled: ld_out < padded output width");
   const int cus = ws_cus(stream);
-  // the weights-stationary partition's own answer (pgnn_edge_ws_applies)
+  // the weights-stationary partition's own answer (pgnn_edge_ws_applies), and
+  // the K = 300 order's where the caller's operands come in it
+  const bool k300 = (edges_sorted & PGNN_EDGE_K300_ORDER) != 0;
   if (edges_cap == 0 || vertices_cap == 0 ||
-      !edge_ws_applies(p, expected(de, edges_cap), cus))
+      !edge_ws_applies(p, expected(de, edges_cap), cus) ||
+      (k300 && !edge_k300_applies(p, layers, width)))
     return PGNN_E_UNSUPPORTED;  // (no message: an expected answer)
   PGNN_REQUIRE(out && P && Q && edges, PGNN_E_INVALID,
                "edge_mlp_scaled: null pointer");
@@ -1454,6 +1457,10 @@ extern "C" int pgnn_edge_mlp_scatter_max_scaled_fwd(
   }
   const EdgeArgs ea = {P, Q, ld_pq, edges};
   const SegArgs sa = {out, ld_out, vertices_cap, edges_sorted & 1};
+  if (k300)
+    return launch_edge_ws_scaled<19, 7, true>(p.chain.l[0], ea, edges_cap, sa,
+                                              cus, sched_ws, stream, de.dev,
+                                              dk.dev, scale_exp, status);
   if (p.chain.l[0].nt == 19)
     return launch_edge_ws_scaled<19, 7>(p.chain.l[0], ea, edges_cap, sa, cus,
                                         sched_ws, stream, de.dev, dk.dev,

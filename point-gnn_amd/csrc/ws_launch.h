@@ -86,13 +86,14 @@ int plan_edge_ws(EdgeWsArgs &a, const LayerDev &L, const EdgeArgs &ea,
   return 0;
 }
 
-template <int KQ, int NTMAX, bool ROWS, class POL = WsMax, bool SCALED = false>
+template <int KQ, int NTMAX, bool ROWS, class POL = WsMax, bool SCALED = false,
+          bool K300 = false>
 int run_edge_ws(const EdgeWsArgs &a, int cus, hipStream_t stream) {
   static_assert(!POL::kSum || !ROWS, "the sum kernels read no ready rows");
   static_assert(!SCALED || (!POL::kSum && !ROWS), "scaled: the plain max kernel only");
   PGNN_HIP((hipError_t)arm_sched(a.sched, stream));
   const size_t lds = (size_t)KQ * NTMAX * 1024 + 16 * NTMAX * sizeof(float);
-  auto kern = edge_ws_kernel<KQ, NTMAX, false, ROWS, POL, SCALED>;
+  auto kern = edge_ws_kernel<KQ, NTMAX, false, ROWS, POL, SCALED, K300>;
   if constexpr (!ROWS && !POL::kSum && !SCALED) {  // training forward: the rows are written as well
     if (a.rows_out) kern = edge_ws_kernel<KQ, NTMAX, true>;
   }
@@ -114,8 +115,9 @@ int launch_edge_ws(const LayerDev &L, const EdgeArgs &ea, int64_t n_edges,
 
 // The SCALED form of the same launch (edge_ws.h, pk_sub_clamp): ea.P, ea.Q hold
 // 2^-scale_exp x the operands; status / nv_dev: the guard's flag and the
-// capacity form's vertex count (both nullable).
-template <int KQ, int NTMAX>
+// capacity form's vertex count (both nullable).  K300: the operands' and the
+// image's last K group in the order of pgnn_k300_source (edge_ws.h).
+template <int KQ, int NTMAX, bool K300 = false>
 int launch_edge_ws_scaled(const LayerDev &L, const EdgeArgs &ea, int64_t n_edges,
                           const SegArgs &sa, int cus, int32_t *sched,
                           hipStream_t stream, const int32_t *n_dev,
@@ -127,7 +129,7 @@ int launch_edge_ws_scaled(const LayerDev &L, const EdgeArgs &ea, int64_t n_edges
   a.nv_dev = nv_dev;
   a.unscale = (float)((int64_t)1 << scale_exp);
   a.status = status;
-  return run_edge_ws<KQ, NTMAX, false, WsMax, true>(a, cus, stream);
+  return run_edge_ws<KQ, NTMAX, false, WsMax, true, K300>(a, cus, stream);
 }
 
 // the shapes edge_ws.h is instantiated for: one square layer of 19 (C = 300)
@@ -151,6 +153,15 @@ bool edge_ws_applies(const Plan &p, int64_t n_edges, int cus) {
   // below ~2 tiles per wave the fixed cost (133 KiB of weights per workgroup
   // into LDS) is not amortised
   return n_edges >= (int64_t)16 * 2 * kWsWaves * cus;
+}
+
+// ... and the K = 300 order of the scaled kernel's last K group (edge_ws.h,
+// PGNN_EDGE_K300_ORDER): exactly 300 features in 19 K groups.  C = 256 has no
+// padding and no such order.
+inline bool edge_k300_applies(const Plan &p, const pgnn_fc_layer *layers,
+                              int width) {
+  return p.chain.n == 1 && p.chain.l[0].kq == 19 && p.chain.l[0].nt == 19 &&
+         layers[0].k_in == 300 && width == 300;
 }
 
 // Weights-stationary pooling kernel (pool_ws.h): car's 4-32-64-128-300 chain.

@@ -58,6 +58,8 @@ class ParamStore(object):
         # EDGE_SCALED below: a model turns it on for its store (models.py);
         # `inference` is what predict() was last called for
         self.edge_scaled = False
+        # EDGE_K300 below (only where the scaled stage runs)
+        self.edge_k300 = EDGE_K300
         self.inference = True
 
     @property
@@ -233,16 +235,18 @@ class ParamStore(object):
     def mlp(self, scope, n_layers):
         return [self.fc(n) for n in mlp_names(scope, n_layers)]
 
-    def pack(self, w, b):
+    def pack(self, w, b, k300=False):
         """[k_in, n_out] weights + bias -> device tensor in MFMA fragment order
-        (pgnn_pack_fc)."""
+        (pgnn_pack_fc; k300: pgnn_pack_fc_k300, rows 288..303 in EDGE_K300's
+        order)."""
         lib = _lib.load()
         w = np.ascontiguousarray(w, dtype=np.float32)
         b = np.ascontiguousarray(b, dtype=np.float32)
         k_in, n_out = w.shape
         host = np.empty(lib.pgnn_packed_fc_floats(k_in, n_out), np.float32)
-        _lib.check(lib.pgnn_pack_fc(w.ctypes.data, b.ctypes.data, k_in, n_out,
-                                    host.ctypes.data), "pgnn_pack_fc")
+        name = "pgnn_pack_fc_k300" if k300 else "pgnn_pack_fc"
+        _lib.check(getattr(lib, name)(w.ctypes.data, b.ctypes.data, k_in,
+                                      n_out, host.ctypes.data), name)
         return torch.from_numpy(host).to(self._dev())
 
     def cached(self, key, builder):
@@ -258,13 +262,14 @@ class Chain(object):
     """A packed MLP chain: keeps the device buffers alive next to the ctypes
     array of `pgnn_fc_layer` descriptors that points at them."""
 
-    def __init__(self, store, layers):
-        """layers: [(W [k,n], b [n], relu_from)]"""
+    def __init__(self, store, layers, k300=False):
+        """layers: [(W [k,n], b [n], relu_from)]; k300: the images' rows
+        288..303 in EDGE_K300's order"""
         self.buffers = []
         self.array = (_lib.FcLayer * len(layers))()
         self.n = len(layers)
         for i, (w, b, relu_from) in enumerate(layers):
-            buf = store.pack(w, b)
+            buf = store.pack(w, b, k300)
             self.buffers.append(buf)
             self.array[i].packed = buf.data_ptr()
             self.array[i].k_in = int(w.shape[0])
@@ -875,6 +880,37 @@ EDGE_ARITHS = ('f32', 'bf16x3', 'f16x2')
 EDGE_SCALE_HEADROOM = 0.125
 EDGE_SCALE_ROWS, EDGE_SCALE_SLOTS = 64, 16    # ParamStore.edge_scale_begin_pass
 
+# The scaled stage of a 300-wide layer without the MFMA step of K = 300's
+# padding (csrc/edge_ws.h, K300; PGNN_EDGE_K300_ORDER), `model.edge_k300`: the
+# hidden features 288..303 -- the last K group -- are kept in the order of
+# pgnn_k300_source, in which the four padding features are the group's whole
+# fourth MFMA step.  Only data moves: the scaled images of w1, b1 and wx get
+# their output columns permuted, the second layer's image its rows
+# (pgnn_pack_fc_k300); the real products keep their place in every fmaf chain,
+# so the results stay what they were bit for bit.  Nothing but the scaled kernel
+# reads operands in this order: the plain rerun after a guard trip, the
+# LDS-tile kernel, EDGE_INPUT_TAP, the 16-bit arithmetics, sum / mean and
+# training are on the natural order, as they are off the scaled path.
+EDGE_K300 = True
+
+
+def edge_k300_order(n=304):
+    """src [n]: column p of the permuted operands is feature src[p] (300..303:
+    the zero padding)."""
+    lib = _lib.load()
+    return np.array([lib.pgnn_k300_source(p) for p in range(n)], np.int64)
+
+
+def edge_k300_columns(a, width=304):
+    """[..., 300] -> [..., width] float32 with the columns in
+    edge_k300_order()."""
+    a = np.asarray(a, np.float32)
+    src = edge_k300_order(width)
+    out = np.zeros(a.shape[:-1] + (width,), np.float32)
+    real = src < a.shape[-1]
+    out[..., real] = a[..., src[real]]
+    return out
+
 
 def edge_scale_exp_for(max_abs):
     """Smallest k >= 0 with max_abs * 2^-k <= EDGE_SCALE_HEADROOM (24 at the
@@ -972,20 +1008,30 @@ class GraphNetAutoCenter(object):
             if applies.value:
                 scale_k = store.edge_scale_exp(edge_scope)
                 calibrate = scale_k is None and cnt_k is None
+        # ... and EDGE_K300's order of the last K group, for this kernel alone
+        k300 = scale_k is not None and store.edge_k300 and \
+            EDGE_INPUT_TAP is None and rest.k_in == 300
+        rest_k = rest
         if scale_k is not None:
             def build_scaled():
-                w1, b1 = store.mlp(edge_scope, len(edge_widths))[0]
+                fcs = store.mlp(edge_scope, len(edge_widths))
+                w1, b1 = fcs[0]
                 s = np.float32(2.0 ** -scale_k)
+                if k300:
+                    w1, b1 = edge_k300_columns(w1), edge_k300_columns(b1)
                 wx = np.zeros((3, padded_width(w1.shape[1])), np.float32)
                 wx[:, :w1.shape[1]] = w1[c:c + 3] * s
                 made = (Chain(store, [(w1 * s, b1 * s, w1.shape[1])]),
-                        torch.from_numpy(wx).to(store._dev()))
+                        torch.from_numpy(wx).to(store._dev()),
+                        Chain(store, [fcs[1] + (0,)], k300=True)
+                        if k300 else None)
                 # (other streams will read the images without an event)
                 torch.cuda.current_stream().synchronize()
                 return made
-            p_chain, wx_dev = store.cached(
-                ('edge_scaled', edge_scope, tuple(edge_widths), scale_k),
+            p_chain, wx_dev, rest_k = store.cached(
+                ('edge_scaled', edge_scope, tuple(edge_widths), scale_k, k300),
                 build_scaled)
+            rest_k = rest_k or rest
 
         # per vertex, one launch (gnn.py:341-356): [optional] coordinate offset
         # delta = MLP(h) (auto-registration), Q = (x + delta) @ W1[C:],
@@ -1060,8 +1106,11 @@ class GraphNetAutoCenter(object):
         elif scale_k is not None:
             # (p, q are scaled: the plain entry would be wrong from here on,
             # and the query above was this entry's own decision)
+            flags = edge_args[9] | (_lib.EDGE_K300_ORDER if k300 else 0)
             _lib.check(lib.pgnn_edge_mlp_scatter_max_scaled_fwd(
-                *edge_args, scale_k, store.edge_scale_status(edge_scope),
+                *(edge_args[:7] + (rest_k.array, rest_k.n, flags) +
+                  edge_args[10:]),
+                scale_k, store.edge_scale_status(edge_scope),
                 cnt_e.arg() if cnt_e is not None else None,
                 cnt_k.arg() if cnt_k is not None else None, st),
                 "pgnn_edge_mlp_scatter_max_scaled_fwd")

@@ -178,6 +178,19 @@ class MultiLayerFastLocalGraphModelV2(object):
         if self._store is not None:
             self._store.edge_scaled = self._edge_scaled
 
+    @property
+    def edge_k300(self):
+        """The scaled edge stage of a 300-wide layer without the MFMA step of
+        K = 300's padding (gnn.EDGE_K300 and the comment above it): same
+        results bit for bit.  Not part of the reference's surface."""
+        return getattr(self, '_edge_k300', gnn.EDGE_K300)
+
+    @edge_k300.setter
+    def edge_k300(self, value):
+        self._edge_k300 = bool(value)
+        if self._store is not None:
+            self._store.edge_k300 = self._edge_k300
+
     def edge_scale_begin_pass(self):
         """Takes a row of guard flags for the forward pass about to be
         enqueued (gnn.ParamStore.edge_scale_begin_pass) and returns it: ask
@@ -221,6 +234,7 @@ class MultiLayerFastLocalGraphModelV2(object):
         self._store = gnn.ParamStore(params, device)
         self._store.edge_arith = self._edge_arith
         self._store.edge_scaled = self.edge_scaled
+        self._store.edge_k300 = self.edge_k300
         return self
 
     def init_weights(self, config, seed=0, **kw):
