@@ -106,7 +106,7 @@ class DeferredFrame(object):
     is the second, and if either half overflowed a capacity both are rebuilt
     singly."""
 
-    def __init__(self, engine, xyz, intensity, logits, boxes, counts,
+    def __init__(self, engine, xyz, intensity, logits, boxes, counts, row,
                  pair=None):
         self.engine = engine
         self.xyz, self.intensity = xyz, intensity
@@ -114,13 +114,11 @@ class DeferredFrame(object):
         self.counts = counts
         self.pair = pair
         self._out = None
-        # the scaled edge stage's guard: the flag row of the pass that computed
-        # this frame (InferenceEngine._begin_pass); in_batch: the batch entry
-        # point reads the rows of all its frames together; rebuilt: the pass's
-        # outputs were not used (its flags mean nothing)
-        self.scale_row = engine._pass_row
+        # the edge stage's guard (gnn.EdgePath): the flag row of the pass that
+        # computed this frame; in_batch: the batch entry point reads the rows
+        # of all its frames together
+        self.row = row
         self.in_batch = False
-        self.rebuilt = False
 
     def result(self, host_counts=None):
         if self._out is not None:
@@ -132,31 +130,29 @@ class DeferredFrame(object):
         graph_gen.check_kd_status(c.kd_status)
         k, edges = c.k, c.edges
         eng._hints = (eng._hints or graph_gen.CountHints()).update(k, edges)
-        if c.overflowed:
+        if c.overflowed or (self.pair is not None and
+                            any(p.overflowed for p in self.pair)):
             # an edge list did not fit the capacity the hints gave it (the
-            # hints now hold 2 x this frame's sizes): rebuild the frame
-            # with host-read sizes
-            eng.deferred_overflows += 1
-            self.rebuilt = True
-            eng.model.edge_scale_discard(self.scale_row)
+            # hints now hold 2 x this frame's sizes), or the other half of
+            # the pass lost rows, so the pass's edge lists are not this
+            # frame's either: rebuild the frame with host-read sizes (the
+            # pass's flags mean nothing; the rebuild's row takes their place)
+            eng.deferred_overflows += bool(c.overflowed)
+            eng.model.edge.discard(self.row)
             self._out = eng.run_frame(self.xyz, self.intensity)
-        elif self.pair is not None and any(p.overflowed for p in self.pair):
-            # the other half of the pass lost rows, so the pass's edge lists
-            # are not this frame's either
-            self.rebuilt = True
-            eng.model.edge_scale_discard(self.scale_row)
-            self._out = eng.run_frame(self.xyz, self.intensity)
+            self.row = eng.model.edge.row
         else:
             eng.frame_shapes.append((k,) + tuple(edges))
             r0 = 0
             if self.pair is not None and self.pair[0] is not c:
                 r0 = self.pair[0].k
             self._out = (self.logits[r0:r0 + k], self.boxes[r0:r0 + k])
-            if not self.in_batch and \
-                    not eng.model.edge_scale_ok([self.scale_row]):
-                del eng.frame_shapes[-1]
-                self._out = eng._rerun_plain(
-                    lambda: eng.run_frame(self.xyz, self.intensity))
+            if not self.in_batch:
+                # (scale flags only: the range flag of 'f16x2' is left to
+                # check_edge_range(), and no scaled kernel ran under it)
+                self._out = eng._plain_if(
+                    eng.model.edge.read([self.row], kinds=('scale',)),
+                    lambda: eng.run_frame(self.xyz, self.intensity), self._out)
         return self._out
 
 
@@ -189,11 +185,10 @@ class CapturedFrame(object):
             self.graph.replay()
         cur.wait_stream(self.stream)
         f = self.frame
-        out = DeferredFrame(self.engine, xyz, intensity, f.logits, f.boxes,
-                            graph_gen.FrameCounts(f.counts.tensor,
-                                                  f.counts.edge_caps))
-        out.scale_row = f.scale_row     # (the captured kernels' flag row)
-        return out
+        # (f.row: the flag row the captured kernels keep writing into)
+        return DeferredFrame(self.engine, xyz, intensity, f.logits, f.boxes,
+                             graph_gen.FrameCounts(f.counts.tensor,
+                                                   f.counts.edge_caps), f.row)
 
 
 class InferenceEngine(object):
@@ -220,28 +215,38 @@ class InferenceEngine(object):
         # are expected to be, learnt from the frames finished so far
         self._hints = None
         self.deferred_overflows = 0
-        # the scaled edge stage (gnn.EDGE_SCALE_HEADROOM): the guard's flags
-        # are kept per forward pass
-        self._pass_row = 0
+        # how often a guard of the edge stage (gnn.EdgePath) sent results
+        # through _plain_if's rerun: the scaled stage's; a batch's 'f16x2' range
         self.edge_scale_reruns = 0
+        self.f16x2_batch_reruns = 0
 
-    def _begin_pass(self):
-        """Before every model.predict whose results are looked at on their
-        own: a row of guard flags for it (DeferredFrame.scale_row)."""
-        self._pass_row = self.model.edge_scale_begin_pass()
-        return self._pass_row
+    def _plain_if(self, verdict, run, out=None):
+        """`out` when the guard's `verdict` on the passes that computed it is
+        clean; else `run()` on the plain path -- the fp32 edge stage, not
+        scaled -- which gives correct results instead of an exception and a
+        discarded batch.  The first pass noted its frames' shapes already."""
+        if not (verdict.range or verdict.scale):
+            return out
+        if verdict.range:
+            self.f16x2_batch_reruns += 1
+        else:     # (the tripped layers' exponents were raised by the verdict)
+            self.edge_scale_reruns += 1
+        shapes = len(self.frame_shapes)
+        with self.model.edge.plain():
+            out = run()
+        del self.frame_shapes[shapes:]
+        return out
 
-    def _rerun_plain(self, run):
-        """`run()` with the scaled edge stage off; `edge_scale_reruns` counts
-        how often (the tripped layers' exponents were raised when the guard
-        was read)."""
-        self.edge_scale_reruns += 1
-        was = self.model.edge_scaled
-        self.model.edge_scaled = False
-        try:
-            return run()
-        finally:
-            self.model.edge_scaled = was
+    def _warm_up(self, frame):
+        """First use: the packed weight images are built lazily (host pack +
+        pageable upload) on whichever stream runs first, and the capacity
+        form needs size hints.  One frame on the CURRENT stream, which every
+        forked stream waits for, so no other stream can read a half-uploaded
+        image; its results (and flags) are not used."""
+        self.run_frame(*frame)
+        self.frame_shapes.pop()
+        self.model.edge.discard(self.model.edge.row)
+        self._warm = True
 
     def _note_shape(self, graph):
         coords, _, edges = graph
@@ -272,17 +277,18 @@ class InferenceEngine(object):
             # no size hints yet, or an empty cloud (host-known: nothing to
             # defer, and empty tensors have no device pointers to hand over)
             out = self.run_frame(xyz, intensity)
-            f = DeferredFrame(self, xyz, intensity, None, None, None)
+            f = DeferredFrame(self, xyz, intensity, None, None, None,
+                              self.model.edge.row)
             f._out = out
             return f
         graph = self.build_graph_deferred(xyz, overlap_build)
         coords, kps, edges = graph
-        self._begin_pass()
+        row = self.model.edge.take_row()
         logits, boxes = self.model.predict(intensity, coords, kps, edges,
                                            is_training=False)
         self.last_graph = graph
         return DeferredFrame(self, xyz, intensity, logits, boxes,
-                             edges[0]._pgnn_count.frame)
+                             edges[0]._pgnn_count.frame, row)
 
     def _pairs_apply(self):
         """Frame pairs (run_frames_on_streams) need size hints, the fp32 edge
@@ -328,13 +334,13 @@ class InferenceEngine(object):
         ga = self.build_graph_deferred(xa)
         gb = self.build_graph_deferred(xb)
         feats, coords, kps, edges = graph_gen.merge_frames_dyn(ga, ia, gb, ib)
-        self._begin_pass()
+        row = self.model.edge.take_row()
         logits, boxes = self.model.predict(feats, coords, kps, edges,
                                            is_training=False)
         self.last_graph = gb
         pair = (ga[2][0]._pgnn_count.frame, gb[2][0]._pgnn_count.frame)
-        return (DeferredFrame(self, xa, ia, logits, boxes, pair[0], pair),
-                DeferredFrame(self, xb, ib, logits, boxes, pair[1], pair))
+        return (DeferredFrame(self, xa, ia, logits, boxes, pair[0], row, pair),
+                DeferredFrame(self, xb, ib, logits, boxes, pair[1], row, pair))
 
     def build_graph(self, xyz):
         """(vertex_coord_list, keypoint_indices_list, edges_list) on the
@@ -479,9 +485,7 @@ class InferenceEngine(object):
         if not frames:
             return []
         if self._hints is None or not getattr(self, "_warm", False):
-            self.run_frame(*frames[0])     # weight images, size hints
-            self.frame_shapes.pop()
-            self._warm = True
+            self._warm_up(frames[0])
         streams = list(concurrent_streams(max(1, int(n_streams))))
         cur = torch.cuda.current_stream()
         for s in streams:
@@ -514,7 +518,7 @@ class InferenceEngine(object):
                         t.record_stream(h)     # allocated on b, read on h
                     frame = edges[0]._pgnn_count.frame
                     frame.tensor.record_stream(h)
-                    self._begin_pass()
+                    row = self.model.edge.take_row()
                     logits, boxes = self.model.predict(
                         intensity, coords, kps, edges, is_training=False)
                     # the next build on b may not overtake this frame's GNN by
@@ -522,7 +526,7 @@ class InferenceEngine(object):
                 b.wait_stream(h)
                 self.last_graph = graph
                 pending.append(DeferredFrame(self, xyz, intensity, logits,
-                                             boxes, frame))
+                                             boxes, frame, row))
             for h in hi:
                 cur.wait_stream(h)
         elif int(frames_per_pass) >= 2 and self._pairs_apply():
@@ -563,19 +567,11 @@ class InferenceEngine(object):
         for lg, bx in outs:     # allocated on a side stream, used by the caller
             lg.record_stream(cur)
             bx.record_stream(cur)
-        if not self._edge_range_clean():
-            return self._rerun_batch_f32(
-                lambda: self.run_frames_on_streams(frames, n_streams,
-                                                   gnn_priority,
-                                                   frames_per_pass))
-        rows = sorted({f.scale_row for f in pending
-                       if not f.rebuilt and f.counts is not None})
-        if rows and not self.model.edge_scale_ok(rows):
-            return self._rerun_batch_plain(
-                lambda: self.run_frames_on_streams(frames, n_streams,
-                                                   gnn_priority,
-                                                   frames_per_pass))
-        return outs
+        # the guard's flags of this batch's own passes, in one read
+        return self._plain_if(
+            self.model.edge.read(sorted({f.row for f in pending})),
+            lambda: self.run_frames_on_streams(frames, n_streams, gnn_priority,
+                                               frames_per_pass), outs)
 
     def _priority_streams(self, n):
         """n high-priority streams (HIP keeps a pool of hardware queues per
@@ -616,13 +612,7 @@ class InferenceEngine(object):
         if not frames:
             return []
         if not getattr(self, "_warm", False):
-            # first use: the packed weight images are built lazily (host pack +
-            # pageable upload) on whichever stream runs first; do that on the
-            # CURRENT stream, which every forked stream waits for below, so no
-            # compute stream can read a half-uploaded image
-            self.run_frame(*frames[0])
-            self.frame_shapes.pop()
-            self._warm = True
+            self._warm_up(frames[0])
         rows = []
         sg, scs = self._pipeline_streams(graph_cus)
         scs = scs[:max(1, min(4, int(compute_streams)))]
@@ -694,11 +684,11 @@ class InferenceEngine(object):
                     if deferred:
                         counts = edges[0]._pgnn_count.frame
                         counts.tensor.record_stream(sc)
-                    rows.append(self._begin_pass())
+                    rows.append(self.model.edge.take_row())
                     out = self.model.predict(frames[i][1], coords, kps,
                                              edges, is_training=False)
                     outs.append(DeferredFrame(self, frames[i][0], frames[i][1],
-                                              out[0], out[1], counts)
+                                              out[0], out[1], counts, rows[-1])
                                 if deferred else out)
                 self.last_graph = graph
                 if not deferred:
@@ -722,60 +712,28 @@ class InferenceEngine(object):
             host = torch.stack([f.counts.tensor for f in outs]).tolist()
             for f in outs:
                 f.in_batch = True
-            outs = [f.result(h) for f, h in zip(outs, host)]
+            deferred_frames = outs
+            outs = [f.result(h) for f, h in zip(deferred_frames, host)]
+            # (a frame rebuilt for an overflow: the row of its rebuild)
+            rows = [f.row for f in deferred_frames]
             for lg, bx in outs:
                 lg.record_stream(cur)
                 bx.record_stream(cur)
-        if not self._edge_range_clean():
-            return self._rerun_batch_f32(
-                lambda: self.run_frames_pipelined(
-                    frames, compute_streams, graph_cus, lookahead, deferred,
-                    graph_streams))
-        if rows and not self.model.edge_scale_ok(sorted(set(rows))):
-            return self._rerun_batch_plain(
-                lambda: self.run_frames_pipelined(
-                    frames, compute_streams, graph_cus, lookahead, deferred,
-                    graph_streams))
-        return outs
-
-    def _edge_range_clean(self):
-        """edge_arith 'f16x2': True when no frame since the last look left
-        fp16's safe range (always True for the other arithmetics)."""
-        return self.model.edge_arith != 'f16x2' or self.model.edge_range_ok()
-
-    def _rerun_batch_f32(self, run):
-        """The range guard of 'f16x2' tripped somewhere in a batch (the flag is
-        the model's, not a frame's): the batch again with the fp32 edge stage
-        -- correct results instead of an exception and a discarded batch.
-        `f16x2_batch_reruns` counts how often."""
-        self.f16x2_batch_reruns = getattr(self, "f16x2_batch_reruns", 0) + 1
-        shapes = len(self.frame_shapes)
-        self.model.edge_arith = 'f32'
-        try:
-            # (the first pass noted the batch's shapes already)
-            outs = run()
-            del self.frame_shapes[shapes:]
-            return outs
-        finally:
-            self.model.edge_arith = 'f16x2'
-
-    def _rerun_batch_plain(self, run):
-        """The scaled edge stage's guard tripped somewhere in a batch: the
-        batch again with the plain edge kernel (_rerun_plain)."""
-        shapes = len(self.frame_shapes)
-        outs = self._rerun_plain(run)
-        # (the first pass noted the batch's shapes already)
-        del self.frame_shapes[shapes:]
-        return outs
+        # the guard's flags of this batch's own passes, in one read
+        return self._plain_if(
+            self.model.edge.read(sorted(set(rows))),
+            lambda: self.run_frames_pipelined(
+                frames, compute_streams, graph_cus, lookahead, deferred,
+                graph_streams), outs)
 
     def check_edge_range(self):
         """edge_arith 'f16x2' only: raises when an activation of a frame run
         since the last call left fp16's range (the kernel clamps at 65504 and
         flags >= 32768; a trained Point-GNN stays below 100) -- such frames
-        must be rerun with edge_arith 'f32'.  One small device-to-host read:
-        the batch entry points (run_frames, run_frames_on_streams) call it
-        once per batch, callers of run_frame / run_frame_deferred call it when
-        they take results."""
+        must be rerun with edge_arith 'f32'.  One small device-to-host read of
+        every row's range flag: the batch entry points look at their own
+        passes' rows themselves and rerun, callers of run_frame /
+        run_frame_deferred call this when they take results."""
         if self.model.edge_arith == 'f16x2' and not self.model.edge_range_ok():
             from . import _lib
             raise _lib.PointGnnHipError(
@@ -795,12 +753,15 @@ class InferenceEngine(object):
             torch.cuda.synchronize()
             t1 = time.perf_counter()
         coords, kps, edges = graph
-        row = self._begin_pass()
+        row = self.model.edge.take_row()
         out = self.model.predict(intensity, coords, kps, edges,
                                  is_training=False)
-        if not self.model.edge_scale_ok([row]):
-            out = self._rerun_plain(lambda: self.model.predict(
-                intensity, coords, kps, edges, is_training=False))
+        # (scale flags only: no read under 'f16x2', whose range flag is left
+        # to check_edge_range())
+        out = self._plain_if(
+            self.model.edge.read([row], kinds=('scale',)),
+            lambda: self.model.predict(intensity, coords, kps, edges,
+                                       is_training=False), out)
         if timed:
             torch.cuda.synchronize()
             t2 = time.perf_counter()

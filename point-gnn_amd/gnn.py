@@ -20,6 +20,7 @@ torch CUDA float32 / int32; activations are kept zero-padded to a multiple of
 16 columns
 (`padded_width`) between operators -- `.features(t, width)` strips the pad.
 """
+import collections
 import contextlib
 import ctypes
 import threading
@@ -35,7 +36,7 @@ __all__ = ["PointSetPooling", "GraphNetAutoCenter", "ClassAwarePredictor",
            "fuse_vertex_stages",
            "multi_layer_neural_network_fn", "multi_layer_fc_fn",
            "graph_scatter_max_fn", "graph_scatter_sum_fn",
-           "graph_scatter_mean_fn", "ParamStore", "parameters",
+           "graph_scatter_mean_fn", "ParamStore", "EdgePath", "parameters",
            "variable_scope", "padded_width"]
 
 
@@ -50,149 +51,22 @@ class ParamStore(object):
     """Holds the model's variables (NumPy, reference TF names) and the
     device-side packed images derived from them (built lazily, cached)."""
 
-    def __init__(self, params, device=None):
+    def __init__(self, params, device=None, edge=None):
+        """edge: the owning model's EdgePath (a bare store makes its own,
+        with the scaled stage off); its calibration and flags start afresh
+        with the store."""
         self.params = {k: np.asarray(v) for k, v in params.items()}
         self.device = device
         self._cache = {}
-        self._edge_arith = 'f32'
-        # EDGE_SCALED below: a model turns it on for its store (models.py);
-        # `inference` is what predict() was last called for
-        self.edge_scaled = False
-        # EDGE_K300 below (only where the scaled stage runs)
-        self.edge_k300 = EDGE_K300
-        self.inference = True
-
-    @property
-    def edge_arith(self):
-        """Arithmetic of GraphNetAutoCenter's per-edge product: EDGE_ARITHS."""
-        return self._edge_arith
-
-    @edge_arith.setter
-    def edge_arith(self, value):
-        if value not in EDGE_ARITHS:
-            raise ValueError("edge_arith must be one of %r, not %r"
-                             % (EDGE_ARITHS, value))
-        self._edge_arith = value
+        self.edge = EdgePath() if edge is None else edge
+        self.edge.reset(device)
 
     def range_status(self):
-        """Device int32 the 'f16x2' edge kernel raises when an activation left
-        fp16's comfortable range (>= 32768); zeroed when created / read."""
-        if getattr(self, '_range_status', None) is None:
-            self._range_status = torch.zeros(1, dtype=torch.int32,
-                                             device=self._dev())
-        return self._range_status
-
-    def edge_range_ok(self):
-        """Reads (and clears) the flag: one small device-to-host read.  True
-        when every 'f16x2' edge stage since the last call stayed in range."""
-        st = getattr(self, '_range_status', None)
-        if st is None:
-            return True
-        ok = int(st.item()) == 0
-        if not ok:
-            st.zero_()
-        return ok
-
-    # ---- scaled operands of the fp32 edge stage (EDGE_SCALED below) ----------
-    def edge_scale_exp(self, scope):
-        """The exponent k layer `scope` runs with, or None while it is not
-        calibrated.  A calibration frame's maxima are read here, at the first
-        call that needs them: one small device-to-host read per model (never
-        while a stream is being captured: the layer stays on the plain path
-        then)."""
-        scales = self.__dict__.setdefault('_edge_scale', {})
-        pend = self.__dict__.setdefault('_edge_scale_pending', {})
-        if scope not in scales and scope in pend and \
-                not torch.cuda.is_current_stream_capturing():
-            names = list(pend)
-            got = [pend.pop(n) for n in names]
-            for _, done in got:      # (written on another stream, perhaps)
-                done.synchronize()
-            for name, m in zip(names,
-                               torch.stack([t for t, _ in got]).tolist()):
-                scales[name] = edge_scale_exp_for(m)
-        return scales.get(scope)
-
-    def note_edge_range(self, scope, p, q):
-        """Calibration: max(|P|, |Q|) of a host-sized frame that ran the plain
-        kernel, kept on the device until edge_scale_exp() needs it."""
-        if torch.cuda.is_current_stream_capturing():
-            return
-        pend = self.__dict__.setdefault('_edge_scale_pending', {})
-        m = torch.maximum(p.abs().max(), q.abs().max())
-        done = torch.cuda.Event()
-        done.record()
-        pend[scope] = (m, done)
-
-    # The guard's flags are a PASS's, not the model's: [EDGE_SCALE_ROWS rows,
-    # EDGE_SCALE_SLOTS layers] int32.  Whoever runs a forward pass whose results
-    # it will look at on its own takes a row first (edge_scale_begin_pass) and
-    # asks about that row afterwards, so a pass whose outputs are thrown away
-    # -- a frame that overflowed a capacity -- taints nobody else.  Rows are
-    # handed out round robin; more than EDGE_SCALE_ROWS passes in flight share
-    # rows (a trip then reruns all that share it).
-    def edge_scale_begin_pass(self):
-        """The flag row of the forward pass about to be enqueued."""
-        self._edge_scale_row = (self.__dict__.get('_edge_scale_row', 0) + 1) \
-            % EDGE_SCALE_ROWS
-        return self._edge_scale_row
-
-    def edge_scale_status(self, scope):
-        """Pointer to the device int32 the scaled kernel of layer `scope`
-        raises, in the current pass's row, when an operand left [-0.5, 0.5]."""
-        slots = self.__dict__.setdefault('_edge_scale_slots', {})
-        if getattr(self, '_edge_scale_flags', None) is None:
-            self._edge_scale_flags = torch.zeros(
-                (EDGE_SCALE_ROWS, EDGE_SCALE_SLOTS), dtype=torch.int32,
-                device=self._dev())
-        if scope not in slots:
-            if len(slots) >= EDGE_SCALE_SLOTS:
-                raise NotImplementedError("more than %d scaled edge layers"
-                                          % EDGE_SCALE_SLOTS)
-            slots[scope] = len(slots)
-        row = self.__dict__.get('_edge_scale_row', 0)
-        return self._edge_scale_flags.data_ptr() + \
-            4 * (row * EDGE_SCALE_SLOTS + slots[scope])
-
-    def edge_scale_ok(self, rows=None):
-        """Reads (and clears) the flags of the passes `rows` (None: all): one
-        small device-to-host read, none before the first scaled launch.  True
-        when no operand left [-0.5, 0.5]; else the tripped layers' exponents
-        are raised by 2 and the caller reruns those passes with `edge_scaled`
-        off."""
-        flags = getattr(self, '_edge_scale_flags', None)
-        if flags is None:
-            return True
-        host = flags.tolist()
-        rows = range(EDGE_SCALE_ROWS) if rows is None else rows
-        return self.edge_scale_tripped({r: host[r] for r in rows})
-
-    def edge_scale_flags(self):
-        """The flags' device tensor [rows, layers] (None before the first
-        scaled launch), for a caller that reads a row with other words of its
-        own."""
-        return getattr(self, '_edge_scale_flags', None)
-
-    def edge_scale_tripped(self, host, count=True):
-        """edge_scale_ok() on rows the caller has read (`host`: {row: its
-        values}); count=False only clears them (the pass's results are not
-        used)."""
-        bad = [r for r, v in host.items() if any(v)]
-        if not bad:
-            return True
-        for r in bad:
-            self._edge_scale_flags[r].zero_()
-        if count:
-            for s, i in self._edge_scale_slots.items():
-                if any(host[r][i] for r in bad):
-                    self._edge_scale[s] = min(24, self._edge_scale.get(s, 0) + 2)
-        return False
-
-    def edge_scale_discard(self, row):
-        """Clears a row unread: its pass's results are not used."""
-        flags = getattr(self, '_edge_scale_flags', None)
-        if flags is not None:
-            flags[row].zero_()
+        """The int32 the 'f16x2' kernels of the calling thread's current pass
+        raise when an activation left fp16's comfortable range (>= 32768): a
+        1-element view of the guard's table (EdgePath)."""
+        self.edge.status('range')
+        return self.edge.flags[self.edge.row, EDGE_SCALE_SLOTS:]
 
     def _dev(self):
         if self.device is None:
@@ -235,16 +109,31 @@ class ParamStore(object):
     def mlp(self, scope, n_layers):
         return [self.fc(n) for n in mlp_names(scope, n_layers)]
 
-    def pack(self, w, b, k300=False):
-        """[k_in, n_out] weights + bias -> device tensor in MFMA fragment order
-        (pgnn_pack_fc; k300: pgnn_pack_fc_k300, rows 288..303 in EDGE_K300's
-        order)."""
+    # kind -> (size query, its unit, packer) of pack()
+    PACKERS = {
+        'f32': ("pgnn_packed_fc_floats", np.float32, "pgnn_pack_fc"),
+        'k300': ("pgnn_packed_fc_floats", np.float32, "pgnn_pack_fc_k300"),
+        'bf16x3': ("pgnn_packed_fc_bf16x3_bytes", np.uint8,
+                   "pgnn_pack_fc_bf16x3"),
+        'f16x2': ("pgnn_packed_fc_f16x2_bytes", np.uint8,
+                  "pgnn_pack_fc_f16x2"),
+        'f16x2_acc': ("pgnn_packed_fc_f16x2_bytes", np.uint8,
+                      "pgnn_pack_fc_f16x2_acc"),
+    }
+
+    def pack(self, w, b, kind='f32'):
+        """[k_in, n_out] weights + bias -> device tensor: packed on the host,
+        then uploaded.  'f32': MFMA fragment order (pgnn_pack_fc); 'k300': the
+        same with rows 288..303 in EDGE_K300's order; 'bf16x3' / 'f16x2': the
+        split-precision edge kernels' images; 'f16x2_acc': the f16x2 pooling
+        kernel's.  The 16-bit packers refuse a weight outside their format's
+        range (E_UNSUPPORTED)."""
         lib = _lib.load()
+        size, unit, name = self.PACKERS[kind]
         w = np.ascontiguousarray(w, dtype=np.float32)
         b = np.ascontiguousarray(b, dtype=np.float32)
         k_in, n_out = w.shape
-        host = np.empty(lib.pgnn_packed_fc_floats(k_in, n_out), np.float32)
-        name = "pgnn_pack_fc_k300" if k300 else "pgnn_pack_fc"
+        host = np.empty(getattr(lib, size)(k_in, n_out), unit)
         _lib.check(getattr(lib, name)(w.ctypes.data, b.ctypes.data, k_in,
                                       n_out, host.ctypes.data), name)
         return torch.from_numpy(host).to(self._dev())
@@ -269,7 +158,7 @@ class Chain(object):
         self.array = (_lib.FcLayer * len(layers))()
         self.n = len(layers)
         for i, (w, b, relu_from) in enumerate(layers):
-            buf = store.pack(w, b, k300)
+            buf = store.pack(w, b, 'k300' if k300 else 'f32')
             self.buffers.append(buf)
             self.array[i].packed = buf.data_ptr()
             self.array[i].k_in = int(w.shape[0])
@@ -280,14 +169,16 @@ class Chain(object):
 
 
 class _State(threading.local):
-    """The bound ParamStore and the variable-scope stack, PER THREAD: two
-    Python threads driving operators (the frame pipeline's builder thread, a
-    serving front end) each see their own `parameters()` / `variable_scope()`
-    nesting, like tf.variable_scope's thread-local stack."""
+    """The bound ParamStore, the variable-scope stack and the current pass's
+    row of guard flags, PER THREAD: two Python threads driving operators (the
+    frame pipeline's builder thread, a serving front end) each see their own
+    `parameters()` / `variable_scope()` nesting, like tf.variable_scope's
+    thread-local stack, and raise flags in the row they took themselves."""
 
     def __init__(self):
         self.store = None
         self.scope = []
+        self.edge_row = 0      # EdgePath.take_row()
         self.fuse = False      # fuse_vertex_stages() active
         self.pending = None    # an operator's deferred per-vertex tail
         self.taken = None      # ... taken over by its consumer, not launched yet
@@ -317,6 +208,276 @@ def variable_scope(name):
 
 def _scope(*suffix):
     return '/'.join(list(_state.scope) + list(suffix))
+
+
+# --------------------------------------------------------------------------
+# the edge stage's settings, calibration and guard
+# --------------------------------------------------------------------------
+# Arithmetic of the per-edge 300x300 / 256x256 product (gnn.py:355-365), an
+# attribute of the MODEL (`model.edge_arith`, `InferenceEngine(...,
+# edge_arith=)`; it lives in the model's EdgePath, so two models in one
+# process -- or frames of two engines in flight on different streams -- do not
+# share a switch):
+#   'f32'    -- fp32 MFMA (default; the parity reference, bit-identical between
+#               its kernel variants);
+#   'bf16x3' -- SECONDARY: both operands split exactly into three bf16 parts,
+#               six bf16 MFMAs per block accumulated in fp32
+#               (csrc/edge_ws_split.h, pgnn_edge_mlp_scatter_max_bf16x3_fwd):
+#               agrees with 'f32' to fp32 rounding noise, ~1.7x faster.  Falls
+#               back to 'f32' where the kernel does not apply (few edges,
+#               other layer shapes).
+#   'f16x2'  -- SECONDARY: both operands as TWO fp16 values (22 significand
+#               bits, round to nearest), three fp16 MFMAs per block
+#               (csrc/edge_ws_split.h, pgnn_edge_mlp_scatter_max_f16x2_fwd):
+#               not exact -- the stage's distance to float64 grows by a few per
+#               cent -- ~3x faster than 'f32'.  Activations are clamped at
+#               65504; the kernel flags passes in which one could reach 32768, in
+#               the range column of the pass's row of the guard's table
+#               (EdgePath), and whoever takes the pass's results reads it with
+#               them (`model.edge.read([row])`; `model.edge_range_ok()` looks at
+#               every row): rerun such a frame in 'f32'.  Also covers
+#               the wide last layer of PointSetPooling's point MLP
+#               (csrc/pool_ws_f16.h, pgnn_point_set_pooling_f16x2_fwd; car's
+#               4-32-64-128-300 chain), same representation, same guard.
+# The split-precision kernels are max-only: a layer built with
+# graph_scatter_sum_fn / graph_scatter_mean_fn runs the fp32 kernel under
+# 'bf16x3' and 'f16x2' too.
+EDGE_ARITHS = ('f32', 'bf16x3', 'f16x2')
+
+# Scaled operands of the 'f32' edge stage (csrc/edge_ws.h, pk_sub_clamp;
+# pgnn_edge_mlp_scatter_max_scaled_fwd), an attribute of the MODEL
+# (`model.edge_scaled`, default on; off for a bare ParamStore): where the
+# weights-stationary kernel serves the launch (pgnn_edge_ws_applies), the
+# per-vertex stage writes P' = 2^-k P, Q' = 2^-k Q -- from a second image of the
+# vertex-side first layer, w1, b1 and wx times 2^-k, which is exact -- and the
+# edge kernel's packed subtraction, clamped to [0, 1], is its own ReLU.  The
+# results are those of the plain kernel bit for bit.  k is the layer's: the
+# first host-sized inference frame runs the plain kernel and leaves
+# max(|P|, |Q|) on the device; k is the smallest exponent that brings it to
+# 0.125 or below (4x headroom under the kernel's guard at 0.5).  A tripped guard
+# (the `scale` of `model.edge.read(rows)`, read by the engine with a batch's
+# results) means: rerun those frames inside `model.edge.plain()`; the layer's k
+# has been raised by 2.  Sum / mean aggregation, the 16-bit arithmetics and
+# training take the plain path.
+EDGE_SCALE_HEADROOM = 0.125
+# the guard's table: EDGE_SCALE_ROWS passes, one column per scaled layer and,
+# behind them, the 'f16x2' range flag's (EdgePath.take_row / .status)
+EDGE_SCALE_ROWS, EDGE_SCALE_SLOTS = 64, 16
+EDGE_FLAG_KINDS = ('scale', 'range')
+
+# The scaled stage of a 300-wide layer without the MFMA step of K = 300's
+# padding (csrc/edge_ws.h, K300; PGNN_EDGE_K300_ORDER), `model.edge_k300`: the
+# hidden features 288..303 -- the last K group -- are kept in the order of
+# pgnn_k300_source, in which the four padding features are the group's whole
+# fourth MFMA step.  Only data moves: the scaled images of w1, b1 and wx get
+# their output columns permuted, the second layer's image its rows
+# (pgnn_pack_fc_k300); the real products keep their place in every fmaf chain,
+# so the results stay what they were bit for bit.  Nothing but the scaled kernel
+# reads operands in this order: the plain rerun after a guard trip, the
+# LDS-tile kernel, EDGE_INPUT_TAP, the 16-bit arithmetics, sum / mean and
+# training are on the natural order, as they are off the scaled path.
+EDGE_K300 = True
+
+
+def edge_k300_order(n=304):
+    """src [n]: column p of the permuted operands is feature src[p] (300..303:
+    the zero padding)."""
+    lib = _lib.load()
+    return np.array([lib.pgnn_k300_source(p) for p in range(n)], np.int64)
+
+
+def edge_k300_columns(a, width=304):
+    """[..., 300] -> [..., width] float32 with the columns in
+    edge_k300_order()."""
+    a = np.asarray(a, np.float32)
+    src = edge_k300_order(width)
+    out = np.zeros(a.shape[:-1] + (width,), np.float32)
+    real = src < a.shape[-1]
+    out[..., real] = a[..., src[real]]
+    return out
+
+
+def edge_scale_exp_for(max_abs):
+    """Smallest k >= 0 with max_abs * 2^-k <= EDGE_SCALE_HEADROOM (24 at the
+    most: the kernel's range; an infinite or NaN maximum gets 24 and trips the
+    guard)."""
+    k = 0
+    while k < 24 and not max_abs * 2.0 ** -k <= EDGE_SCALE_HEADROOM:
+        k += 1
+    return k
+
+
+# what the flags of some passes said: `range` -- an 'f16x2' kernel saw an
+# activation of 32768 or more; `scale` -- a scaled kernel an operand outside
+# [-0.5, 0.5].  Either way those passes' results are run again inside
+# EdgePath.plain().
+EdgeVerdict = collections.namedtuple('EdgeVerdict', 'range scale')
+
+
+class EdgePath(object):
+    """How a model's edge stage runs: the settings (`arith`: EDGE_ARITHS;
+    `scaled`: EDGE_SCALE_HEADROOM; `k300`: EDGE_K300; `inference`: what
+    predict() was last called for), the scaled stage's calibration (`exps`:
+    {layer scope: k}) and the guard of the fast forms.  The model owns it and
+    hands it to its ParamStore: the settings outlive load_state_dict,
+    everything else starts afresh with the store (reset).
+
+    The guard's flags are a PASS's, not the model's: `flags` is int32
+    [EDGE_SCALE_ROWS, EDGE_SCALE_SLOTS + 1], a column per scaled layer
+    (`slots`, in first-use order) and one for the 'f16x2' range flag; the
+    kernels raise them with an atomic OR.  Whoever runs a forward pass whose
+    results it will look at on its own takes a row first (take_row: it becomes
+    the calling THREAD's current row, which status() points the kernels at)
+    and asks about that row afterwards (read / verdict), so a pass whose
+    outputs are thrown away -- a frame that overflowed a capacity -- taints
+    nobody else (discard).  Rows are handed out round robin; more than
+    EDGE_SCALE_ROWS passes in flight share rows (a trip then reruns all that
+    share it)."""
+
+    def __init__(self, arith='f32', scaled=False, k300=EDGE_K300, device=None):
+        self.arith = arith
+        self.scaled, self.k300 = bool(scaled), bool(k300)
+        self.inference = True
+        self._last_row = 0
+        self.reset(device)
+
+    @property
+    def arith(self):
+        return self._arith
+
+    @arith.setter
+    def arith(self, value):
+        if value not in EDGE_ARITHS:
+            raise ValueError("edge_arith must be one of %r, not %r"
+                             % (EDGE_ARITHS, value))
+        self._arith = value
+
+    def reset(self, device=None):
+        """New weights: no calibration, no slots, no table (`flags` is None
+        until the first status())."""
+        self.device = device
+        self.exps = {}
+        self._pending = {}
+        self.slots = {}
+        self._range_used = False
+        self.flags = None
+
+    @contextlib.contextmanager
+    def plain(self):
+        """The path every guarded result is run again on: `scaled` off and
+        'f16x2' replaced by 'f32' ('bf16x3' has no guard and stays)."""
+        was = self.arith, self.scaled
+        self.arith = 'f32' if self.arith == 'f16x2' else self.arith
+        self.scaled = False
+        try:
+            yield self
+        finally:
+            self.arith, self.scaled = was
+
+    # ---- calibration of the scaled stage ---------------------------------
+    def exp(self, scope):
+        """The exponent k layer `scope` runs with, or None while it is not
+        calibrated.  A calibration frame's maxima are read here, at the first
+        call that needs them: one small device-to-host read per model (never
+        while a stream is being captured: the layer stays on the plain path
+        then)."""
+        if scope not in self.exps and scope in self._pending and \
+                not torch.cuda.is_current_stream_capturing():
+            names = list(self._pending)
+            got = [self._pending.pop(n) for n in names]
+            for _, done in got:      # (written on another stream, perhaps)
+                done.synchronize()
+            for name, m in zip(names,
+                               torch.stack([t for t, _ in got]).tolist()):
+                self.exps[name] = edge_scale_exp_for(m)
+        return self.exps.get(scope)
+
+    def note_edge_range(self, scope, p, q):
+        """Calibration: max(|P|, |Q|) of a host-sized frame that ran the plain
+        kernel, kept on the device until exp() needs it."""
+        if torch.cuda.is_current_stream_capturing():
+            return
+        m = torch.maximum(p.abs().max(), q.abs().max())
+        done = torch.cuda.Event()
+        done.record()
+        self._pending[scope] = (m, done)
+
+    # ---- the guard -----------------------------------------------------------
+    def take_row(self):
+        """The flag row of the forward pass the calling thread is about to
+        enqueue; it stays the thread's current row until its next call."""
+        self._last_row = (self._last_row + 1) % EDGE_SCALE_ROWS
+        _state.edge_row = self._last_row
+        return self._last_row
+
+    @property
+    def row(self):
+        """The calling thread's current row (0 before it took one)."""
+        return _state.edge_row
+
+    def column(self, kind, scope=None):
+        """'range': the range flag's column; 'scale': layer `scope`'s."""
+        if kind == 'range':
+            self._range_used = True
+            return EDGE_SCALE_SLOTS
+        if scope not in self.slots:
+            if len(self.slots) >= EDGE_SCALE_SLOTS:
+                raise NotImplementedError("more than %d scaled edge layers"
+                                          % EDGE_SCALE_SLOTS)
+            self.slots[scope] = len(self.slots)
+        return self.slots[scope]
+
+    def status(self, kind, scope=None):
+        """Address of the int32 a kernel raises in the calling thread's current
+        row: kind 'scale' -- the scaled kernel of layer `scope`, when an
+        operand left [-0.5, 0.5]; 'range' -- an 'f16x2' kernel, when an
+        activation reached 32768."""
+        col = self.column(kind, scope)
+        if self.flags is None:
+            dev = self.device if self.device is not None else \
+                torch.device("cuda", torch.cuda.current_device())
+            self.flags = torch.zeros((EDGE_SCALE_ROWS, EDGE_SCALE_SLOTS + 1),
+                                     dtype=torch.int32, device=dev)
+        return self.flags.data_ptr() + \
+            4 * (_state.edge_row * (EDGE_SCALE_SLOTS + 1) + col)
+
+    def verdict(self, host, count=True, kinds=EDGE_FLAG_KINDS):
+        """`host`: {row: its values, read by the caller}.  Says which `kinds`
+        of flag were up in them and clears, on the device, what it looked at.
+        A scale trip raises the tripped layers' exponents by 2 (24 at the
+        most); count=False only clears (the passes' results are not used)."""
+        cols = slice(0 if 'scale' in kinds else EDGE_SCALE_SLOTS,
+                     EDGE_SCALE_SLOTS + ('range' in kinds))
+        up = [r for r, v in host.items() if any(v[cols])]
+        for r in up:
+            self.flags[r, cols].zero_()
+        tripped = [s for s, i in self.slots.items()
+                   if 'scale' in kinds and any(host[r][i] for r in up)]
+        if count:
+            for s in tripped:
+                self.exps[s] = min(24, self.exps.get(s, 0) + 2)
+        return EdgeVerdict('range' in kinds and
+                           any(host[r][EDGE_SCALE_SLOTS] for r in up),
+                           bool(tripped))
+
+    def read(self, rows=None, count=True, kinds=None):
+        """verdict() of the passes `rows` (None: all) from the device: one
+        small device-to-host read, none for a kind no kernel has been pointed
+        at yet.  kinds None: what the current `arith` can raise."""
+        if kinds is None:
+            kinds = EDGE_FLAG_KINDS if self.arith == 'f16x2' else ('scale',)
+        kinds = [k for k in kinds
+                 if (self.slots if k == 'scale' else self._range_used)]
+        if not kinds or self.flags is None:
+            return EdgeVerdict(False, False)
+        host = self.flags.tolist()
+        rows = range(EDGE_SCALE_ROWS) if rows is None else rows
+        return self.verdict({r: host[r] for r in rows}, count, kinds)
+
+    def discard(self, row):
+        """Clears a row unread: its pass's results are not used."""
+        if self.flags is not None:
+            self.flags[row].zero_()
 
 
 # --------------------------------------------------------------------------
@@ -661,6 +822,14 @@ def _both_counts(cnt_a, n_a, cnt_b, n_b, device):
 # --------------------------------------------------------------------------
 # layers
 # --------------------------------------------------------------------------
+# what a layer's `_form` decides before it launches anything: the kind of the
+# fused stage and what that kind's entry needs
+_PoolForm = collections.namedtuple('_PoolForm', 'kind image hidden ws_bytes')
+_EdgeForm = collections.namedtuple(
+    '_EdgeForm', 'kind p_chain wx rest scale_k k300 image calibrate')
+
+
+
 class PointSetPooling(object):
     """gnn.py:211-283."""
 
@@ -671,6 +840,45 @@ class PointSetPooling(object):
         self._point_feature_fn = point_feature_fn
         self._aggregation_fn = aggregation_fn
         self._output_fn = output_fn
+
+    def _form(self, lib, store, point_chain, pscope, widths, n_feat, n_e,
+              cnt_e):
+        """Which form the fused stage takes, decided before any launch:
+        'agg' (sum / mean), 'f16x2' (with its two images), else _form_f32's."""
+        if self._aggregation != _lib.AGG_MAX:
+            return _PoolForm('agg', None, None, 0)
+        if store.edge.arith == 'f16x2' and point_chain.n == 4:
+            # the model's 16-bit arithmetic covers this stage's wide layer too
+            # (csrc/pool_ws_f16.h)
+            def image(li):
+                return store.pack(*store.mlp(pscope, point_chain.n)[li],
+                                  'f16x2_acc')
+            try:
+                return _PoolForm(
+                    'f16x2',
+                    store.cached(('pool_f16x2', pscope, widths),
+                                 lambda: image(-1)),
+                    store.cached(('pool_f16x2_h', pscope, widths),
+                                 lambda: image(-2)), 0)
+            except _lib.PointGnnHipError as err:
+                if "code %d" % _lib.E_UNSUPPORTED not in str(err):
+                    raise
+                # fallback (a weight outside fp16's range): the fp32 kernel
+        return self._form_f32(lib, point_chain, n_feat, n_e, cnt_e)
+
+    @staticmethod
+    def _form_f32(lib, point_chain, n_feat, n_e, cnt_e):
+        """'workspace': chains whose last layer does not fit one CU's LDS
+        (ped_cyl's 4-32-64-128-256-512) run as two launches through a
+        workspace of hidden rows (csrc/pool_split.h); 'plain': everything
+        else asks for none."""
+        ws_bytes = ctypes.c_size_t(0)
+        _lib.check(lib.pgnn_point_set_pooling_workspace_bytes(
+            point_chain.array, point_chain.n, n_feat, n_e,
+            int(cnt_e.hint) if cnt_e is not None else 0,
+            ctypes.byref(ws_bytes)), "pgnn_point_set_pooling_workspace_bytes")
+        return _PoolForm('workspace' if ws_bytes.value else 'plain', None,
+                         None, ws_bytes.value)
 
     def apply_regular(self, point_features, point_coordinates,
                       keypoint_indices, set_indices,
@@ -687,9 +895,9 @@ class PointSetPooling(object):
         _flush_pending()
         lib = _lib.load()
         store = _store()
-        with variable_scope('extract_vertex_features'):
-            point_chain = _relu_chain(store, _scope(),
-                                      list(point_MLP_depth_list), False)
+        pscope = _scope('extract_vertex_features')
+        point_chain = _relu_chain(store, pscope, list(point_MLP_depth_list),
+                                  False)
         feats = _as_f32(point_features)
         xyz = _as_f32(point_coordinates)
         # capacity form (graph_gen's deferred_counts): K and the edge count
@@ -740,86 +948,44 @@ class PointSetPooling(object):
             feats = feats[:, :n_feat].contiguous()
         agg = torch.empty((k, padded_width(point_chain.n_out)),
                           dtype=torch.float32, device=xyz.device)
-        args = (_lib.ptr(feats), n_feat, _lib.ptr(xyz), _lib.ptr(kp),
-                _lib.ptr(edges), int(edges.shape[0]), k, point_chain.array,
-                point_chain.n, _edges_sorted_flag(set_indices), _lib.ptr(agg),
-                agg.stride(0), _lib.ptr(_lib.sched_ws(xyz.device)))
+        n_e = int(edges.shape[0])
+        head = (_lib.ptr(feats), n_feat, _lib.ptr(xyz), _lib.ptr(kp),
+                _lib.ptr(edges), n_e, k, point_chain.array, point_chain.n)
+        out = (_edges_sorted_flag(set_indices), _lib.ptr(agg), agg.stride(0),
+               _lib.ptr(_lib.sched_ws(xyz.device)))
         if cnt_k is not None or cnt_e is not None:
-            cnt_k, cnt_e = _both_counts(cnt_k, k, cnt_e, int(edges.shape[0]),
-                                        xyz.device)
-        done = False
-        if self._aggregation != _lib.AGG_MAX:
+            cnt_k, cnt_e = _both_counts(cnt_k, k, cnt_e, n_e, xyz.device)
+        dyn = (cnt_e.arg(), cnt_k.arg()) if cnt_e is not None else (None, None)
+        form = self._form(lib, store, point_chain, pscope,
+                          tuple(point_MLP_depth_list), n_feat, n_e, cnt_e)
+        if form.kind == 'f16x2':
+            rc = lib.pgnn_point_set_pooling_f16x2_fwd(
+                *head, _lib.ptr(form.image), _lib.ptr(form.hidden), *out,
+                store.edge.status('range'), *dyn, _lib.stream_ptr())
+            if rc == _lib.E_UNSUPPORTED:
+                # fallback (other shapes, few edges): the fp32 kernel
+                form = self._form_f32(lib, point_chain, n_feat, n_e, cnt_e)
+            else:
+                _lib.check(rc, "pgnn_point_set_pooling_f16x2_fwd")
+        if form.kind == 'agg':
             # sum / mean (csrc/ws_sum.h; fp32 whatever the model's edge_arith)
             _aggregate(lib, "point_set_pooling_agg",
-                       (point_chain.array, point_chain.n, n_feat), args,
-                       int(edges.shape[0]), k, cnt_e, cnt_k, self._aggregation,
-                       xyz.device)
-            done = True
-        elif store.edge_arith == 'f16x2' and point_chain.n == 4:
-            # the model's 16-bit arithmetic covers this stage's wide layer too
-            # (csrc/pool_ws_f16.h); other shapes / few edges: the fp32 kernel
-            with variable_scope('extract_vertex_features'):
-                pscope = _scope()
-
-            def build(li=-1):
-                w, b = store.mlp(pscope, point_chain.n)[li]
-                w = np.ascontiguousarray(w, dtype=np.float32)
-                b = np.ascontiguousarray(b, dtype=np.float32)
-                host = np.empty(lib.pgnn_packed_fc_f16x2_bytes(*w.shape),
-                                np.uint8)
-                _lib.check(lib.pgnn_pack_fc_f16x2_acc(
-                    w.ctypes.data, b.ctypes.data, w.shape[0], w.shape[1],
-                    host.ctypes.data), "pgnn_pack_fc_f16x2_acc")
-                return torch.from_numpy(host).to(store._dev())
-            try:
-                image = store.cached(
-                    ('pool_f16x2', pscope, tuple(point_MLP_depth_list)), build)
-                hidden = store.cached(
-                    ('pool_f16x2_h', pscope, tuple(point_MLP_depth_list)),
-                    lambda: build(-2))
-            except _lib.PointGnnHipError as err:
-                if "code %d" % _lib.E_UNSUPPORTED not in str(err):
-                    raise
-                image = None     # a weight outside fp16's range
-            if image is not None:
-                rc = lib.pgnn_point_set_pooling_f16x2_fwd(
-                    *(args[:9] + (_lib.ptr(image), _lib.ptr(hidden)) +
-                      args[9:] +
-                      (_lib.ptr(store.range_status()),
-                       cnt_e.arg() if cnt_e is not None else None,
-                       cnt_k.arg() if cnt_k is not None else None,
-                       _lib.stream_ptr())))
-                if rc != _lib.E_UNSUPPORTED:
-                    _lib.check(rc, "pgnn_point_set_pooling_f16x2_fwd")
-                    done = True
-        ws_bytes = ctypes.c_size_t(0)
-        if not done:
-            # chains whose last layer does not fit one CU's LDS (ped_cyl's
-            # 4-32-64-128-256-512) run as two launches through a workspace of
-            # hidden rows (csrc/pool_split.h); everything else asks for none
-            _lib.check(lib.pgnn_point_set_pooling_workspace_bytes(
-                point_chain.array, point_chain.n, n_feat, int(edges.shape[0]),
-                int(cnt_e.hint) if cnt_e is not None else 0,
-                ctypes.byref(ws_bytes)),
-                "pgnn_point_set_pooling_workspace_bytes")
-        if done:
-            pass
-        elif ws_bytes.value:
+                       (point_chain.array, point_chain.n, n_feat), head + out,
+                       n_e, k, cnt_e, cnt_k, self._aggregation, xyz.device)
+        elif form.kind == 'workspace':
             # (a stream-ordered allocation of the caching allocator: the next
             # frame on this stream gets the same block back)
-            work = torch.empty(ws_bytes.value // 4, dtype=torch.float32,
+            work = torch.empty(form.ws_bytes // 4, dtype=torch.float32,
                                device=xyz.device)
             _lib.check(lib.pgnn_point_set_pooling_fwd_ws(
-                *args, cnt_e.arg() if cnt_e is not None else None,
-                cnt_k.arg() if cnt_k is not None else None, _lib.ptr(work),
-                ws_bytes.value, _lib.stream_ptr()),
-                "pgnn_point_set_pooling_fwd_ws")
-        elif cnt_k is None and cnt_e is None:
+                *head, *out, *dyn, _lib.ptr(work), form.ws_bytes,
+                _lib.stream_ptr()), "pgnn_point_set_pooling_fwd_ws")
+        elif form.kind == 'plain' and cnt_e is None:
             _lib.check(lib.pgnn_point_set_pooling_fwd(
-                *args, _lib.stream_ptr()), "pgnn_point_set_pooling_fwd")
-        else:
+                *head, *out, _lib.stream_ptr()), "pgnn_point_set_pooling_fwd")
+        elif form.kind == 'plain':
             _lib.check(lib.pgnn_point_set_pooling_fwd_dyn(
-                *args, cnt_e.arg(), cnt_k.arg(), _lib.stream_ptr()),
+                *head, *out, *dyn, _lib.stream_ptr()),
                 "pgnn_point_set_pooling_fwd_dyn")
         if AGGREGATE_TAP is not None:
             AGGREGATE_TAP.append(agg)
@@ -833,95 +999,6 @@ class PointSetPooling(object):
 # tensors: bench.py times the edge kernel on a frame's real inputs with it
 EDGE_INPUT_TAP = None
 
-# Arithmetic of the per-edge 300x300 / 256x256 product (gnn.py:355-365), an
-# attribute of the MODEL (`model.edge_arith`, `InferenceEngine(...,
-# edge_arith=)`; it travels with the model's ParamStore, so two models in one
-# process -- or frames of two engines in flight on different streams -- do not
-# share a switch):
-#   'f32'    -- fp32 MFMA (default; the parity reference, bit-identical between
-#               its kernel variants);
-#   'bf16x3' -- SECONDARY: both operands split exactly into three bf16 parts,
-#               six bf16 MFMAs per block accumulated in fp32
-#               (csrc/edge_ws_split.h, pgnn_edge_mlp_scatter_max_bf16x3_fwd):
-#               agrees with 'f32' to fp32 rounding noise, ~1.7x faster.  Falls
-#               back to 'f32' where the kernel does not apply (few edges,
-#               other layer shapes).
-#   'f16x2'  -- SECONDARY: both operands as TWO fp16 values (22 significand
-#               bits, round to nearest), three fp16 MFMAs per block
-#               (csrc/edge_ws_split.h, pgnn_edge_mlp_scatter_max_f16x2_fwd):
-#               not exact -- the stage's distance to float64 grows by a few per
-#               cent -- ~3x faster than 'f32'.  Activations are clamped at
-#               65504; the kernel flags frames in which one could reach 32768 and
-#               `model.edge_range_ok()` (read by the engine with a frame's
-#               results) reports it: rerun such a frame in 'f32'.  Also covers
-#               the wide last layer of PointSetPooling's point MLP
-#               (csrc/pool_ws_f16.h, pgnn_point_set_pooling_f16x2_fwd; car's
-#               4-32-64-128-300 chain), same representation, same guard.
-# The split-precision kernels are max-only: a layer built with
-# graph_scatter_sum_fn / graph_scatter_mean_fn runs the fp32 kernel under
-# 'bf16x3' and 'f16x2' too.
-EDGE_ARITHS = ('f32', 'bf16x3', 'f16x2')
-
-# Scaled operands of the 'f32' edge stage (csrc/edge_ws.h, pk_sub_clamp;
-# pgnn_edge_mlp_scatter_max_scaled_fwd), an attribute of the MODEL
-# (`model.edge_scaled`, default on; off for a bare ParamStore): where the
-# weights-stationary kernel serves the launch (pgnn_edge_ws_applies), the
-# per-vertex stage writes P' = 2^-k P, Q' = 2^-k Q -- from a second image of the
-# vertex-side first layer, w1, b1 and wx times 2^-k, which is exact -- and the
-# edge kernel's packed subtraction, clamped to [0, 1], is its own ReLU.  The
-# results are those of the plain kernel bit for bit.  k is the layer's: the
-# first host-sized inference frame runs the plain kernel and leaves
-# max(|P|, |Q|) on the device; k is the smallest exponent that brings it to
-# 0.125 or below (4x headroom under the kernel's guard at 0.5).  A tripped guard
-# (`model.edge_scale_ok()` False, read by the engine with a batch's results)
-# means: rerun those frames with `edge_scaled` off; the layer's k has been
-# raised by 2.  Sum / mean aggregation, the 16-bit arithmetics and training take
-# the plain path.
-EDGE_SCALE_HEADROOM = 0.125
-EDGE_SCALE_ROWS, EDGE_SCALE_SLOTS = 64, 16    # ParamStore.edge_scale_begin_pass
-
-# The scaled stage of a 300-wide layer without the MFMA step of K = 300's
-# padding (csrc/edge_ws.h, K300; PGNN_EDGE_K300_ORDER), `model.edge_k300`: the
-# hidden features 288..303 -- the last K group -- are kept in the order of
-# pgnn_k300_source, in which the four padding features are the group's whole
-# fourth MFMA step.  Only data moves: the scaled images of w1, b1 and wx get
-# their output columns permuted, the second layer's image its rows
-# (pgnn_pack_fc_k300); the real products keep their place in every fmaf chain,
-# so the results stay what they were bit for bit.  Nothing but the scaled kernel
-# reads operands in this order: the plain rerun after a guard trip, the
-# LDS-tile kernel, EDGE_INPUT_TAP, the 16-bit arithmetics, sum / mean and
-# training are on the natural order, as they are off the scaled path.
-EDGE_K300 = True
-
-
-def edge_k300_order(n=304):
-    """src [n]: column p of the permuted operands is feature src[p] (300..303:
-    the zero padding)."""
-    lib = _lib.load()
-    return np.array([lib.pgnn_k300_source(p) for p in range(n)], np.int64)
-
-
-def edge_k300_columns(a, width=304):
-    """[..., 300] -> [..., width] float32 with the columns in
-    edge_k300_order()."""
-    a = np.asarray(a, np.float32)
-    src = edge_k300_order(width)
-    out = np.zeros(a.shape[:-1] + (width,), np.float32)
-    real = src < a.shape[-1]
-    out[..., real] = a[..., src[real]]
-    return out
-
-
-def edge_scale_exp_for(max_abs):
-    """Smallest k >= 0 with max_abs * 2^-k <= EDGE_SCALE_HEADROOM (24 at the
-    most: the kernel's range; an infinite or NaN maximum gets 24 and trips the
-    guard)."""
-    k = 0
-    while k < 24 and not max_abs * 2.0 ** -k <= EDGE_SCALE_HEADROOM:
-        k += 1
-    return k
-
-
 class GraphNetAutoCenter(object):
     """gnn.py:285-373."""
 
@@ -934,6 +1011,68 @@ class GraphNetAutoCenter(object):
         self._aggregation_fn = aggregation_fn
         self._update_fn = update_fn
         self._auto_offset_fn = auto_offset_fn
+
+    def _form(self, lib, store, edge_scope, widths, natural, n_e, cnt_e, cnt_k,
+              st):
+        """Which form the stage takes, decided before any launch (the
+        per-vertex stage writes the scaled operands): 'agg' (sum / mean),
+        'split' (the 16-bit arithmetics, with the second layer's image),
+        'scaled' (EDGE_SCALE_HEADROOM: with the scaled vertex-side images and
+        the exponent) or 'plain' (`calibrate`: leave the operands' maxima for
+        the scaled stage).  natural: the cached ('edge', ...) entry."""
+        c, p_chain, wx_dev, rest = natural
+        edge = store.edge
+
+        def form(kind, image=None, calibrate=False):
+            # (the natural operands: every kind but 'scaled')
+            return _EdgeForm(kind, p_chain, wx_dev, rest, None, False, image,
+                             calibrate)
+        if self._aggregation != _lib.AGG_MAX:
+            return form('agg')
+        if rest.n != 1:
+            return form('plain')
+        if edge.arith != 'f32':
+            return form('split', image=store.cached(
+                ('edge_' + edge.arith, edge_scope, widths),
+                lambda: store.pack(*store.mlp(edge_scope, len(widths))[1],
+                                   edge.arith)))
+        if not (edge.scaled and edge.inference):
+            return form('plain')
+        # the launcher's own partition query
+        n_exp = n_e
+        if cnt_e is not None and 0 < cnt_e.hint < n_exp:
+            n_exp = cnt_e.hint
+        applies = ctypes.c_int32(0)
+        _lib.check(lib.pgnn_edge_ws_applies(
+            rest.array, rest.n, int(rest.k_in), n_exp, st,
+            ctypes.byref(applies)), "pgnn_edge_ws_applies")
+        if not applies.value:
+            return form('plain')
+        scale_k = edge.exp(edge_scope)
+        if scale_k is None:
+            return form('plain', calibrate=cnt_k is None)
+        # ... and EDGE_K300's order of the last K group, for this kernel alone
+        k300 = edge.k300 and EDGE_INPUT_TAP is None and rest.k_in == 300
+
+        def build_scaled():
+            fcs = store.mlp(edge_scope, len(widths))
+            w1, b1 = fcs[0]
+            s = np.float32(2.0 ** -scale_k)
+            if k300:
+                w1, b1 = edge_k300_columns(w1), edge_k300_columns(b1)
+            wx = np.zeros((3, padded_width(w1.shape[1])), np.float32)
+            wx[:, :w1.shape[1]] = w1[c:c + 3] * s
+            made = (Chain(store, [(w1 * s, b1 * s, w1.shape[1])]),
+                    torch.from_numpy(wx).to(store._dev()),
+                    Chain(store, [fcs[1] + (0,)], k300=True)
+                    if k300 else None)
+            # (other streams will read the images without an event)
+            torch.cuda.current_stream().synchronize()
+            return made
+        p_s, wx_s, rest_s = store.cached(
+            ('edge_scaled', edge_scope, widths, scale_k, k300), build_scaled)
+        return _EdgeForm('scaled', p_s, wx_s, rest_s or rest, scale_k, k300,
+                         None, False)
 
     def apply_regular(self, input_vertex_features, input_vertex_coordinates,
                       NOT_USED, edges, edge_MLP_depth_list=None,
@@ -992,46 +1131,10 @@ class GraphNetAutoCenter(object):
             raise NotImplementedError("edge MLP needs at least two layers")
         assert h.shape[1] >= c, "vertex features narrower than edge MLP input"
 
-        # scaled operands (EDGE_SCALED above): decided before the per-vertex
-        # stage, which writes them, by the launcher's own partition query
-        scale_k, calibrate = None, False
-        if store.edge_scaled and store.inference and rest.n == 1 and \
-                store.edge_arith == 'f32' and \
-                self._aggregation == _lib.AGG_MAX:
-            n_exp = int(e.shape[0])
-            if cnt_e is not None and 0 < cnt_e.hint < n_exp:
-                n_exp = cnt_e.hint
-            applies = ctypes.c_int32(0)
-            _lib.check(lib.pgnn_edge_ws_applies(
-                rest.array, rest.n, int(rest.k_in), n_exp, st,
-                ctypes.byref(applies)), "pgnn_edge_ws_applies")
-            if applies.value:
-                scale_k = store.edge_scale_exp(edge_scope)
-                calibrate = scale_k is None and cnt_k is None
-        # ... and EDGE_K300's order of the last K group, for this kernel alone
-        k300 = scale_k is not None and store.edge_k300 and \
-            EDGE_INPUT_TAP is None and rest.k_in == 300
-        rest_k = rest
-        if scale_k is not None:
-            def build_scaled():
-                fcs = store.mlp(edge_scope, len(edge_widths))
-                w1, b1 = fcs[0]
-                s = np.float32(2.0 ** -scale_k)
-                if k300:
-                    w1, b1 = edge_k300_columns(w1), edge_k300_columns(b1)
-                wx = np.zeros((3, padded_width(w1.shape[1])), np.float32)
-                wx[:, :w1.shape[1]] = w1[c:c + 3] * s
-                made = (Chain(store, [(w1 * s, b1 * s, w1.shape[1])]),
-                        torch.from_numpy(wx).to(store._dev()),
-                        Chain(store, [fcs[1] + (0,)], k300=True)
-                        if k300 else None)
-                # (other streams will read the images without an event)
-                torch.cuda.current_stream().synchronize()
-                return made
-            p_chain, wx_dev, rest_k = store.cached(
-                ('edge_scaled', edge_scope, tuple(edge_widths), scale_k, k300),
-                build_scaled)
-            rest_k = rest_k or rest
+        n_e = int(e.shape[0])
+        form = self._form(lib, store, edge_scope, tuple(edge_widths),
+                          (c, p_chain, wx_dev, rest), n_e, cnt_e, cnt_k, st)
+        p_chain, wx_dev = form.p_chain, form.wx
 
         # per vertex, one launch (gnn.py:341-356): [optional] coordinate offset
         # delta = MLP(h) (auto-registration), Q = (x + delta) @ W1[C:],
@@ -1081,49 +1184,51 @@ class GraphNetAutoCenter(object):
         else:
             _lib.check(lib.pgnn_vertex_pre_edge_fwd_dyn(
                 *pre_args, cnt_k.arg(), st), "pgnn_vertex_pre_edge_fwd_dyn")
-        if calibrate:
-            store.note_edge_range(edge_scope, p, q)
+        if form.calibrate:
+            store.edge.note_edge_range(edge_scope, p, q)
         if EDGE_INPUT_TAP is not None:   # measurement hook (bench.py)
             EDGE_INPUT_TAP.append((p, q))
         # per-edge: ReLU(P[src] - Q[dst]) -> remaining edge layers -> max
-        edge_args = (_lib.ptr(p), _lib.ptr(q), wq, int(rest.k_in), _lib.ptr(e),
-                     int(e.shape[0]), k, rest.array, rest.n,
-                     _edges_sorted_flag(edges) | 2, _lib.ptr(agg),
-                     agg.stride(0), _lib.ptr(_lib.sched_ws(h.device)))
-        done = False
-        if self._aggregation != _lib.AGG_MAX:
+        head = (_lib.ptr(p), _lib.ptr(q), wq, int(rest.k_in), _lib.ptr(e), n_e,
+                k)
+        order = _edges_sorted_flag(edges) | 2
+        out = (_lib.ptr(agg), agg.stride(0))
+        sched = _lib.ptr(_lib.sched_ws(h.device))
+        dyn = (cnt_e.arg(), cnt_k.arg()) if cnt_e is not None else (None, None)
+        plain_args = head + (rest.array, rest.n, order) + out + (sched,)
+        kind = form.kind
+        if kind == 'split':
+            # the matrix pipe's 16-bit formats ('bf16x3' / 'f16x2')
+            name = "pgnn_edge_mlp_scatter_max_%s_fwd" % store.edge.arith
+            status = (store.edge.status('range'),) \
+                if store.edge.arith == 'f16x2' else ()
+            rc = getattr(lib, name)(
+                *head, _lib.ptr(form.image), int(rest.n_out),
+                int(rest.array[0].relu_from), order, *out, *status, *dyn, st)
+            if rc == _lib.E_UNSUPPORTED:
+                kind = 'plain'   # fallback: the kernel does not apply here
+            else:
+                _lib.check(rc, name)
+        if kind == 'agg':
             # sum / mean: the entry zeroes `agg` itself (the lowest() the
             # per-vertex launch wrote is max's identity) and runs in fp32
             _aggregate(lib, "edge_mlp_scatter_agg",
-                       (rest.array, rest.n, int(rest.k_in)), edge_args,
-                       int(e.shape[0]), k, cnt_e, cnt_k, self._aggregation,
-                       h.device)
-            done = True
-        elif store.edge_arith != 'f32' and rest.n == 1:
-            done = self._edge_split(lib, store, edge_scope, edge_widths, p, q,
-                                    wq, rest, e, k, edges, agg, cnt_e, cnt_k,
-                                    st)
-        elif scale_k is not None:
+                       (rest.array, rest.n, int(rest.k_in)), plain_args, n_e,
+                       k, cnt_e, cnt_k, self._aggregation, h.device)
+        elif kind == 'scaled':
             # (p, q are scaled: the plain entry would be wrong from here on,
-            # and the query above was this entry's own decision)
-            flags = edge_args[9] | (_lib.EDGE_K300_ORDER if k300 else 0)
+            # and the query in _form was this entry's own decision)
             _lib.check(lib.pgnn_edge_mlp_scatter_max_scaled_fwd(
-                *(edge_args[:7] + (rest_k.array, rest_k.n, flags) +
-                  edge_args[10:]),
-                scale_k, store.edge_scale_status(edge_scope),
-                cnt_e.arg() if cnt_e is not None else None,
-                cnt_k.arg() if cnt_k is not None else None, st),
-                "pgnn_edge_mlp_scatter_max_scaled_fwd")
-            done = True
-        if done:
-            pass
-        elif cnt_k is None:
-            _lib.check(lib.pgnn_edge_mlp_scatter_max_fwd(*edge_args, st),
+                *head, form.rest.array, form.rest.n,
+                order | (_lib.EDGE_K300_ORDER if form.k300 else 0), *out,
+                sched, form.scale_k, store.edge.status('scale', edge_scope),
+                *dyn, st), "pgnn_edge_mlp_scatter_max_scaled_fwd")
+        elif kind == 'plain' and cnt_k is None:
+            _lib.check(lib.pgnn_edge_mlp_scatter_max_fwd(*plain_args, st),
                        "pgnn_edge_mlp_scatter_max_fwd")
-        else:
+        elif kind == 'plain':
             _lib.check(lib.pgnn_edge_mlp_scatter_max_fwd_dyn(
-                *edge_args, cnt_e.arg(), cnt_k.arg(), st),
-                "pgnn_edge_mlp_scatter_max_fwd_dyn")
+                *plain_args, *dyn, st), "pgnn_edge_mlp_scatter_max_fwd_dyn")
         if AGGREGATE_TAP is not None:
             AGGREGATE_TAP.append(agg)
         # update + residual, gnn.py:367-372
@@ -1137,45 +1242,6 @@ class GraphNetAutoCenter(object):
             h = hp
         return _finish_rows(upd_chain, agg, rest.n_out, residual=h,
                             count=cnt_k)
-
-
-    @staticmethod
-    def _edge_split(lib, store, edge_scope, edge_widths, p, q, wq, rest, e, k,
-                    edges, agg, cnt_e, cnt_k, st):
-        """The edge stage on the matrix pipe's 16-bit formats ('bf16x3' /
-        'f16x2'); False (nothing done) where the kernel does not apply."""
-        arith = store.edge_arith
-
-        def build():
-            w, b = store.mlp(edge_scope, len(edge_widths))[1]
-            w = np.ascontiguousarray(w, dtype=np.float32)
-            b = np.ascontiguousarray(b, dtype=np.float32)
-            nbytes = getattr(lib, "pgnn_packed_fc_%s_bytes" % arith)(*w.shape)
-            host = np.empty(nbytes, np.uint8)
-            name = "pgnn_pack_fc_%s" % arith
-            _lib.check(getattr(lib, name)(
-                w.ctypes.data, b.ctypes.data, w.shape[0], w.shape[1],
-                host.ctypes.data), name)
-            return torch.from_numpy(host).to(store._dev())
-        image = store.cached(('edge_' + arith, edge_scope, tuple(edge_widths)),
-                             build)
-        head = (_lib.ptr(p), _lib.ptr(q), wq, int(rest.k_in), _lib.ptr(e),
-                int(e.shape[0]), k, _lib.ptr(image), int(rest.n_out),
-                int(rest.array[0].relu_from), _edges_sorted_flag(edges) | 2,
-                _lib.ptr(agg), agg.stride(0))
-        tail = (cnt_e.arg() if cnt_e is not None else None,
-                cnt_k.arg() if cnt_k is not None else None, st)
-        if arith == 'bf16x3':
-            name = "pgnn_edge_mlp_scatter_max_bf16x3_fwd"
-            rc = lib.pgnn_edge_mlp_scatter_max_bf16x3_fwd(*(head + tail))
-        else:
-            name = "pgnn_edge_mlp_scatter_max_f16x2_fwd"
-            rc = lib.pgnn_edge_mlp_scatter_max_f16x2_fwd(
-                *(head + (_lib.ptr(store.range_status()),) + tail))
-        if rc == _lib.E_UNSUPPORTED:
-            return False
-        _lib.check(rc, name)
-        return True
 
 
 class ClassAwarePredictor(object):

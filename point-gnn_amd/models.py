@@ -140,101 +140,60 @@ class MultiLayerFastLocalGraphModelV2(object):
         assert mode in ['train', 'eval', 'test'], 'Unsupported mode'
         self._mode = mode
         self._store = None
-        self._edge_arith = 'f32'
+        # how the edge stage runs: settings, calibration and the guard's flags
+        # (gnn.EdgePath); the three properties below are views of it.  Not
+        # part of the reference's surface.
+        self.edge = gnn.EdgePath(scaled=True)
 
     @property
     def edge_arith(self):
         """Arithmetic of the per-edge product of the GraphNetAutoCenter layers
         (gnn.EDGE_ARITHS): 'f32' (default, the parity reference) or the
-        secondary 'bf16x3'.  Not part of the reference's surface."""
-        return self._edge_arith
+        secondary 'bf16x3' / 'f16x2'."""
+        return self.edge.arith
 
     @edge_arith.setter
     def edge_arith(self, value):
-        if value not in gnn.EDGE_ARITHS:
-            raise ValueError("edge_arith must be one of %r, not %r"
-                             % (gnn.EDGE_ARITHS, value))
-        self._edge_arith = value
-        if self._store is not None:
-            self._store.edge_arith = value
-
-    def edge_range_ok(self):
-        """edge_arith 'f16x2' only: False when an activation of a frame since
-        the last call reached 32768 (fp16 ends at 65504; the kernel clamps) --
-        such a frame's results are unreliable, rerun it with edge_arith 'f32'.
-        One small device-to-host read; always True for the other arithmetics."""
-        return self._store is None or self._store.edge_range_ok()
+        self.edge.arith = value
 
     @property
     def edge_scaled(self):
         """Scaled operands of the fp32 edge stage (gnn.EDGE_SCALE_HEADROOM and
-        the comment above it): on by default, same results bit for bit.  Not
-        part of the reference's surface."""
-        return getattr(self, '_edge_scaled', True)
+        the comment above it): on by default, same results bit for bit."""
+        return self.edge.scaled
 
     @edge_scaled.setter
     def edge_scaled(self, value):
-        self._edge_scaled = bool(value)
-        if self._store is not None:
-            self._store.edge_scaled = self._edge_scaled
+        self.edge.scaled = bool(value)
 
     @property
     def edge_k300(self):
         """The scaled edge stage of a 300-wide layer without the MFMA step of
         K = 300's padding (gnn.EDGE_K300 and the comment above it): same
-        results bit for bit.  Not part of the reference's surface."""
-        return getattr(self, '_edge_k300', gnn.EDGE_K300)
+        results bit for bit."""
+        return self.edge.k300
 
     @edge_k300.setter
     def edge_k300(self, value):
-        self._edge_k300 = bool(value)
-        if self._store is not None:
-            self._store.edge_k300 = self._edge_k300
+        self.edge.k300 = bool(value)
 
-    def edge_scale_begin_pass(self):
-        """Takes a row of guard flags for the forward pass about to be
-        enqueued (gnn.ParamStore.edge_scale_begin_pass) and returns it: ask
-        edge_scale_ok([row]) when the pass's results are taken."""
-        return 0 if self._store is None else \
-            self._store.edge_scale_begin_pass()
-
-    def edge_scale_ok(self, rows=None):
-        """False when a scaled edge kernel of the passes `rows` (None: any)
-        found an operand outside [-0.5, 0.5]: their results are unspecified,
-        rerun them with `edge_scaled` off (the tripped layers' exponents have
-        been raised by 2).  One small device-to-host read, none before the
-        first scaled launch."""
-        return self._store is None or self._store.edge_scale_ok(rows)
-
-    def edge_scale_flags(self):
-        """The guard flags as a device tensor [rows, layers] (or None), for a
-        caller that reads a row with a host copy of its own and hands the
-        values to edge_scale_tripped()."""
-        return None if self._store is None else self._store.edge_scale_flags()
-
-    def edge_scale_tripped(self, host, count=True):
-        """edge_scale_ok() on rows the caller has read ({row: values})."""
-        return self._store.edge_scale_tripped(host, count)
-
-    def edge_scale_discard(self, row):
-        """Clears a row unread: its pass's results are not used."""
-        if self._store is not None:
-            self._store.edge_scale_discard(row)
+    def edge_range_ok(self):
+        """edge_arith 'f16x2' only: False when an activation of a pass since
+        the last look reached 32768 (fp16 ends at 65504; the kernel clamps) --
+        such a frame's results are unreliable, rerun it with edge_arith 'f32'.
+        Reads and clears the range column of every row: one small
+        device-to-host read; always True for the other arithmetics."""
+        return not self.edge.read(kinds=('range',)).range
 
     def edge_scale_exps(self):
         """{layer scope: k} of the layers calibrated so far."""
-        if self._store is None:
-            return {}
-        return dict(self._store.__dict__.get('_edge_scale', {}))
+        return dict(self.edge.exps)
 
     # ---- weights ----------------------------------------------------------
     def load_state_dict(self, params, device=None):
         """params: {TF variable name: ndarray} (extra keys such as the
         global-step `Variable` are ignored)."""
-        self._store = gnn.ParamStore(params, device)
-        self._store.edge_arith = self._edge_arith
-        self._store.edge_scaled = self.edge_scaled
-        self._store.edge_k300 = self.edge_k300
+        self._store = gnn.ParamStore(params, device, self.edge)
         return self
 
     def init_weights(self, config, seed=0, **kw):
@@ -298,7 +257,7 @@ class MultiLayerFastLocalGraphModelV2(object):
         # per-vertex stages (the unfused reference form the tests compare with)
         fuse = getattr(self, 'fuse_vertex_stages', True)
         # (gnn.EDGE_SCALE_HEADROOM: the scaled edge stage is for inference)
-        self._store.inference = not is_training
+        self.edge.inference = not is_training
         with gnn.parameters(self._store), gnn.fuse_vertex_stages(fuse):
             feats = t_initial_vertex_features
             *body, head = self._layer_configs

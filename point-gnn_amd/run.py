@@ -88,29 +88,18 @@ def detect_frame(dataset, frame_idx, model, config, use_box_merge=True,
     coords, kps, edges = fn(points.xyz, **config['runtime_graph_gen_kwargs'])
     t = lap('gen graph', t)
     input_v = _input_features(config, points)
-    scale_row = model.edge_scale_begin_pass()
+    row = model.edge.take_row()
     logits, box_encodings = model.predict(input_v, coords, kps, edges, False)
-    if model.edge_arith == 'f16x2' and not model.edge_range_ok():
-        # an activation left fp16's safe range (gnn.EDGE_ARITHS): this frame
-        # in fp32 (the results are read below anyway: no extra wait)
-        td['f16x2 range reruns'] = td.get('f16x2 range reruns', 0) + 1
-        model.edge_arith = 'f32'
-        try:
+    # the guard of the edge stage's fast forms (gnn.EdgePath), read with the
+    # results (they are read below anyway: no extra wait): under 'f16x2' an
+    # activation left fp16's safe range, or an operand left the scaled stage's
+    verdict = model.edge.read([row])
+    if verdict.range or verdict.scale:
+        key = 'f16x2 range reruns' if verdict.range else 'edge scale reruns'
+        td[key] = td.get(key, 0) + 1
+        with model.edge.plain():     # this frame in fp32, with the plain kernel
             logits, box_encodings = model.predict(input_v, coords, kps, edges,
                                                   False)
-        finally:
-            model.edge_arith = 'f16x2'
-    if not model.edge_scale_ok([scale_row]):
-        # the scaled edge stage's guard (gnn.EDGE_SCALE_HEADROOM): this frame
-        # with the plain kernel
-        td['edge scale reruns'] = td.get('edge scale reruns', 0) + 1
-        was = model.edge_scaled
-        model.edge_scaled = False
-        try:
-            logits, box_encodings = model.predict(input_v, coords, kps, edges,
-                                                  False)
-        finally:
-            model.edge_scaled = was
     probs = model.postprocess(logits)
     t = lap('gnn inference', t)
     label_map = kitti_output.LABEL_MAPS[config['label_method']]
@@ -221,7 +210,7 @@ class _Frame(object):
     """One frame on its way through FramePipeline."""
     __slots__ = ("idx", "points", "calib", "stream", "ev", "graph", "probs",
                  "box_enc", "cand", "host_a", "n_rec", "host_b", "n_cand",
-                 "rerun", "t_fetch", "scale_row")
+                 "rerun", "t_fetch", "row")
 
 
 class FramePipeline(object):
@@ -300,7 +289,7 @@ class FramePipeline(object):
                 **cfg['runtime_graph_gen_kwargs'])
             ev[1].record()
             coords, kps, edges = graph
-            f.scale_row = model.edge_scale_begin_pass()
+            f.row = model.edge.take_row()
             logits, box_enc = model.predict(_input_features(cfg, f.points),
                                             coords, kps, edges, False)
             probs = model.postprocess(logits)
@@ -308,11 +297,11 @@ class FramePipeline(object):
             frame = edges[0]._pgnn_count.frame
             cand = nms.select_candidates_dyn(probs, frame.tensor[0:1])
             n_rec = int(frame.tensor.numel())
-            # (behind them this pass's row of the scaled edge kernels' flags,
-            # in the same read)
-            flags = model.edge_scale_flags()
+            # (behind them this pass's row of the edge stage's guard flags,
+            # the 'f16x2' range flag among them, in the same read)
+            flags = model.edge.flags
             if flags is not None:
-                flags = flags[f.scale_row]
+                flags = flags[f.row]
             n_fl = 0 if flags is None else int(flags.numel())
             host = torch.empty(n_rec + 1 + n_fl, dtype=torch.int32,
                                pin_memory=True)
@@ -336,20 +325,18 @@ class FramePipeline(object):
         self.hints = self.hints.update(k, frame.edges)
         self._add('gen graph', f.ev[0].elapsed_time(f.ev[1]) * 1e-3)
         self._add('gnn inference', f.ev[1].elapsed_time(f.ev[2]) * 1e-3)
-        if frame.overflowed:
-            f.rerun = True
-        if self.model.edge_arith == 'f16x2' and not self.model.edge_range_ok():
-            # the flag is the model's, not the frame's: every frame whose GNN
-            # may have run since the last look goes through the fp32 path
+        # the pass's flags (gnn.EdgePath) are this frame's alone: a frame that
+        # left fp16's range or the scaled stage's goes through the plain path
+        # (stage C); so does one that overflowed a capacity, and its flags
+        # mean nothing
+        verdict = self.model.edge.verdict({f.row: rec[f.n_rec + 1:]},
+                                          count=not frame.overflowed)
+        f.rerun = bool(frame.overflowed)
+        if verdict.range:
             self.td['f16x2 range reruns'] = \
                 self.td.get('f16x2 range reruns', 0) + 1
             f.rerun = True
-            for g in self._in_a:
-                g.rerun = True
-        if any(rec[f.n_rec + 1:]) and not self.model.edge_scale_tripped(
-                {f.scale_row: rec[f.n_rec + 1:]}, count=not f.rerun):
-            # likewise the scaled edge stage's guard, whose flags are this
-            # pass's: the frame with the plain kernel (stage C)
+        if verdict.scale:
             if not f.rerun:
                 self.td['edge scale reruns'] = \
                     self.td.get('edge scale reruns', 0) + 1
@@ -391,20 +378,12 @@ class FramePipeline(object):
     def _stage_c(self, f, writer):
         if f.rerun:
             self.fallbacks += 1
-            edge_arith = self.model.edge_arith
-            self.model.edge_arith = 'f32' if edge_arith == 'f16x2' \
-                else edge_arith
-            edge_scaled = self.model.edge_scaled
-            self.model.edge_scaled = False
-            try:
+            with self.model.edge.plain():
                 _frame_sequential(self.dataset, f.idx, self.model, self.config,
                                   self.output_dir, self.use_box_merge,
                                   self.use_box_score, self.td,
                                   self.image_reader, self.log,
                                   self.write_alpha)
-            finally:
-                self.model.edge_arith = edge_arith
-                self.model.edge_scaled = edge_scaled
             return
         f.ev[1].synchronize()
         self._add('decode box + nms', f.ev[0].elapsed_time(f.ev[1]) * 1e-3)
@@ -498,7 +477,7 @@ class FramePipeline(object):
                    threading.Thread(target=writer, daemon=True)]
         for t in threads:
             t.start()
-        self._in_a = deque()
+        in_a = deque()
         in_b = deque()
         try:
             for i in range(len(rest)):
@@ -506,17 +485,17 @@ class FramePipeline(object):
                 if isinstance(f, BaseException):
                     raise f
                 self._stage_a(f, compute[i % len(compute)])
-                self._in_a.append(f)
-                if len(self._in_a) > self.in_flight:
-                    g = self._in_a.popleft()
+                in_a.append(f)
+                if len(in_a) > self.in_flight:
+                    g = in_a.popleft()
                     self._stage_b(g)
                     in_b.append(g)
                 if len(in_b) > self.in_flight:
                     self._stage_c(in_b.popleft(), to_write)
                 if failure:
                     raise failure[0]
-            while self._in_a:
-                g = self._in_a.popleft()
+            while in_a:
+                g = in_a.popleft()
                 self._stage_b(g)
                 in_b.append(g)
             while in_b:

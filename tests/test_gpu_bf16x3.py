@@ -413,3 +413,44 @@ def test_engine_reruns_a_flagged_f16x2_batch_in_fp32(dev):
                          device=dev, edge_arith="f16x2")
     ok.run_frames_on_streams(frames, 2)
     assert getattr(ok, "f16x2_batch_reruns", 0) == 0
+
+
+def test_f16x2_range_flag_is_the_pass_s_own(dev):
+    """Two frames in flight on one 'f16x2' engine, B's intensity times 1e6 so
+    that B alone leaves fp16's range: the range flag is raised in B's row of
+    the guard's table (gnn.EdgePath) and not in A's, and A's results are those
+    of A run alone.  Measured for this input under the plain 'f32' engine:
+    max|P| of the graph layer is 6.78 as generated and 61734 at the factor
+    1e6 (max|Q| 7264), above the guard's 32768."""
+    import torch
+    from pointgnn_amd import _lib, configs, weights
+    from pointgnn_amd.engine import InferenceEngine
+    from pointgnn_amd.synthetic import synthetic_cloud
+    cfg = configs.car_auto_config(1)
+    params = weights.init_params(cfg, seed=4, bias_scale=0.05)
+    xyz, inten = synthetic_cloud(seed=0, preset="small")
+    a = (T(xyz, dev), T(inten, dev))
+    b = (T(xyz, dev), T(inten * np.float32(1e6), dev))
+    _lib.set_tunable("b16_force", 1)
+    try:
+        eng = InferenceEngine(cfg, params, device=dev, edge_arith="f16x2")
+        eng.run_frame(*a)                      # size hints
+        fa = eng.run_frame_deferred(*a)
+        fb = eng.run_frame_deferred(*b)
+        assert fa.row != fb.row
+        torch.cuda.synchronize()
+        edge = eng.model.edge
+        for_b = edge.read([fb.row])
+        for_a = edge.read([fa.row])
+        print("verdicts: B", for_b, "A", for_a)
+        assert for_b.range and not for_b.scale
+        assert not for_a.range and not for_a.scale
+        logits, boxes = fa.result()
+        fb.result()
+        assert eng.deferred_overflows == 0
+        alone = InferenceEngine(cfg, params, device=dev, edge_arith="f16x2")
+        want_l, want_b = alone.run_frame(*a)
+        alone.check_edge_range()
+        assert torch.equal(logits, want_l) and torch.equal(boxes, want_b)
+    finally:
+        _lib.set_tunable("b16_force", 0)

@@ -177,7 +177,8 @@ def test_frame_loop_with_the_f16x2_arithmetic(tmp_path):
                 np.array([r[4:] for r in rows32], np.float64), rtol=2e-3,
                 atol=2e-3)
         # a frame flagged by the range guard: rerun in fp32, model unchanged
-        m16.edge_range_ok = lambda: False
+        from pointgnn_amd import gnn
+        m16.edge.read = lambda rows=None, **kw: gnn.EdgeVerdict(True, False)
         td = {}
         _, st = RUN.detect_frame(ds, 0, m16, cfg, time_dict=td)
         assert td['f16x2 range reruns'] == 1 and m16.edge_arith == "f16x2"

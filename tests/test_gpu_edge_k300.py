@@ -401,7 +401,7 @@ def test_engine_reruns_a_batch_whose_guard_tripped(dev):
         assert eng.edge_scale_reruns == 0 and len(exps) == 1
         assert len(k300_images(eng)) == 1
         for scope, k in exps.items():
-            eng.model._store._edge_scale[scope] = k - 6
+            eng.model.edge.exps[scope] = k - 6
         same_bytes(want, eng.run_frames_on_streams(frames, 2))
         assert eng.edge_scale_reruns == 1 and eng.model.edge_k300
         assert eng.model.edge_scale_exps() == {s: k - 4

@@ -341,10 +341,10 @@ def test_engine_same_bytes_scaled_and_plain(dev):
     exps = on.model.edge_scale_exps()
     print("calibrated exponents:", exps)
     assert len(exps) == 2 and all(0 <= k <= 24 for k in exps.values())
-    assert on.model.edge_scale_flags() is not None      # scaled kernels ran
+    assert on.model.edge.flags is not None      # scaled kernels ran
     assert on.edge_scale_reruns == 0
     assert off.model.edge_scale_exps() == {} and \
-        off.model.edge_scale_flags() is None
+        off.model.edge.flags is None
 
 
 def test_engine_reruns_a_batch_whose_guard_tripped(dev):
@@ -370,7 +370,7 @@ def test_engine_reruns_a_batch_whose_guard_tripped(dev):
         assert eng.edge_scale_reruns == 0 and len(exps) == 1
         assert all(k >= 6 for k in exps.values()), exps
         for scope, k in exps.items():
-            eng.model._store._edge_scale[scope] = k - 6
+            eng.model.edge.exps[scope] = k - 6
         shapes = len(eng.frame_shapes)
         got = eng.run_frames_on_streams(frames, 2)
         same_bytes(want, got)
