@@ -13,7 +13,8 @@ TF towers:
 Every arithmetic step runs in a HIP kernel behind the C ABI; torch is used for
 allocation, views/concatenation and the three residual-style tensor adds of the
 backward pass.  The inference path never materialises E x C activations; the
-training forward does (the backward needs them).
+training forward does (the backward needs them).  Forward and backward
+themselves run on one of the two step engines of train_step.py.
 
 Weights live in ONE flat device buffer (reference variable order, [in,out]
 layouts); gradients in a second one, so data-parallel synchronisation is a
@@ -25,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .gnn import padded_width
+from .train_step import ComposedStep, NativeStep, StepSelector
 from .weights import init_params, mlp_names, variable_specs
 
 __all__ = ["Trainer", "batch_data", "learning_rate", "fetch_data",
@@ -626,7 +627,9 @@ def check_trainable_kinds(config):
                     "%s: %s = %r has no training path" % (lc['scope'], key, val))
 
 
-class Trainer(object):
+class Trainer(StepSelector):
+    """Parameters, optimizer, loss and one training step; forward, backward
+    and repack (StepSelector's) run on a step engine of train_step.py."""
     def __init__(self, config, train_config=None, params=None, seed=0,
                  device=None, box_encoding_len=7, process_group=None,
                  comm=None, force_collective=False):
@@ -764,13 +767,8 @@ class Trainer(object):
                                 self._view(self.flat, base + '/biases'),
                                 self._view(self.grad, name),
                                 self._view(self.grad, base + '/biases'))
-        self._ws = None
-        self._ws2 = None
-        self._pack_jobs = None
-        # The step runs natively by default (csrc/trainer.hip: forward and
-        # backward are one C call each, all launches issued from C++);
-        # native = False drives the same primitives from Python (the readable
-        # composition below; tests hold the two to the same gradients).
+        # The step runs natively by default (train_step.NativeStep); native =
+        # False drives the same primitives from Python (ComposedStep).
         self.native = True
         n_pool = sum(lc['type'] == 'scatter_max_point_set_pooling'
                      for lc in config['model_kwargs']['layer_configs'])
@@ -779,11 +777,21 @@ class Trainer(object):
             # config); a second one (models.py:119-149 is generic) trains
             # through the Python-driven composition of the same primitives
             self.native = False
-        self._native = None
-        self._native_ws = None
-        self._py_images_stale = True
-        self._native_images_stale = False
+        self._native_step = None     # created by the first native forward
+        self._composed_step = ComposedStep(self)
+        self._saved = None
         self.repack()
+
+    def _create_native_step(self):
+        return NativeStep.create(self)
+
+    def __del__(self):
+        eng = getattr(self, '_native_step', None)
+        if eng is not None:
+            try:
+                eng.destroy()
+            except Exception:
+                pass
 
     # ---- plumbing -----------------------------------------------------------
     def _view(self, flat, name):
@@ -921,527 +929,6 @@ class Trainer(object):
     def _st(self):
         return _lib.stream_ptr()
 
-    def _sparse_layers(self):
-        """Names of the layers whose output feeds a scatter-max (the last
-        per-edge layer of every pooling / GNN stage): their adjoint runs
-        sparse (pgnn_segmax_fc_bwd_f32) and needs a plain W^T image."""
-        out = []
-        for lc in self.config['model_kwargs']['layer_configs'][:-1]:
-            kw = lc['kwargs']
-            if lc['type'] == 'scatter_max_point_set_pooling':
-                n = len(kw['point_MLP_depth_list'])
-            elif lc['type'] == 'scatter_max_graph_auto_center_net':
-                n = len(kw['edge_MLP_depth_list'])
-            else:
-                continue
-            if n >= 2:   # the layer needs a materialised input activation
-                out.append(mlp_names(
-                    lc['scope'] + '/extract_vertex_features', n)[-1])
-        return out
-
-    def _build_pack_jobs(self):
-        """Device table of pgnn_pack_fc_many: the fragment images (forward,
-        transposed) of every layer, the W^T rows of the Wx block of each first
-        edge layer (dx' = dQ Wx^T), plain W^T of the sparse-adjoint layers."""
-        lib = self.lib
-        sparse = set(self._sparse_layers())
-        jobs = []
-
-        def add(w_ptr, b_ptr, dst, k_in, n_out, kind):
-            if kind == 2:
-                elems = n_out * padded_width(k_in)
-            elif kind == 1:
-                elems = lib.pgnn_packed_fc_floats(n_out, k_in)
-            else:
-                elems = lib.pgnn_packed_fc_floats(k_in, n_out)
-            jobs.append((w_ptr, b_ptr, dst.data_ptr(), k_in, n_out, kind,
-                         (int(elems) + 255) // 256))
-        for fc in self.fc.values():
-            fc.packed = torch.empty(
-                lib.pgnn_packed_fc_floats(fc.k_in, fc.n_out),
-                dtype=torch.float32, device=self.device)
-            fc.packed_t = torch.empty(
-                lib.pgnn_packed_fc_floats(fc.n_out, fc.k_in),
-                dtype=torch.float32, device=self.device)
-            add(fc.w.data_ptr(), fc.b.data_ptr(), fc.packed, fc.k_in,
-                fc.n_out, 0)
-            add(fc.w.data_ptr(), 0, fc.packed_t, fc.k_in, fc.n_out, 1)
-            if fc.name in sparse:
-                fc.wt = torch.empty((fc.n_out, padded_width(fc.k_in)),
-                                    dtype=torch.float32, device=self.device)
-                add(fc.w.data_ptr(), 0, fc.wt, fc.k_in, fc.n_out, 2)
-        # Wx = rows c..c+2 of every first edge layer, transposed image
-        self.wx_packed_t = {}
-        for lc in self.config['model_kwargs']['layer_configs'][:-1]:
-            if lc['type'] != 'scatter_max_graph_auto_center_net':
-                continue
-            name = mlp_names(lc['scope'] + '/extract_vertex_features', 1)[0]
-            w1 = self.fc[name]
-            c = w1.k_in - 3
-            pk = torch.empty(lib.pgnn_packed_fc_floats(w1.n_out, 3),
-                             dtype=torch.float32, device=self.device)
-            add(w1.w.data_ptr() + 4 * c * w1.n_out, 0, pk, 3, w1.n_out, 1)
-            self.wx_packed_t[name] = pk
-        arr = (_lib.PackJob * len(jobs))()
-        first = 0
-        for i, (w, b, dst, k, n, kind, blocks) in enumerate(jobs):
-            arr[i].w, arr[i].b, arr[i].dst = w, b or None, dst
-            arr[i].k_in, arr[i].n_out, arr[i].kind = int(k), int(n), int(kind)
-            arr[i].first_block = first
-            first += blocks
-        raw = np.frombuffer(bytes(arr), dtype=np.uint8).copy()
-        self._pack_jobs = torch.from_numpy(raw).to(self.device)
-        self._pack_n, self._pack_blocks = len(jobs), first
-
-    def repack(self):
-        """Refresh every device image derived from the flat buffer (MFMA
-        fragment images forward / transposed, plain W^T of the sparse-adjoint
-        layers) -- after init and after every SGD step: ONE launch.  Only the
-        images of the path in use are refreshed (native step: the handle's;
-        Python-driven step: this object's, lazily)."""
-        if self.native and self.sparse_adjoint:
-            self._py_images_stale = True
-            if self._native is not None:
-                _lib.check(self.lib.pgnn_trainer_repack(self._native,
-                                                        self._st()),
-                           "pgnn_trainer_repack")
-            # (a handle created later packs in pgnn_trainer_bind)
-            self._native_images_stale = False
-            return
-        # Python-driven step: the native handle's images (if one exists) are
-        # now behind the flat buffer; _native_forward repacks before reuse
-        self._native_images_stale = self._native is not None
-        self._repack_py()
-
-    def _repack_py(self):
-        if getattr(self, '_pack_jobs', None) is None:
-            self._build_pack_jobs()
-        _lib.check(self.lib.pgnn_pack_fc_many(
-            _lib.ptr(self._pack_jobs), self._pack_n, self._pack_blocks,
-            self._st()), "pgnn_pack_fc_many")
-        self._py_images_stale = False
-
-    def _layer_array(self, packed, k_in, n_out, relu):
-        arr = (_lib.FcLayer * 1)()
-        arr[0].packed = packed.data_ptr()
-        arr[0].k_in, arr[0].n_out = int(k_in), int(n_out)
-        arr[0].relu_from = 0 if relu else int(n_out)
-        return arr
-
-    def _mlp1(self, packed, k_in, n_out, relu, x, nx, x2=None, nx2=0,
-              residual=None):
-        rows = int(x.shape[0])
-        y = torch.empty((rows, padded_width(n_out)), dtype=torch.float32,
-                        device=self.device)
-        arr = self._layer_array(packed, k_in, n_out, relu)
-        _lib.check(self.lib.pgnn_mlp_fwd(
-            _lib.ptr(x), x.stride(0), int(nx), _lib.ptr(x2),
-            x2.stride(0) if x2 is not None else 0, int(nx2), rows, arr, 1,
-            _lib.ptr(residual),
-            residual.stride(0) if residual is not None else 0, _lib.ptr(y),
-            y.stride(0), self._st()), "pgnn_mlp_fwd")
-        return y
-
-    def fc_fwd(self, name, x, relu, x2=None, nx2=0, residual=None):
-        fc = self.fc[name]
-        return self._mlp1(fc.packed, fc.k_in, fc.n_out, relu, x,
-                          fc.k_in - nx2, x2, nx2, residual)
-
-    def _weight_grad(self, x, ld_x, k_in, dz, n_out, gw_ptr, gb_ptr):
-        rows = int(dz.shape[0])
-        need = self.lib.pgnn_weight_grad_workspace_bytes(k_in, n_out, rows)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(int(need), dtype=torch.uint8,
-                                   device=self.device)
-        _lib.check(self.lib.pgnn_weight_grad_f32(
-            _lib.ptr(x), ld_x, k_in, _lib.ptr(dz), dz.stride(0), n_out, rows,
-            gw_ptr, gb_ptr, 1, _lib.ptr(self._ws), self._ws.numel(),
-            self._st()), "pgnn_weight_grad_f32")
-
-    def fc_bwd(self, name, x, y, dy, relu, need_dx=True):
-        """dy is consumed (masked in place when relu).  x: the saved input
-        [rows, >= k_in] (already concatenated for two-input layers)."""
-        fc = self.fc[name]
-        if relu:
-            _lib.check(self.lib.pgnn_relu_mask_mul(
-                _lib.ptr(dy), _lib.ptr(y), dy.numel(), self._st()),
-                "pgnn_relu_mask_mul")
-        self._weight_grad(x, x.stride(0), fc.k_in, dy, fc.n_out,
-                          _lib.ptr(fc.gw), _lib.ptr(fc.gb))
-        if not need_dx:
-            return None
-        return self._mlp1(fc.packed_t, fc.n_out, fc.k_in, False, dy, fc.n_out)
-
-    def _scatter_max(self, data, dst, k):
-        out = torch.empty((k, data.shape[1]), dtype=torch.float32,
-                          device=self.device)
-        _lib.check(self.lib.pgnn_scatter_max_f32(
-            _lib.ptr(data), data.stride(0), _lib.ptr(dst), int(data.shape[0]),
-            int(data.shape[1]), k, _lib.ptr(out), out.stride(0),
-            int(getattr(dst, "_pgnn_sorted", 0)), self._st()),
-            "pgnn_scatter_max_f32")
-        return out
-
-    def _scatter_max_bwd(self, data, dst, out, gout):
-        """Dense adjoint of out = scatter_max(data) for `data` that left a
-        ReLU: relu_mask = 1 whatever the order of the ids (rows tied at a
-        maximum of exactly 0 get nothing, TF's ReluGrad; both callers hand
-        the result to fc_bwd(..., relu=False) as dZ)."""
-        k, cols = int(out.shape[0]), int(data.shape[1])
-        ties = torch.empty(k * cols, dtype=torch.int32, device=self.device)
-        gdata = torch.empty_like(data)
-        _lib.check(self.lib.pgnn_scatter_max_bwd_f32(
-            _lib.ptr(data), data.stride(0), _lib.ptr(dst), int(data.shape[0]),
-            cols, k, _lib.ptr(out), out.stride(0), _lib.ptr(gout),
-            gout.stride(0), _lib.ptr(ties), _lib.ptr(gdata), gdata.stride(0),
-            1, self._st()), "pgnn_scatter_max_bwd_f32")
-        return gdata
-
-    def _segmax_fc_bwd(self, name, y, dst, out, gout, x, need_dx=True,
-                       mask_x=True):
-        """Adjoint of out = scatter_max(y), y = ReLU(x W + b) for layer `name`
-        (pgnn_segmax_fc_bwd_f32): accumulates dW / db, returns dX (masked by
-        x > 0) or None."""
-        fc = self.fc[name]
-        rows, k = int(y.shape[0]), int(out.shape[0])
-        need = self.lib.pgnn_segmax_fc_bwd_workspace_bytes(rows, fc.n_out, k,
-                                                           fc.k_in)
-        if self._ws2 is None or self._ws2.numel() < need:
-            self._ws2 = torch.empty(int(need), dtype=torch.uint8,
-                                    device=self.device)
-        dx = None
-        if need_dx:
-            dx = torch.empty((rows, int(x.shape[1])), dtype=torch.float32,
-                             device=self.device)
-        _lib.check(self.lib.pgnn_segmax_fc_bwd_f32(
-            _lib.ptr(y), y.stride(0), _lib.ptr(dst), rows, fc.n_out, k,
-            _lib.ptr(out), out.stride(0), _lib.ptr(gout), gout.stride(0),
-            _lib.ptr(x), x.stride(0), fc.k_in, _lib.ptr(fc.wt),
-            fc.wt.stride(0), _lib.ptr(dx),
-            dx.stride(0) if dx is not None else 0,
-            int(x.shape[1]) if dx is not None else 0, 1 if mask_x else 0,
-            _lib.ptr(fc.gw), _lib.ptr(fc.gb), _lib.ptr(self._ws2),
-            self._ws2.numel(), self._st()), "pgnn_segmax_fc_bwd_f32")
-        return dx
-
-    @staticmethod
-    def _sorted_dst(edges):
-        """dst column, tagged with whether the list is grouped by ascending
-        dst: graph_gen / batch_data lists are (tagged there), a foreign list is
-        checked once (gnn._edges_sorted_flag) and takes the all-atomic path of
-        the scatter-max kernels when it is not."""
-        from . import gnn
-        d = edges[:, 1].contiguous()
-        d._pgnn_sorted = int(gnn._edges_sorted_flag(edges))
-        return d
-
-    # ---- native step (csrc/trainer.hip) -----------------------------------------------
-    def _fc_ref(self, dst, name):
-        off_w, (k, n) = self.offsets[name + '/weights']
-        off_b, _ = self.offsets[name + '/biases']
-        dst.w_off, dst.b_off, dst.k_in, dst.n_out = off_w, off_b, int(k), int(n)
-
-    def _native_handle(self):
-        """pgnn_trainer_create + bind for this model (once)."""
-        if self._native is not None:
-            return self._native
-        lib = self.lib
-        m = _lib.TrainModel()
-        lcs = self.config['model_kwargs']['layer_configs']
-        m.n_stages = len(lcs) - 1
-        m.num_classes, m.box_len = self.nc, self.box_len
-        m.n_params = int(self.flat.numel())
-        for si, lc in enumerate(lcs[:-1]):
-            st, kw, scope = m.stages[si], lc['kwargs'], lc['scope']
-            st.graph_level = int(lc['graph_level'])
-            if lc['type'] == 'scatter_max_point_set_pooling':
-                st.kind = 0
-                a = mlp_names(scope + '/extract_vertex_features',
-                              len(kw['point_MLP_depth_list']))
-                b = mlp_names(scope + '/combined_features',
-                              len(kw['output_MLP_depth_list']))
-                c = []
-            elif lc['type'] == 'scatter_max_graph_auto_center_net':
-                st.kind = 1
-                a = mlp_names(scope + '/extract_vertex_features',
-                              len(kw['edge_MLP_depth_list']))
-                b = mlp_names(scope + '/combined_features',
-                              len(kw['update_MLP_depth_list']))
-                c = mlp_names(scope, len(kw['auto_offset_MLP_depth_list'])) \
-                    if kw['auto_offset'] else []
-            else:
-                raise NotImplementedError(lc['type'])
-            st.n_a, st.n_b, st.n_c = len(a), len(b), len(c)
-            for arr, names in ((st.a, a), (st.b, b), (st.c, c)):
-                for i, n in enumerate(names):
-                    self._fc_ref(arr[i], n)
-        pc = lcs[-1]
-        m.loc_split = int(self._head_slice is not None)
-        ps = pc['scope'] + '/predictor'
-        for i, n in enumerate(mlp_names(ps + '/cls', 2)):
-            self._fc_ref(m.cls[i], n)
-        for j in range(self.nc):
-            for i, n in enumerate(mlp_names(ps + '/loc/cls_%d' % j, 3)):
-                self._fc_ref(m.loc[j][i], n)
-        h = ctypes.c_void_p()
-        rc = lib.pgnn_trainer_create(ctypes.byref(m), ctypes.byref(h))
-        if rc == _lib.E_UNSUPPORTED:
-            # layer shapes outside what csrc/trainer.hip orchestrates: the
-            # Python-driven composition of the same primitives takes over
-            import warnings
-            warnings.warn("native training step unavailable for this model "
-                          "(%s); using the Python-driven step" % (
-                              (lib.pgnn_last_error() or b'?').decode(),),
-                          RuntimeWarning)
-            self.native = False
-            return None
-        _lib.check(rc, "pgnn_trainer_create")
-        self._native_images = torch.empty(
-            int(lib.pgnn_trainer_images_bytes(h)), dtype=torch.uint8,
-            device=self.device)
-        _lib.check(lib.pgnn_trainer_bind(
-            h, _lib.ptr(self.flat), _lib.ptr(self.grad),
-            _lib.ptr(self._native_images), self._native_images.numel(),
-            self._st()), "pgnn_trainer_bind")
-        self._native = h
-        return h
-
-    def __del__(self):
-        h, self._native = getattr(self, '_native', None), None
-        if h is not None:
-            try:
-                self.lib.pgnn_trainer_destroy(h)
-            except Exception:
-                pass
-
-    def _native_batch(self, input_v, coords, kps, edges):
-        """pgnn_train_batch for these tensors (kept alive by the caller)."""
-        dev = self.device
-        f32 = lambda t: torch.as_tensor(t).to(
-            device=dev, dtype=torch.float32).contiguous()
-        i32 = lambda t: torch.as_tensor(t).to(
-            device=dev, dtype=torch.int32).contiguous()
-        input_v = f32(input_v)
-        coords = [f32(c) for c in coords]
-        kps = [i32(torch.as_tensor(k).reshape(-1)) for k in kps]
-        from . import gnn
-        flags = [int(gnn._edges_sorted_flag(torch.as_tensor(e)))
-                 for e in edges]
-        edges = [i32(e) for e in edges]
-        b = _lib.TrainBatch()
-        b.input_v, b.n_feat = input_v.data_ptr(), int(input_v.shape[1])
-        b.n_levels = len(edges)
-        for l, c in enumerate(coords):
-            b.n_vertices[l], b.coords[l] = int(c.shape[0]), c.data_ptr()
-        for l in range(len(edges)):
-            b.keypoints[l] = kps[l].data_ptr()
-            b.edges[l], b.n_edges[l] = edges[l].data_ptr(), int(edges[l].shape[0])
-            b.edges_sorted[l] = flags[l]
-        return b, (input_v, coords, kps, edges)
-
-    def _native_forward(self, input_v, coords, kps, edges):
-        lib = self.lib
-        h = self._native_handle()
-        if h is None:     # unsupported shapes: Trainer.native was switched off
-            self._py_images_stale = True
-            return self.forward(input_v, coords, kps, edges)
-        if self._native_images_stale:
-            # weights were updated while native = False (repack() refreshed
-            # only the Python-side images then)
-            _lib.check(lib.pgnn_trainer_repack(h, self._st()),
-                       "pgnn_trainer_repack")
-            self._native_images_stale = False
-        batch, keep = self._native_batch(input_v, coords, kps, edges)
-        need = int(lib.pgnn_trainer_workspace_bytes(h, ctypes.byref(batch)))
-        if need == 0:
-            raise _lib.PointGnnHipError("pgnn_trainer_workspace_bytes: %s" % (
-                (lib.pgnn_last_error() or b'?').decode()))
-        if self._native_ws is None or self._native_ws.numel() < need:
-            self._native_ws = torch.empty(
-                (int(need * 1.25) + 255) // 256 * 256, dtype=torch.uint8,
-                device=self.device)
-        lg, ld, pb = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_void_p()
-        _lib.check(lib.pgnn_trainer_forward(
-            h, ctypes.byref(batch), _lib.ptr(self._native_ws),
-            self._native_ws.numel(), ctypes.byref(lg), ctypes.byref(ld),
-            ctypes.byref(pb), self._st()), "pgnn_trainer_forward")
-        k = int(batch.n_vertices[batch.n_levels])
-        # views INTO the workspace (valid until the next forward)
-        base = self._native_ws.data_ptr()
-        flat = self._native_ws.view(torch.float32)
-        o_lg = (lg.value - base) // 4
-        o_pb = (pb.value - base) // 4
-        logits = flat[o_lg:o_lg + k * ld.value].view(k, ld.value)
-        pred = flat[o_pb:o_pb + k * self.nc * self.box_len].view(
-            k, self.nc, self.box_len)
-        self._saved = ('native', batch, keep)
-        self._h_width = padded_width(self.fc[mlp_names(
-            self.config['model_kwargs']['layer_configs'][-1]['scope'] +
-            '/predictor/cls', 2)[0]].k_in)
-        return logits[:, :self.nc], pred
-
-    def _native_backward(self, dlogits, dpred, sync_sums=None):
-        _, batch, keep = self._saved
-        dl = dlogits.contiguous()
-        dp = dpred.contiguous()
-        sync = sync_sums is not None and self.comm is not None
-        _lib.check(self.lib.pgnn_trainer_backward_sync(
-            self._native_handle(), ctypes.byref(batch),
-            _lib.ptr(self._native_ws), self._native_ws.numel(), _lib.ptr(dl),
-            _lib.ptr(dp), self.comm.handle if sync else None,
-            _lib.ptr(sync_sums) if sync else None,
-            sync_sums.numel() if sync else 0, self._st()),
-            "pgnn_trainer_backward_sync")
-        self._saved = None
-        return sync
-
-    # ---- forward with saved activations ------------------------------------------
-    def forward(self, input_v, coords, kps, edges):
-        """Returns (logits [K,nc], pred_box [K,nc,L]) and keeps what backward
-        needs in self._saved."""
-        if self.native and self.sparse_adjoint:
-            return self._native_forward(input_v, coords, kps, edges)
-        if getattr(self, '_py_images_stale', True):
-            self._repack_py()
-        lib, st = self.lib, self._st()
-        dev = self.device
-        f32 = lambda t: torch.as_tensor(t).to(
-            device=dev, dtype=torch.float32).contiguous()
-        i32 = lambda t: torch.as_tensor(t).to(
-            device=dev, dtype=torch.int32).contiguous()
-        input_v = f32(input_v)
-        coords = [f32(c) for c in coords]
-        kps = [i32(k.reshape(-1)) for k in kps]
-        edges = [i32(e) for e in edges]
-        saved = []
-        h = None
-        for lc in self.config['model_kwargs']['layer_configs'][:-1]:
-            scope, kw, lvl = lc['scope'], lc['kwargs'], lc['graph_level']
-            if lc['type'] == 'scatter_max_point_set_pooling':
-                e = edges[lvl]
-                k = int(kps[lvl].shape[0])
-                names = mlp_names(scope + '/extract_vertex_features',
-                                  len(kw['point_MLP_depth_list']))
-                upper = None
-                if h is None:
-                    feat = torch.empty((int(e.shape[0]), 16),
-                                       dtype=torch.float32, device=dev)
-                    _lib.check(lib.pgnn_pool_features_fwd(
-                        _lib.ptr(input_v), int(input_v.shape[1]),
-                        _lib.ptr(coords[lvl]), _lib.ptr(kps[lvl]), _lib.ptr(e),
-                        int(e.shape[0]), _lib.ptr(feat), st),
-                        "pgnn_pool_features_fwd")
-                else:
-                    # a pooling level above the first (models.py:119-149 is
-                    # generic; no shipped config has one): the edge rows
-                    # [h[src], x[src] - x[kp[dst]]] of the previous level's
-                    # features are materialised, as gnn.PointSetPooling's
-                    # wide-feature path does
-                    n_feat = self.fc[names[0]].k_in - 3
-                    feat = torch.empty((int(e.shape[0]),
-                                        padded_width(n_feat + 3)),
-                                       dtype=torch.float32, device=dev)
-                    _lib.check(lib.pgnn_pool_features_wide_fwd(
-                        _lib.ptr(h), h.stride(0), n_feat,
-                        _lib.ptr(coords[lvl]), _lib.ptr(kps[lvl]), _lib.ptr(e),
-                        int(e.shape[0]), _lib.ptr(feat), feat.stride(0), st),
-                        "pgnn_pool_features_wide_fwd")
-                    upper = (e, n_feat, int(h.shape[0]), int(h.shape[1]))
-                acts = [feat]
-                for n in names:
-                    acts.append(self.fc_fwd(n, acts[-1], True))
-                dst = self._sorted_dst(e)
-                agg = self._scatter_max(acts[-1], dst, k)
-                onames = mlp_names(scope + '/combined_features',
-                                   len(kw['output_MLP_depth_list']))
-                oacts = [agg]
-                for n in onames:
-                    oacts.append(self.fc_fwd(n, oacts[-1], True))
-                h = oacts[-1]
-                saved.append(('pool', names, acts, dst, agg, onames, oacts,
-                              upper))
-            elif lc['type'] == 'scatter_max_graph_auto_center_net':
-                e = edges[lvl]
-                x = coords[lvl]
-                k = int(h.shape[0])
-                enames = mlp_names(scope + '/extract_vertex_features',
-                                   len(kw['edge_MLP_depth_list']))
-                w1 = self.fc[enames[0]]
-                c = w1.k_in - 3
-                wq = padded_width(w1.n_out)
-                off_names, off_acts, delta = None, None, None
-                if kw['auto_offset']:
-                    off_names = mlp_names(
-                        scope, len(kw['auto_offset_MLP_depth_list']))
-                    off_acts = [h]
-                    for i, n in enumerate(off_names):
-                        off_acts.append(self.fc_fwd(
-                            n, off_acts[-1], i + 1 < len(off_names)))
-                    delta = off_acts[-1]
-                wx = torch.zeros((3, wq), dtype=torch.float32, device=dev)
-                wx[:, :w1.n_out] = w1.w[c:c + 3]
-                xo = torch.empty_like(x)
-                q = torch.empty((k, wq), dtype=torch.float32, device=dev)
-                _lib.check(lib.pgnn_offset_apply(
-                    _lib.ptr(x), _lib.ptr(delta),
-                    delta.stride(0) if delta is not None else 0, k,
-                    _lib.ptr(wx), _lib.ptr(xo), _lib.ptr(q), wq, st),
-                    "pgnn_offset_apply")
-                hx = torch.zeros((k, padded_width(c + 3)),
-                                 dtype=torch.float32, device=dev)
-                hx[:, :c] = h[:, :c]
-                hx[:, c:c + 3] = x
-                p = self.fc_fwd(enames[0], hx, False)
-                h1 = torch.empty((int(e.shape[0]), wq), dtype=torch.float32,
-                                 device=dev)
-                _lib.check(lib.pgnn_edge_hidden_fwd(
-                    _lib.ptr(p), _lib.ptr(q), wq, _lib.ptr(e),
-                    int(e.shape[0]), _lib.ptr(h1), st), "pgnn_edge_hidden_fwd")
-                eacts = [h1]
-                for n in enames[1:]:
-                    eacts.append(self.fc_fwd(n, eacts[-1], True))
-                dst = self._sorted_dst(e)
-                agg = self._scatter_max(eacts[-1], dst, k)
-                unames = mlp_names(scope + '/combined_features',
-                                   len(kw['update_MLP_depth_list']))
-                uacts = [agg]
-                for i, n in enumerate(unames):
-                    last = i + 1 == len(unames)
-                    uacts.append(self.fc_fwd(n, uacts[-1], not last,
-                                             residual=h if last else None))
-                saved.append(('gnn', enames, hx, xo, e, eacts, dst, agg,
-                              unames, uacts, off_names, off_acts, c))
-                h = uacts[-1]
-            else:
-                raise NotImplementedError(lc['type'])
-        pc = self.config['model_kwargs']['layer_configs'][-1]
-        ps = pc['scope'] + '/predictor'
-        cls_names = mlp_names(ps + '/cls', 2)
-        cacts = [h, self.fc_fwd(cls_names[0], h, True)]
-        cacts.append(self.fc_fwd(cls_names[1], cacts[-1], False))
-        logits = cacts[-1]
-        loc = []
-        k = int(h.shape[0])
-        pred = torch.empty((k, self.nc, self.box_len), dtype=torch.float32,
-                           device=dev)
-        for j in range(self.nc):
-            names = mlp_names(ps + '/loc/cls_%d' % j, 3)
-            a = [h]
-            if self._head_slice is not None:
-                # tf.split (gnn.py:196): this head's columns as rows of their own
-                s = self._head_slice
-                a = [torch.zeros((k, padded_width(s)), dtype=torch.float32,
-                                 device=dev)]
-                a[0][:, :s] = h[:, j * s:(j + 1) * s]
-            for i, n in enumerate(names):
-                a.append(self.fc_fwd(n, a[-1], i < 2))
-            pred[:, j, :] = a[-1][:, :self.box_len]
-            loc.append((names, a))
-        saved.append(('heads', cls_names, cacts, loc))
-        self._saved = saved
-        self._h_width = int(h.shape[1])
-        return logits[:, :self.nc], pred
-
     # ---- loss ---------------------------------------------------------------------
     def _loss_inputs(self, logits, labels, gt_box, valid):
         dev = self.device
@@ -1476,94 +963,53 @@ class Trainer(object):
         sel: top_k_selection()'s masks (computed here when omitted and the
         loss is a top-k one); with 'top_k_huber_loss' nv_total / counts_dev[1]
         must count the valid vertices INSIDE the selection (models.py:283)."""
-        if self.cls_topk or self.loc_topk:
-            return self._loss_and_grads_top_k(
-                logits, pred, labels, gt_box, valid, n_total, nv_total,
-                want_grads, counts_dev, sel, sums_out)
-        dev = self.device
+        lib, cf, cd = self.lib, ctypes.c_float, ctypes.c_double
         k = int(logits.shape[0])
-        lg = logits if logits.stride(1) == 1 else logits.contiguous()
-        labels = labels.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-        gt = gt_box.to(device=dev, dtype=torch.float32).reshape(
-            k, self.box_len).contiguous()
-        va = valid.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        lg, labels, gt, va = self._loss_inputs(logits, labels, gt_box, valid)
+        top_k = self.cls_topk or self.loc_topk
+        if top_k:
+            pred = pred.contiguous()
+            sel_c, sel_l = sel if sel is not None else self.top_k_selection(
+                lg, pred, labels, gt, va)
+        dev = self.device
         sums = sums_out if sums_out is not None else torch.empty(
             4, dtype=torch.float64, device=dev)   # (zeroed by the entries)
         dlog = torch.empty((k, self.nc), dtype=torch.float32, device=dev) \
             if want_grads else None
         dpred = torch.empty((k, self.nc, self.box_len), dtype=torch.float32,
                             device=dev) if want_grads else None
-        if self.cls_kind[0] != 0 or self._class_loc_w_host is not None:
-            if self._class_loc_w is None and self._class_loc_w_host is not None:
-                self._class_loc_w = torch.tensor(
-                    self._class_loc_w_host, dtype=torch.float32, device=dev)
-            cls_scale = self.cls_w / n_total \
-                if counts_dev is None and n_total > 0 else 0.0
-            loc_scale = self.loc_w / nv_total \
-                if counts_dev is None and nv_total > 0 else 0.0
-            _lib.check(self.lib.pgnn_loss_fwd_bwd_ex(
-                _lib.ptr(lg), lg.stride(0), _lib.ptr(labels), _lib.ptr(pred),
-                self.box_len, _lib.ptr(gt), _lib.ptr(va), k, self.nc,
-                ctypes.c_float(cls_scale), ctypes.c_float(loc_scale),
-                _lib.ptr(counts_dev), ctypes.c_double(self.cls_w),
-                ctypes.c_double(self.loc_w), self.cls_kind[0],
-                ctypes.c_float(self.cls_kind[1]),
-                ctypes.c_float(self.cls_kind[2]), _lib.ptr(self._class_loc_w),
-                _lib.ptr(sums), _lib.ptr(dlog), _lib.ptr(dpred), self._st()),
-                "pgnn_loss_fwd_bwd_ex")
-            return sums, dlog, dpred
-        if counts_dev is not None:
-            _lib.check(self.lib.pgnn_loss_fwd_bwd_counts(
-                _lib.ptr(lg), lg.stride(0), _lib.ptr(labels), _lib.ptr(pred),
-                self.box_len, _lib.ptr(gt), _lib.ptr(va), k, self.nc,
-                ctypes.c_double(self.cls_w), ctypes.c_double(self.loc_w),
-                _lib.ptr(counts_dev), _lib.ptr(sums), _lib.ptr(dlog),
-                _lib.ptr(dpred), self._st()), "pgnn_loss_fwd_bwd_counts")
-            return sums, dlog, dpred
-        cls_scale = self.cls_w / n_total if n_total > 0 else 0.0
-        loc_scale = self.loc_w / nv_total if nv_total > 0 else 0.0  # div_no_nan
-        _lib.check(self.lib.pgnn_loss_fwd_bwd(
-            _lib.ptr(lg), lg.stride(0), _lib.ptr(labels), _lib.ptr(pred),
-            self.box_len, _lib.ptr(gt), _lib.ptr(va), k, self.nc,
-            ctypes.c_float(cls_scale), ctypes.c_float(loc_scale),
-            _lib.ptr(sums), _lib.ptr(dlog), _lib.ptr(dpred), self._st()),
-            "pgnn_loss_fwd_bwd")
+        # 'top_k_softmax': the reference's mean over the k selected values,
+        # written as the callers' sum / n_total: every selected vertex weighs
+        # n_rank / k
+        ce_w = float(k) / self.cls_topk if self.cls_topk else 1.0
+        # the host's normalisers (div_no_nan); unused with counts_dev
+        scales = (cf(self.cls_w * ce_w / n_total
+                     if counts_dev is None and n_total > 0 else 0.0),
+                  cf(self.loc_w / nv_total
+                     if counts_dev is None and nv_total > 0 else 0.0))
+        args = (_lib.ptr(lg), lg.stride(0), _lib.ptr(labels), _lib.ptr(pred),
+                self.box_len, _lib.ptr(gt), _lib.ptr(va), k, self.nc)
+        outs = (_lib.ptr(sums), _lib.ptr(dlog), _lib.ptr(dpred), self._st())
+        kind = (_lib.ptr(counts_dev), cd(self.cls_w), cd(self.loc_w),
+                self.cls_kind[0], cf(self.cls_kind[1]), cf(self.cls_kind[2]),
+                _lib.ptr(self._class_loc_w))
+        if top_k:
+            _lib.check(lib.pgnn_loss_fwd_bwd_sel(*(
+                args + scales + kind + (_lib.ptr(sel_c), _lib.ptr(sel_l),
+                                        cf(ce_w), None, None) + outs)),
+                "pgnn_loss_fwd_bwd_sel")
+        elif self.cls_kind[0] != 0 or self._class_loc_w_host is not None:
+            _lib.check(lib.pgnn_loss_fwd_bwd_ex(*(
+                args + scales + kind + outs)), "pgnn_loss_fwd_bwd_ex")
+        elif counts_dev is not None:
+            _lib.check(lib.pgnn_loss_fwd_bwd_counts(*(
+                args + (cd(self.cls_w), cd(self.loc_w), _lib.ptr(counts_dev))
+                + outs)), "pgnn_loss_fwd_bwd_counts")
+        else:
+            _lib.check(lib.pgnn_loss_fwd_bwd(*(args + scales + outs)),
+                       "pgnn_loss_fwd_bwd")
         return sums, dlog, dpred
 
-    def _loss_and_grads_top_k(self, logits, pred, labels, gt_box, valid,
-                              n_total, nv_total, want_grads, counts_dev, sel,
-                              sums_out=None):
-        dev = self.device
-        k = int(logits.shape[0])
-        lg, labels, gt, va = self._loss_inputs(logits, labels, gt_box, valid)
-        pred = pred.contiguous()
-        if sel is None:
-            sel = self.top_k_selection(lg, pred, labels, gt, va)
-        sel_c, sel_l = sel
-        sums = sums_out if sums_out is not None else torch.empty(
-            4, dtype=torch.float64, device=dev)   # (zeroed by the entry)
-        dlog = torch.empty((k, self.nc), dtype=torch.float32, device=dev) \
-            if want_grads else None
-        dpred = torch.empty((k, self.nc, self.box_len), dtype=torch.float32,
-                            device=dev) if want_grads else None
-        # the reference's mean over the k selected values, written as the
-        # callers' sum / n_total: every selected vertex weighs n_rank / k
-        ce_w = float(k) / self.cls_topk if self.cls_topk else 1.0
-        cls_scale = self.cls_w * ce_w / n_total \
-            if counts_dev is None and n_total > 0 else 0.0
-        loc_scale = self.loc_w / nv_total \
-            if counts_dev is None and nv_total > 0 else 0.0
-        _lib.check(self.lib.pgnn_loss_fwd_bwd_sel(
-            _lib.ptr(lg), lg.stride(0), _lib.ptr(labels), _lib.ptr(pred),
-            self.box_len, _lib.ptr(gt), _lib.ptr(va), k, self.nc,
-            ctypes.c_float(cls_scale), ctypes.c_float(loc_scale),
-            _lib.ptr(counts_dev), ctypes.c_double(self.cls_w),
-            ctypes.c_double(self.loc_w), self.cls_kind[0],
-            ctypes.c_float(self.cls_kind[1]), ctypes.c_float(self.cls_kind[2]),
-            _lib.ptr(self._class_loc_w), _lib.ptr(sel_c), _lib.ptr(sel_l),
-            ctypes.c_float(ce_w), None, None, _lib.ptr(sums), _lib.ptr(dlog),
-            _lib.ptr(dpred), self._st()), "pgnn_loss_fwd_bwd_sel")
-        return sums, dlog, dpred
 
     def _weight_norms(self, out2):
         """out2[0] = sum |w| over the weights and, when there is an l2 term,
@@ -1585,7 +1031,6 @@ class Trainer(object):
         v = out.tolist()
         return self.l1_scale * v[0] + 0.5 * self.l2_scale * v[1]
 
-    # ---- backward -----------------------------------------------------------------
     def _multi(self):
         """Does a step issue its collectives?  More than one rank, or one rank
         with force_collective."""
@@ -1596,142 +1041,6 @@ class Trainer(object):
         import torch.distributed as dist
         return self.force_collective and dist.is_available() and \
             dist.is_initialized()
-
-    def backward(self, dlogits, dpred, sync_sums=None):
-        """Gradients of the last forward into self.grad.  sync_sums (the loss
-        sums of a multi-rank step): with a Communicator and the native step the
-        all-reduce of (self.grad, sync_sums) is enqueued by the same C call;
-        returns True when that happened (the caller reduces otherwise)."""
-        if self._saved and self._saved[0] == 'native':
-            return self._native_backward(dlogits, dpred, sync_sums)
-        lib, st, dev = self.lib, self._st(), self.device
-        saved = list(self._saved)
-        kind, cls_names, cacts, loc = saved.pop()
-        k = int(cacts[0].shape[0])
-        hw = self._h_width
-        dh = torch.zeros((k, hw), dtype=torch.float32, device=dev)
-
-        def add_dh(dx, width, col0=0):
-            dh[:, col0:col0 + width] += dx[:, :width]
-
-        # heads
-        dy = torch.zeros((k, padded_width(self.nc)), dtype=torch.float32,
-                         device=dev)
-        dy[:, :self.nc] = dlogits
-        d1 = self.fc_bwd(cls_names[1], cacts[1], cacts[2], dy, False)
-        dx = self.fc_bwd(cls_names[0], cacts[0], cacts[1], d1, True)
-        cwidth = self.fc[cls_names[0]].k_in
-        add_dh(dx, cwidth)
-        for j, (names, a) in enumerate(loc):
-            dy = torch.zeros((k, padded_width(self.box_len)),
-                             dtype=torch.float32, device=dev)
-            dy[:, :self.box_len] = dpred[:, j, :]
-            d = self.fc_bwd(names[2], a[2], a[3], dy, False)
-            d = self.fc_bwd(names[1], a[1], a[2], d, True)
-            d = self.fc_bwd(names[0], a[0], a[1], d, True)
-            if self._head_slice is not None:
-                # a split head's input gradient goes to its own columns
-                add_dh(d, self._head_slice, j * self._head_slice)
-            else:
-                add_dh(d, cwidth)
-        # layers in reverse
-        while saved:
-            item = saved.pop()
-            if item[0] == 'gnn':
-                (_, enames, hx, xo, e, eacts, dst, agg, unames, uacts,
-                 off_names, off_acts, c) = item
-                d = dh            # gradient w.r.t. this layer's output
-                dh_in = dh.clone()  # residual branch (gnn.py:372)
-                for i in range(len(unames) - 1, -1, -1):
-                    last = i + 1 == len(unames)
-                    dcur = d if not last else d.clone()
-                    d = self.fc_bwd(unames[i], uacts[i], uacts[i + 1], dcur,
-                                    not last)
-                dagg = d
-                if self.sparse_adjoint and self.fc[enames[-1]].wt is not None:
-                    # last edge layer + scatter-max: sparse adjoint (returns
-                    # the gradient w.r.t. its input, already ReLU-masked)
-                    g = self._segmax_fc_bwd(enames[-1], eacts[-1], dst, agg,
-                                            dagg, eacts[-2])
-                    dense_from = len(enames) - 2
-                else:
-                    g = self._scatter_max_bwd(eacts[-1], dst, agg, dagg)
-                    dense_from = len(enames) - 1
-                for i in range(dense_from, 0, -1):
-                    # g is already masked by the ReLU of layer i (relu_mask)
-                    g = self.fc_bwd(enames[i], eacts[i - 1], eacts[i], g,
-                                    relu=False)
-                    _lib.check(lib.pgnn_relu_mask_mul(
-                        _lib.ptr(g), _lib.ptr(eacts[i - 1]), g.numel(), st),
-                        "pgnn_relu_mask_mul")
-                kk = int(hx.shape[0])
-                wq = int(g.shape[1])
-                dp = torch.empty((kk, wq), dtype=torch.float32, device=dev)
-                dq = torch.empty((kk, wq), dtype=torch.float32, device=dev)
-                _lib.check(lib.pgnn_edge_hidden_bwd(
-                    _lib.ptr(g), wq, _lib.ptr(e), int(e.shape[0]), kk,
-                    _lib.ptr(dp), _lib.ptr(dq), st), "pgnn_edge_hidden_bwd")
-                w1 = self.fc[enames[0]]
-                if getattr(self, 'debug', None) is not None:
-                    self.debug[enames[0]] = dict(
-                        g1=g.clone(), dp=dp.clone(), dq=dq.clone(), dagg=dagg.clone(),
-                        dh_out=dh.clone(), hx=hx.clone(), agg=agg.clone())
-                # P = [h, x] W1 + b1
-                dhx = self.fc_bwd(enames[0], hx, None, dp, False)
-                dh_in[:, :c] += dhx[:, :c]
-                # Q = x' Wx, Wx = rows c..c+2 of W1 (pre-activation is P - Q; the
-                # minus sign is already in dq)
-                gwx_ptr = ctypes.c_void_p(w1.gw.data_ptr() + 4 * c * w1.n_out)
-                self._weight_grad(xo, 3, 3, dq, w1.n_out, gwx_ptr, None)
-                if off_names is not None:
-                    # dx' = dQ Wx^T (image refreshed by repack())
-                    d = self._mlp1(self.wx_packed_t[enames[0]], w1.n_out, 3,
-                                   False, dq, w1.n_out)
-                    for i in range(len(off_names) - 1, -1, -1):
-                        d = self.fc_bwd(off_names[i], off_acts[i],
-                                        off_acts[i + 1], d,
-                                        i + 1 < len(off_names))
-                    dh_in[:, :c] += d[:, :c]
-                dh = dh_in
-            else:
-                _, names, acts, dst, agg, onames, oacts, upper = item
-                d = dh
-                for i in range(len(onames) - 1, -1, -1):
-                    d = self.fc_bwd(onames[i], oacts[i], oacts[i + 1], d, True)
-                # (the gradient w.r.t. the stage's input rows is wanted only
-                # above the first level; acts[0] is a gathered input, not a
-                # ReLU output: no mask there)
-                if self.sparse_adjoint and self.fc[names[-1]].wt is not None:
-                    first = len(names) == 1
-                    g = self._segmax_fc_bwd(
-                        names[-1], acts[-1], dst, agg, d, acts[-2],
-                        need_dx=not first or upper is not None,
-                        mask_x=not first)
-                    dense_from = len(names) - 2
-                else:
-                    g = self._scatter_max_bwd(acts[-1], dst, agg, d)
-                    dense_from = len(names) - 1
-                for i in range(dense_from, -1, -1):
-                    g = self.fc_bwd(names[i], acts[i], acts[i + 1], g,
-                                    relu=False,
-                                    need_dx=i > 0 or upper is not None)
-                    if i > 0:
-                        _lib.check(lib.pgnn_relu_mask_mul(
-                            _lib.ptr(g), _lib.ptr(acts[i]), g.numel(), st),
-                            "pgnn_relu_mask_mul")
-                if upper is not None:
-                    # adjoint of the gather h[src]: dh_prev[src] += g[:, :n]
-                    # (the coordinate columns behind them have no parameters
-                    # upstream)
-                    e, n_feat, k_prev, w_prev = upper
-                    src = e[:, 0].contiguous()
-                    dh = torch.zeros((k_prev, w_prev), dtype=torch.float32,
-                                     device=dev)
-                    _lib.check(lib.pgnn_scatter_sum_f32(
-                        _lib.ptr(g), g.stride(0), _lib.ptr(src),
-                        int(src.shape[0]), n_feat, k_prev, _lib.ptr(dh),
-                        dh.stride(0), 0, None, st), "pgnn_scatter_sum_f32")
-        self._saved = None
 
     # ---- one training step ----------------------------------------------------------
     def train_step(self, batch, apply=True, num_valid=None,

@@ -688,7 +688,7 @@ def test_training_step_on_unordered_edge_lists(dev, name, order):
                                 mode, (lg_s - lg_u).abs().max().item(),
                                 (bx_s - bx_u).abs().max().item()))
         if native:
-            nb, keep = t2._native_batch(*batch[:4])
+            nb, keep = t2._native_step.batch(*batch[:4])
             assert [nb.edges_sorted[l] for l in range(nb.n_levels)] == \
                 [0] * nb.n_levels
             del nb, keep
@@ -1346,7 +1346,8 @@ def test_native_sparse_and_dense_steps_give_the_same_gradient(dev, name,
         tr = train.Trainer(cfg, params=params, device=dev)
         tr.native, tr.sparse_adjoint = native, sparse
         out = tr.train_step(batch, apply=False)
-        assert (tr._native is not None) == (mode == "native")
+        assert (getattr(tr._native_step, 'handle', None) is not None) == (
+            mode == "native")
         grads[mode] = tr.grad_dict()
         losses[mode] = (out['cls_loss'], out['loc_loss'])
     assert losses["native"] == losses["python"] == losses["dense"]
@@ -1389,7 +1390,7 @@ def test_native_step_above_the_row_chain_limit(dev):
         tr = train.Trainer(cfg, params=params, device=dev)
         tr.native = native
         out = tr.train_step(batch, apply=False)
-        assert (tr._native is not None) == native
+        assert (getattr(tr._native_step, 'handle', None) is not None) == native
         grads[mode] = tr.grad_dict()
         losses[mode] = (out['cls_loss'], out['loc_loss'])
     assert losses["native"] == losses["python"]
@@ -1483,6 +1484,40 @@ def test_switching_step_paths_never_runs_on_stale_weight_images(dev):
         fresh.native = first
         lg2, pb2 = fresh.forward(*b3[:4])
         assert torch.equal(lg, lg2) and torch.equal(pb, pb2), first
+
+
+def test_one_parameter_history_through_all_three_engine_selections(dev):
+    """Three applied SGD steps, each on another selection -- native, composed
+    with the sparse adjoint, composed with the dense one -- so that both lazy
+    image refreshes happen in ONE parameter history (the composed engine's
+    after the native update, and again after its own), against the same three
+    steps on the dense composition throughout.  The bar is the one
+    test_native_step_updates_like_the_python_step holds a native and a
+    Python-driven run of three such steps to: 3e-3 of a variable's scale (the
+    gradients differ by float32 summation order, three updates at lr 0.125
+    amplify that).  An engine that ran on images one update behind would be
+    off by a whole step, lr x gradient: well beyond it."""
+    from pointgnn_amd import train
+    from pointgnn_amd.train_step import ComposedStep, NativeStep
+    cfg = configs.car_auto_config(3)
+    params = weights.init_params(cfg, seed=8, bias_scale=0.05)
+    batches = [_tiny_batch(seed=s) for s in (1, 2, 3)]
+    tr = train.Trainer(cfg, params=params, device=dev)
+    for b, (native, sparse, kind) in zip(batches, (
+            (True, True, NativeStep), (False, True, ComposedStep),
+            (False, False, ComposedStep))):
+        tr.native, tr.sparse_adjoint = native, sparse
+        assert type(tr._engine()) is kind
+        tr.train_step(b)
+    ref = train.Trainer(cfg, params=params, device=dev)
+    ref.native, ref.sparse_adjoint = False, False
+    for b in batches:
+        ref.train_step(b)
+    assert ref._native_step is None
+    got, want = tr.state_dict(), ref.state_dict()
+    for n in want:
+        a, b = got[n].astype(np.float64), want[n].astype(np.float64)
+        assert np.abs(a - b).max() <= 3e-3 * max(np.abs(b).max(), 1e-6) + 1e-7, n
 
 
 @pytest.mark.parametrize("c,fixture", [(300, "graph_small.npz"),

@@ -208,7 +208,7 @@ def test_full_size_gradient_matches_mask_matched_oracle(name):
             got = t2.grad_dict()
         finally:
             _lib.set_tunable("train_h1", 1)
-        assert (t2._native is not None) == native
+        assert (getattr(t2._native_step, 'handle', None) is not None) == native
         del t2
         losses[mode] = (out['cls_loss'], out['loc_loss'])
         errors[mode] = {n: float(np.abs(got[n] - r).max() /
@@ -266,10 +266,10 @@ def _native_step(cfg, params, batch, dev):
     t2 = train.Trainer(cfg, params=params, device=dev)
     t2.native, t2.sparse_adjoint = True, True
     t2.forward(*batch[:4])            # sizes the workspace
-    assert t2._native is not None
-    t2._native_ws.zero_()
+    assert t2._native_step.handle is not None
+    t2._native_step.workspace.zero_()
     t2.forward(*batch[:4])
-    saved = t2._native_ws.clone()
+    saved = t2._native_step.workspace.clone()
     out = t2.train_step(batch, apply=False)
     got = t2.grad_dict()
     del t2

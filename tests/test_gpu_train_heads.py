@@ -142,7 +142,7 @@ def test_native_step_runs_these_heads(dev, head, nc):
     with warnings.catch_warnings():
         warnings.simplefilter("error", RuntimeWarning)
         out = tr.train_step(batch)
-    assert tr.native and tr._native is not None
+    assert tr.native and tr._native_step.handle is not None
     assert np.isfinite(out['cls_loss']) and np.isfinite(out['loc_loss'])
 
 
