@@ -295,6 +295,57 @@ int pgnn_radius_graph_dyn_cap(const void *workspace, size_t workspace_bytes,
                               int64_t new_capacity,
                               int32_t *n_new_dev /* [2], device */,
                               void *stream);
+/* ---- k nearest neighbours without a radius (extension) ------------------
+ * The third neighbourhood of a point-cloud GNN beside the radius graph and the
+ * kNN within a radius above: the k nearest points of the WHOLE cloud, so every
+ * centre has the same fan-in whatever the local density.  Inputs: points
+ * [points_cap, 3] and centres [centers_cap, 3], both float32 or (_f64) both
+ * float64, optional scale3_host, 1 <= k <= 256, cell_size > 0.  k < 1 or
+ * cell_size <= 0 returns PGNN_E_INVALID before any HIP call; k > 256 returns
+ * PGNN_E_UNSUPPORTED.  For every centre q:
+ *   Coordinates and distance: widened to float64 and pre-divided by scale3;
+ *     d2 = (dx*dx + dy*dy) + dz*dz in float64 with no contraction -- the
+ *     arithmetic of the radius graph and of pgnn_knn_graph_*.
+ *   Selection: the m = min(k, number of points) points with the smallest key
+ *     (d2, point index), compared lexicographically, so duplicate points and
+ *     lattice ties are defined.
+ *   Rows: (point_idx, centre_idx); centre q owns rows [q*m, (q+1)*m), in
+ *     ascending key order.  There is no offsets array: the CSR is arithmetic
+ *     and E = centres * m.  When points and centres are the same array the
+ *     centre itself is a candidate (d2 = 0), as in the radius graph.
+ *   cell_size: the edge of the search grid, in scaled units.  It is a tuning
+ *     argument ONLY: the rows are a function of (points, centres, scale, k) and
+ *     never of cell_size.  (It must keep |coordinate / cell_size| below 2^29;
+ *     a good value holds a few times k points per 27 cells.)
+ *   NaN coordinates: unspecified, as in the radius graph.
+ * One call, no host read, in the style of pgnn_radius_graph_dyn: with both
+ * n_points_dev and n_centers_dev NULL the caps ARE the sizes (host-sized form,
+ * E = centers_cap * min(k, points_cap) is known to the caller); when given
+ * (device int32), min(*n_dev, cap) rows are valid and m = min(k, valid points)
+ * is evaluated on the device.  n_edges_dev (nullable) receives {rows written,
+ * rows required} = {min(E, edge_capacity), E}; rows at or beyond edge_capacity
+ * are not written.  Zero valid points or zero valid centres give {0, 0} and
+ * write nothing.  centers_cap * k must fit an int32.  The workspace is a
+ * function of (points_cap, centers_cap, k) alone (0 for an unsupported k). */
+size_t pgnn_knn_nearest_workspace_bytes(int64_t points_cap,
+                                        int64_t centers_cap, int32_t k);
+int pgnn_knn_nearest(const float *points, int64_t points_cap,
+                     const int32_t *n_points_dev, const float *centers,
+                     int64_t centers_cap, const int32_t *n_centers_dev,
+                     const double *scale3_host, int32_t k, double cell_size,
+                     void *workspace, size_t workspace_bytes,
+                     int32_t *edges /* [edge_capacity, 2] */,
+                     int64_t edge_capacity,
+                     int32_t *n_edges_dev /* [2], device, nullable */,
+                     void *stream);
+int pgnn_knn_nearest_f64(const double *points, int64_t points_cap,
+                         const int32_t *n_points_dev, const double *centers,
+                         int64_t centers_cap, const int32_t *n_centers_dev,
+                         const double *scale3_host, int32_t k,
+                         double cell_size, void *workspace,
+                         size_t workspace_bytes, int32_t *edges,
+                         int64_t edge_capacity, int32_t *n_edges_dev,
+                         void *stream);
 
 /* ---- keypoints ----------------------------------------------------------
  * 'center' mode = multi_layer_downsampling_select (graph_gen.py:49-90) for ONE

@@ -528,6 +528,336 @@ __global__ __launch_bounds__(1024) void knn_select_kernel(
   }
 }
 
+// ---- k nearest neighbours without a radius ---------------------------------------
+// (extension; contract: pgnn_knn_nearest in pointgnn_hip.h.)  Every centre
+// keeps the m = min(k, valid points) smallest keys (d2, point index) of the
+// WHOLE cloud, so the rows of centre q are [q m, (q + 1) m): no count phase,
+// no scan.  The grid is the radius grid with `cell` as its edge; the search
+// walks it shell by shell (shell s = the cells at Chebyshev distance s from
+// the centre's cell) and stops as soon as nothing outside the scanned box can
+// enter the list.
+//
+// The record behind the grid in the workspace (kNearRecInts int32):
+//   [0..2] / [3..5]  smallest / largest cell of a valid point per axis,
+//   [6] valid points, [7] m.
+constexpr int kNearRecInts = 8;
+
+__global__ void knn_nearest_init_kernel(int64_t points_cap,
+                                        const int32_t *__restrict__ n_points_dev,
+                                        int64_t centers_cap,
+                                        const int32_t *__restrict__ n_centers_dev,
+                                        int k, int64_t edge_capacity,
+                                        int32_t *__restrict__ rec,
+                                        int32_t *__restrict__ n_edges_dev) {
+  graph_prio();
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  int64_t np = points_cap, nc = centers_cap;
+  if (n_points_dev) np = *n_points_dev < np ? *n_points_dev : np;
+  if (n_centers_dev) nc = *n_centers_dev < nc ? *n_centers_dev : nc;
+  if (np < 0) np = 0;
+  if (nc < 0) nc = 0;
+  const int64_t m = np < k ? np : (int64_t)k;
+  for (int a = 0; a < 3; ++a) {
+    rec[a] = 0x7fffffff;
+    rec[3 + a] = -0x7fffffff - 1;
+  }
+  rec[6] = (int32_t)np;
+  rec[7] = (int32_t)m;
+  if (n_edges_dev) {  // as edge_total_kernel (host: centers_cap * k < 2^31)
+    const int64_t e = nc * m;
+    n_edges_dev[0] = (int32_t)(e < edge_capacity ? e : edge_capacity);
+    n_edges_dev[1] = (int32_t)e;
+  }
+}
+
+// cell bounding box of the valid points (the cells cell_keys_kernel hashed)
+__global__ __launch_bounds__(256) void knn_nearest_bounds_kernel(
+    const SortedPoint *__restrict__ sorted, int64_t n,
+    const int32_t *__restrict__ n_dev, double cell,
+    int32_t *__restrict__ rec) {
+  graph_prio();
+  if (n_dev) n = *n_dev < n ? *n_dev : n;
+  const double inv_cell = 1.0 / cell;  // as in cell_keys_kernel
+  int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff};
+  int hi[3] = {-0x7fffffff - 1, -0x7fffffff - 1, -0x7fffffff - 1};
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const SortedPoint sp = sorted[i];
+    const int c[3] = {rcell_of(sp.x, inv_cell), rcell_of(sp.y, inv_cell),
+                      rcell_of(sp.z, inv_cell)};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = c[a] < lo[a] ? c[a] : lo[a];
+      hi[a] = c[a] > hi[a] ? c[a] : hi[a];
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const int l = __shfl_xor(lo[a], d), h = __shfl_xor(hi[a], d);
+      lo[a] = l < lo[a] ? l : lo[a];
+      hi[a] = h > hi[a] ? h : hi[a];
+    }
+    if ((threadIdx.x & 63) == 0 && lo[a] <= hi[a]) {
+      atomicMin(&rec[a], lo[a]);
+      atomicMax(&rec[3 + a], hi[a]);
+    }
+  }
+}
+
+// One wave per centre; the wave's list and its rank merge are
+// knn_select_kernel's (a copy: that kernel's code stays what it is), with m in
+// the place of k.  Per shell the cells are taken 64 at a time -- lane = cell,
+// one round of bucket loads, a wave scan into one candidate list, chunks of 64
+// candidates -- and a candidate of another cell sharing the bucket is told
+// apart by rcell_of, so every point is a candidate exactly once per centre.
+//
+// The cells of shell s inside the cloud's cell bounding box [lo, hi] are six
+// slabs: z = cz -/+ s over the box's (x, y) extent; y = cy -/+ s over the
+// inner z range (|z - cz| < s) and the x extent; x = cx -/+ s over the inner
+// y and z ranges.  A slab whose plane lies outside [lo, hi] is empty, so a
+// centre far from the cloud starts at the first shell that reaches it and
+// never walks a cell that cannot exist.
+//
+// After shell s every unscanned point lies outside the box cc -/+ s on at
+// least one axis: beyond a face at (cc - s) cell or (cc + s + 1) cell (only
+// faces inside [lo, hi] have points behind them).  b = the smallest distance
+// from the centre to such a face, shrunk by a relative 1e-9 and by 2e-15 of
+// the face's magnitude (rcell_of rounds v * (1 / cell): a point of cell F may
+// lie 2^-51 |F cell| before the face).  The walk stops when the list is full
+// and its last d2 is STRICTLY below b * b -- at equality an unscanned point
+// with a smaller index would have to win -- or when the box covers [lo, hi].
+template <typename T>
+__global__ __launch_bounds__(1024) void knn_nearest_kernel(
+    const T *__restrict__ centers, int64_t n_centers,
+    const int32_t *__restrict__ n_centers_dev, Scale3 sc, double cell,
+    uint32_t mask, const int32_t *__restrict__ cell_start,
+    const int32_t *__restrict__ cell_end,
+    const SortedPoint *__restrict__ sorted, const int32_t *__restrict__ rec,
+    int32_t *__restrict__ edges, int64_t capacity, int k) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char knn_lds[];
+  graph_prio();
+  const int lane = threadIdx.x & 63;
+  const int wpb = blockDim.x >> 6;
+  const int wib = threadIdx.x >> 6;
+  double *ld2 = (double *)knn_lds + (size_t)wib * k;
+  int32_t *lidx = (int32_t *)((double *)knn_lds + (size_t)wpb * k) +
+                  (size_t)wib * k;
+  const int64_t wave0 = (int64_t)blockIdx.x * wpb + wib;
+  const int64_t n_waves = (int64_t)gridDim.x * wpb;
+  if (n_centers_dev)
+    n_centers = *n_centers_dev < n_centers ? *n_centers_dev : n_centers;
+  const int m = rec[7];  // min(k, valid points)
+  if (m <= 0) return;
+  const int lox = rec[0], loy = rec[1], loz = rec[2];
+  const int hix = rec[3], hiy = rec[4], hiz = rec[5];
+  const double inv_cell = 1.0 / cell;  // as in cell_keys_kernel
+  const double kInf = __longlong_as_double(0x7ff0000000000000ll);
+  for (int64_t q = wave0; q < n_centers; q += n_waves) {
+    double cx, cy, cz;
+    load_point(centers, q, sc, cx, cy, cz);
+    // the centre's cell, kept inside +/- 2^29 so that cc +/- s stays an int
+    // (a centre that far out is outside every cloud the grid can hold)
+    const double kFar = 536870912.0;
+    const int ccx = (int)fmin(fmax(floor(cx * inv_cell), -kFar), kFar);
+    const int ccy = (int)fmin(fmax(floor(cy * inv_cell), -kFar), kFar);
+    const int ccz = (int)fmin(fmax(floor(cz * inv_cell), -kFar), kFar);
+    // first shell that reaches [lo, hi]; the shell at which the box covers it
+    int s_first = 0, s_cover = 0;
+    {
+      const int gap[3] = {max(lox - ccx, ccx - hix), max(loy - ccy, ccy - hiy),
+                          max(loz - ccz, ccz - hiz)};
+      const int far[3] = {max(ccx - lox, hix - ccx), max(ccy - loy, hiy - ccy),
+                          max(ccz - loz, hiz - ccz)};
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        s_first = max(s_first, gap[a]);
+        s_cover = max(s_cover, far[a]);
+      }
+    }
+    const double cmag = fmax(fabs(cx), fmax(fabs(cy), fabs(cz)));
+    int n_list = 0;      // wave-uniform: entries of the list
+    double thr_d = 0.0;  // the list's last key once it is full
+    int32_t thr_i = 0;
+    for (int s = s_first; s <= s_cover; ++s) {
+      // the shell's slabs (all wave-uniform)
+      const int x0 = max(lox, ccx - s), x1 = min(hix, ccx + s);
+      const int y0 = max(loy, ccy - s), y1 = min(hiy, ccy + s);
+      const int z0 = max(loz, ccz - s), z1 = min(hiz, ccz + s);
+      const int yi0 = max(y0, ccy - s + 1), yi1 = min(y1, ccy + s - 1);
+      const int zi0 = max(z0, ccz - s + 1), zi1 = min(z1, ccz + s - 1);
+      const int64_t nxs = x1 - x0 + 1, nys = y1 - y0 + 1;
+      const int64_t nyi = yi1 >= yi0 ? yi1 - yi0 + 1 : 0;
+      const int64_t nzi = zi1 >= zi0 ? zi1 - zi0 + 1 : 0;
+      const bool zl = ccz - s >= loz && ccz - s <= hiz;
+      const bool zh = s > 0 && ccz + s >= loz && ccz + s <= hiz;
+      const bool yl = ccy - s >= loy && ccy - s <= hiy;
+      const bool yh = ccy + s >= loy && ccy + s <= hiy;
+      const bool xl = ccx - s >= lox && ccx - s <= hix;
+      const bool xh = ccx + s >= lox && ccx + s <= hix;
+      // (at s = 0 the inner ranges are empty: only the z = cz slab counts)
+      const int64_t e0 = zl ? nxs * nys : 0;
+      const int64_t e1 = e0 + (zh ? nxs * nys : 0);
+      const int64_t e2 = e1 + (yl ? nxs * nzi : 0);
+      const int64_t e3 = e2 + (yh ? nxs * nzi : 0);
+      const int64_t e4 = e3 + (xl ? nyi * nzi : 0);
+      const int64_t n_shell = e4 + (xh ? nyi * nzi : 0);
+      for (int64_t base = 0; base < n_shell; base += 64) {
+        const int64_t left = n_shell - base;
+        const int n_cells = left < 64 ? (int)left : 64;  // wave-uniform
+        int my_s = 0, my_cnt = 0, my_ix = 0, my_iy = 0, my_iz = 0;
+        if (lane < n_cells) {
+          const int64_t i = base + lane;
+          if (i < e1) {
+            const int64_t j = i < e0 ? i : i - e0;
+            my_iz = i < e0 ? ccz - s : ccz + s;
+            my_iy = y0 + (int)(j / nxs);
+            my_ix = x0 + (int)(j % nxs);
+          } else if (i < e3) {
+            const int64_t j = i < e2 ? i - e1 : i - e2;
+            my_iy = i < e2 ? ccy - s : ccy + s;
+            my_iz = zi0 + (int)(j / nxs);
+            my_ix = x0 + (int)(j % nxs);
+          } else {
+            const int64_t j = i < e4 ? i - e3 : i - e4;
+            my_ix = i < e4 ? ccx - s : ccx + s;
+            my_iz = zi0 + (int)(j / nyi);
+            my_iy = yi0 + (int)(j % nyi);
+          }
+          const uint32_t b = cell_hash(my_ix, my_iy, my_iz, mask);
+          my_s = cell_start[b];
+          my_cnt = cell_end[b] - my_s;
+        }
+        int incl = my_cnt;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+          const int t = __shfl_up(incl, d);
+          if (lane >= d) incl += t;
+        }
+        const int total_cand = __shfl(incl, 63);
+        for (int j0 = 0; j0 < total_cand; j0 += 64) {
+          const bool valid = j0 + lane < total_cand;
+          const int j = valid ? j0 + lane : total_cand - 1;
+          int lo = 0, hi = n_cells - 1;
+#pragma unroll
+          for (int step = 0; step < 6; ++step) {
+            const int mid = (lo + hi) >> 1;
+            const int v = __shfl(incl, mid);
+            if (v > j) hi = mid; else lo = mid + 1;
+          }
+          const int c = lo < n_cells ? lo : n_cells - 1;
+          const int c_incl = __shfl(incl, c), c_cnt = __shfl(my_cnt, c);
+          const int c_s = __shfl(my_s, c);
+          const int ix = __shfl(my_ix, c), iy = __shfl(my_iy, c),
+                    iz = __shfl(my_iz, c);
+          const SortedPoint sp = sorted[c_s + (j - (c_incl - c_cnt))];
+          bool hit = false;
+          double d2 = 0.0;
+          const int32_t id = sp.idx;
+          if (valid && rcell_of(sp.x, inv_cell) == ix &&
+              rcell_of(sp.y, inv_cell) == iy &&
+              rcell_of(sp.z, inv_cell) == iz) {
+            const double dx = sp.x - cx, dy = sp.y - cy, dz = sp.z - cz;
+            d2 = (dx * dx + dy * dy) + dz * dz;
+            hit = true;
+          }
+          if (n_list == m) hit = hit && knn_key_less(d2, id, thr_d, thr_i);
+          const unsigned long long hm = __ballot(hit);
+          if (hm == 0ull) continue;  // wave-uniform
+          // ---- the rank merge of knn_select_kernel, list size m ----
+          const int tiers = (n_list + 63) >> 6;
+          double od[4];
+          int32_t oi[4];
+          int shift[4] = {0, 0, 0, 0};
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const int p = lane + 64 * t;
+            od[t] = 0.0;
+            oi[t] = 0;
+            if (t < tiers && p < n_list) {
+              od[t] = ld2[p];
+              oi[t] = lidx[p];
+            }
+          }
+          int below = 0;  // hits of this chunk below mine
+          const int d2_hi = __double2hiint(d2), d2_lo = __double2loint(d2);
+          for (unsigned long long mm = hm; mm != 0ull; mm &= mm - 1ull) {
+            const int b = __builtin_ctzll(mm);  // wave-uniform
+            const double hd =
+                __hiloint2double(__builtin_amdgcn_readlane(d2_hi, b),
+                                 __builtin_amdgcn_readlane(d2_lo, b));
+            const int32_t hi_ = __builtin_amdgcn_readlane(id, b);
+            below += knn_key_less(hd, hi_, d2, id) ? 1 : 0;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+              if (t < tiers)
+                shift[t] += knn_key_less(hd, hi_, od[t], oi[t]) ? 1 : 0;
+          }
+          int rank = 0;  // list entries below my hit
+          if (hit) {
+            int l = 0, h = n_list;
+            while (l < h) {
+              const int mid = (l + h) >> 1;
+              if (knn_key_less(ld2[mid], lidx[mid], d2, id)) l = mid + 1;
+              else h = mid;
+            }
+            rank = l;
+          }
+          knn_wave_sync();  // the old list has been read
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const int p = lane + 64 * t;
+            if (t < tiers && p < n_list && shift[t] > 0 && p + shift[t] < m) {
+              ld2[p + shift[t]] = od[t];
+              lidx[p + shift[t]] = oi[t];
+            }
+          }
+          if (hit && below + rank < m) {
+            ld2[below + rank] = d2;
+            lidx[below + rank] = id;
+          }
+          knn_wave_sync();  // the new list is in place
+          n_list += __popcll(hm);
+          if (n_list >= m) {
+            n_list = m;
+            thr_d = ld2[m - 1];
+            thr_i = lidx[m - 1];
+          }
+        }
+      }
+      if (n_list == m && s < s_cover) {
+        // faces of the scanned box that still have cells of [lo, hi] behind them
+        const double fx0 = (double)(ccx - s) * cell,
+                     fx1 = (double)(ccx + s + 1) * cell;
+        const double fy0 = (double)(ccy - s) * cell,
+                     fy1 = (double)(ccy + s + 1) * cell;
+        const double fz0 = (double)(ccz - s) * cell,
+                     fz1 = (double)(ccz + s + 1) * cell;
+        double b = kInf;
+        b = fmin(b, ccx - s > lox ? cx - fx0 : kInf);
+        b = fmin(b, ccx + s < hix ? fx1 - cx : kInf);
+        b = fmin(b, ccy - s > loy ? cy - fy0 : kInf);
+        b = fmin(b, ccy + s < hiy ? fy1 - cy : kInf);
+        b = fmin(b, ccz - s > loz ? cz - fz0 : kInf);
+        b = fmin(b, ccz + s < hiz ? fz1 - cz : kInf);
+        b = b * (1.0 - 1e-9) - 2e-15 * (cmag + ((double)s + 2.0) * cell);
+        if (b > 0.0 && thr_d < b * b) break;
+      }
+    }
+    const int64_t out0 = q * (int64_t)m;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int p = lane + 64 * t;
+      if (p < n_list && out0 + p < capacity) {
+        edges[2 * (out0 + p)] = lidx[p];
+        edges[2 * (out0 + p) + 1] = (int32_t)q;
+      }
+    }
+    knn_wave_sync();  // before the next centre overwrites the list
+  }
+}
+
 // ---- neighbour cap (training) ---------------------------------------------------
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
   x ^= x >> 30;
@@ -1477,6 +1807,112 @@ extern "C" int pgnn_knn_graph_fill_f64(
   return knn_fill_impl(points, n_points, centers, n_centers, radius,
                        scale3_host, k, workspace, workspace_bytes, offsets,
                        edges, capacity, (hipStream_t)stream_);
+  PGNN_GUARD_END
+}
+
+// ---- k nearest neighbours without a radius (extension) --------------------------
+// Contract: pointgnn_hip.h.  Workspace: [Grid | record (kNearRecInts)].  One
+// call = record + grid + cell bounds + search; E = centres * min(k, points) is
+// arithmetic, so the host-sized and the capacity form are the same launches.
+extern "C" size_t pgnn_knn_nearest_workspace_bytes(int64_t points_cap,
+                                                   int64_t centers_cap,
+                                                   int32_t k) {
+  if (k < 1 || k > kKnnMaxK || points_cap < 0 || centers_cap < 0) return 0;
+  return grid_bytes(points_cap) + align_up((size_t)kNearRecInts * 4, 256) + 256;
+}
+
+namespace {
+template <typename T>
+int knn_nearest_impl(const T *points, int64_t points_cap,
+                     const int32_t *n_points_dev, const T *centers,
+                     int64_t centers_cap, const int32_t *n_centers_dev,
+                     const double *scale3_host, int32_t k, double cell_size,
+                     void *workspace, size_t workspace_bytes, int32_t *edges,
+                     int64_t edge_capacity, int32_t *n_edges_dev,
+                     hipStream_t stream) {
+  PGNN_REQUIRE(k >= 1, PGNN_E_INVALID, "knn_nearest: k < 1");
+  PGNN_REQUIRE(cell_size > 0.0 && cell_size < 1e300, PGNN_E_INVALID,
+               "knn_nearest: cell_size must be positive");
+  PGNN_REQUIRE(points_cap >= 0 && centers_cap >= 0 && edge_capacity >= 0 &&
+                   edge_capacity <= 0x7fffffff,
+               PGNN_E_INVALID, "knn_nearest: bad argument");
+  PGNN_REQUIRE(k <= kKnnMaxK, PGNN_E_UNSUPPORTED,
+               "knn_nearest: k > 256 is not supported");
+  PGNN_REQUIRE(centers_cap <= 0x7fffffff / (int64_t)k, PGNN_E_INVALID,
+               "knn_nearest: centers_cap * k does not fit an int32");
+  PGNN_REQUIRE((points_cap == 0 || points) && (centers_cap == 0 || centers) &&
+                   (edge_capacity == 0 || edges),
+               PGNN_E_INVALID, "knn_nearest: null pointer");
+  PGNN_REQUIRE(workspace != nullptr &&
+                   workspace_bytes >= pgnn_knn_nearest_workspace_bytes(
+                                          points_cap, centers_cap, k),
+               PGNN_E_WORKSPACE, "knn_nearest: workspace too small");
+  Arena a(workspace, workspace_bytes);
+  Grid g;
+  int rc = grid_carve(a, points_cap, g);
+  if (rc) return rc;
+  int32_t *rec = a.take<int32_t>(kNearRecInts);
+  PGNN_REQUIRE(rec, PGNN_E_WORKSPACE, "knn_nearest: workspace too small");
+  const Scale3 sc = make_scale(scale3_host);
+  hipLaunchKernelGGL(knn_nearest_init_kernel, dim3(1), dim3(64),
+                     graph_lds_pad(), stream, points_cap, n_points_dev,
+                     centers_cap, n_centers_dev, (int)k, edge_capacity, rec,
+                     n_edges_dev);
+  PGNN_HIP(hipGetLastError());
+  rc = grid_build(points, points_cap, sc, 0.0, 0.0, 0.0, nullptr, cell_size, g,
+                  stream, nullptr, nullptr, n_points_dev);
+  if (rc) return rc;
+  if (points_cap == 0 || centers_cap == 0 || edge_capacity == 0) return 0;
+  hipLaunchKernelGGL(knn_nearest_bounds_kernel,
+                     dim3(graph_grid((points_cap + 255) / 256)), dim3(256),
+                     graph_lds_pad(), stream,
+                     (const SortedPoint *)g.sorted, points_cap, n_points_dev,
+                     cell_size, rec);
+  const unsigned block = graph_wide_block(), wpb = block >> 6;
+  // the waves' lists: k keys of 8 + 4 bytes each
+  const size_t lds = (size_t)wpb * (size_t)k * 12 + graph_lds_pad();
+  if (lds > 48 * 1024) {
+    rc = ensure_dynamic_lds((const void *)knn_nearest_kernel<T>, lds);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL((knn_nearest_kernel<T>),
+                     dim3(graph_grid((centers_cap + wpb - 1) / wpb)),
+                     dim3(block), lds, stream, centers, centers_cap,
+                     n_centers_dev, sc, cell_size, g.mask,
+                     (const int32_t *)g.cell_start,
+                     (const int32_t *)g.cell_end,
+                     (const SortedPoint *)g.sorted, (const int32_t *)rec, edges,
+                     edge_capacity, (int)k);
+  PGNN_HIP(hipGetLastError());
+  return 0;
+}
+}  // namespace
+
+extern "C" int pgnn_knn_nearest(
+    const float *points, int64_t points_cap, const int32_t *n_points_dev,
+    const float *centers, int64_t centers_cap, const int32_t *n_centers_dev,
+    const double *scale3_host, int32_t k, double cell_size, void *workspace,
+    size_t workspace_bytes, int32_t *edges, int64_t edge_capacity,
+    int32_t *n_edges_dev, void *stream_) {
+  PGNN_GUARD_BEGIN
+  return knn_nearest_impl(points, points_cap, n_points_dev, centers,
+                          centers_cap, n_centers_dev, scale3_host, k,
+                          cell_size, workspace, workspace_bytes, edges,
+                          edge_capacity, n_edges_dev, (hipStream_t)stream_);
+  PGNN_GUARD_END
+}
+
+extern "C" int pgnn_knn_nearest_f64(
+    const double *points, int64_t points_cap, const int32_t *n_points_dev,
+    const double *centers, int64_t centers_cap, const int32_t *n_centers_dev,
+    const double *scale3_host, int32_t k, double cell_size, void *workspace,
+    size_t workspace_bytes, int32_t *edges, int64_t edge_capacity,
+    int32_t *n_edges_dev, void *stream_) {
+  PGNN_GUARD_BEGIN
+  return knn_nearest_impl(points, points_cap, n_points_dev, centers,
+                          centers_cap, n_centers_dev, scale3_host, k,
+                          cell_size, workspace, workspace_bytes, edges,
+                          edge_capacity, n_edges_dev, (hipStream_t)stream_);
   PGNN_GUARD_END
 }
 

@@ -33,6 +33,7 @@ from . import _lib
 
 __all__ = ["gen_disjointed_rnn_local_graph_v3",
            "gen_disjointed_knn_local_graph_v3", "knn_graph_device",
+           "gen_disjointed_nearest_local_graph_v3", "knn_nearest_device",
            "gen_multi_level_local_graph_v3", "get_graph_generate_fn",
            "multi_layer_downsampling_select", "multi_layer_downsampling_random",
            "gen_multi_level_local_graph_v3_one_read", "keypoint_counts",
@@ -525,6 +526,137 @@ def gen_disjointed_knn_local_graph_v3(points_xyz, center_xyz, radius,
     return edges
 
 
+NEAREST_KEY = 'disjointed_nearest_local_graph_v3'
+# clamp of the default search-grid edge (knn_nearest_device, cell_size=None),
+# in scaled units: the range in which tools/knn_nearest_time.py found the
+# fastest cell for k = 16 .. 256 on both car_600k levels
+# (profiles/knn_nearest.md: 0.5 - 1 at level 0, 1 - 2 at level 1).  A LiDAR
+# cloud fills a small part of its bounding box, so cbrt(volume * k / N)
+# overestimates the cell that holds k points and mostly lands on the upper
+# bound; below the lower one the walk visits mostly empty cells.  A cloud in
+# other units should pass its own cell_size.
+NEAREST_CELL_MIN, NEAREST_CELL_MAX = 0.5, 2.0
+
+
+def _nearest_k(num_neighbors):
+    k = int(num_neighbors)
+    if k < 1:
+        raise ValueError("nearest graph: num_neighbors must be >= 1, got %r"
+                         % (num_neighbors,))
+    return k
+
+
+def _nearest_default_cell(points, scale, k):
+    """cbrt(volume * k / N) of the cloud's bounding box in scaled units,
+    clamped to [NEAREST_CELL_MIN, NEAREST_CELL_MAX]: a cell then holds about
+    k points of a uniformly filled box.  ONE host read (the bounding box)."""
+    n = int(points.shape[0])
+    if n == 0:
+        return NEAREST_CELL_MAX
+    box = torch.stack([points.min(dim=0).values,
+                       points.max(dim=0).values]).to(torch.float64).cpu()
+    ext = (box[1] - box[0]).numpy()
+    if scale is not None:
+        ext = ext / np.broadcast_to(
+            np.asarray(scale, dtype=np.float64).reshape(-1), (3,))
+    # a flat or degenerate box still gets a positive volume
+    ext = np.maximum(np.abs(ext), NEAREST_CELL_MIN)
+    cell = float(np.cbrt(np.prod(ext) * k / n))
+    if not np.isfinite(cell):
+        return NEAREST_CELL_MAX
+    return min(max(cell, NEAREST_CELL_MIN), NEAREST_CELL_MAX)
+
+
+class _NearestJob(object):
+    """One pgnn_knn_nearest call: workspace and edge buffer are allocated at
+    construction (on the stream current then), run() is the one enqueue.  With
+    `points_count` / a centre count (DeviceCounts) it is the capacity form; the
+    edge buffer holds max(edge_cap, centers_cap * k) rows, so it cannot
+    overflow.  `n_edges_out`: int32 [2] device slice for the record, or None."""
+
+    def __init__(self, points, points_count, centers_cap, k, scale, cell_size,
+                 edge_cap=0, n_edges_out=None, edge_hint=0):
+        self.lib = _lib.load()
+        self.points, self.cp = points, points_count
+        self.wide = points.dtype == torch.float64
+        self.n_p = int(points.shape[0])
+        self.n_c = int(centers_cap)
+        self.k = _nearest_k(k)
+        self.cell = float(cell_size)
+        if not self.cell > 0.0:
+            raise ValueError("nearest graph: cell_size must be positive, got "
+                             "%r" % (cell_size,))
+        self.keep, self.sp = _scale3(scale)
+        dev = points.device
+        self.ws_bytes = self.lib.pgnn_knn_nearest_workspace_bytes(
+            self.n_p, self.n_c, self.k)
+        self.ws = torch.empty(max(self.ws_bytes, 1), dtype=torch.uint8,
+                              device=dev)
+        self.edge_cap = max(int(edge_cap), self.n_c * min(self.k, self.n_p))
+        self.edges = torch.empty((self.edge_cap, 2), dtype=torch.int32,
+                                 device=dev)
+        self.n_edges_out = n_edges_out
+        self.edge_hint = edge_hint
+
+    def run(self, centers, centers_count=None):
+        if centers.dtype != self.points.dtype or \
+                int(centers.shape[0]) != self.n_c:
+            raise ValueError("nearest graph: centres do not match the job")
+        _lib.check((self.lib.pgnn_knn_nearest_f64 if self.wide else
+                    self.lib.pgnn_knn_nearest)(
+            _lib.ptr(self.points), self.n_p,
+            _lib.ptr(self.cp.dev if self.cp else None),
+            _lib.ptr(centers), self.n_c,
+            _lib.ptr(centers_count.dev if centers_count else None),
+            self.sp, self.k, self.cell, _lib.ptr(self.ws), self.ws_bytes,
+            _lib.ptr(self.edges), self.edge_cap,
+            _lib.ptr(self.n_edges_out), _lib.stream_ptr()),
+            "pgnn_knn_nearest")
+        self.edges._pgnn_sorted = 1  # grouped by ascending centre
+        if self.n_edges_out is None:
+            return self.edges
+        return _lib.tag_count(
+            self.edges,
+            _lib.DeviceCount(self.n_edges_out[0:1], self.edge_hint))
+
+
+def knn_nearest_device(points, centers, num_neighbors, scale=None,
+                       cell_size=None):
+    """The `num_neighbors` nearest points of every centre, with no radius
+    (extension; contract: pgnn_knn_nearest in include/pointgnn_hip.h).  Device
+    tensors in/out.  Returns edges int32 [Q * m, 2], m = min(num_neighbors, N):
+    rows (point_idx, centre_idx), centre q owns rows [q m, (q + 1) m) in
+    ascending (squared distance, point index) order -- a pure function of
+    (points, centres, scale, num_neighbors).  `cell_size` (scaled units) only
+    tunes the search grid; given, the call makes no host read at all; None
+    (default): one host read of the cloud's bounding box, then
+    cbrt(volume * k / N) clamped to [NEAREST_CELL_MIN, NEAREST_CELL_MAX].
+    1 <= num_neighbors <= 256."""
+    k = _nearest_k(num_neighbors)
+    points, centers, _ = _same_precision(points, centers)
+    if cell_size is None:
+        cell_size = _nearest_default_cell(points, scale, k)
+    job = _NearestJob(points, None, int(centers.shape[0]), k, scale,
+                      cell_size)
+    return job.run(centers)
+
+
+def gen_disjointed_nearest_local_graph_v3(points_xyz, center_xyz,
+                                          num_neighbors, scale=None,
+                                          cell_size=None):
+    """Extension beside graph_gen.py:197-220: every centre keeps its
+    `num_neighbors` nearest points, whatever their distance (ties by the
+    smaller point index) -- see knn_nearest_device.  Registry key
+    'disjointed_nearest_local_graph_v3'."""
+    _nearest_k(num_neighbors)
+    p, was_np = _to_dev(points_xyz)
+    c, _ = _to_dev(center_xyz)
+    edges = knn_nearest_device(p, c, num_neighbors, scale, cell_size)
+    if was_np:
+        return edges.cpu().numpy()
+    return edges
+
+
 _AUX_STREAMS = {}
 _IDENTITY = {}
 
@@ -980,19 +1112,28 @@ def _multi_level_graph_deferred(points_xyz, base_voxel_size, level_configs,
         raise ValueError("deferred_counts needs device tensors (a NumPy "
                          "result has to know its size)")
     for cfg in level_configs:
-        if cfg['graph_gen_method'] != 'disjointed_rnn_local_graph_v3':
+        if cfg['graph_gen_method'] == NEAREST_KEY:
+            _nearest_k(cfg['graph_gen_kwargs'].get('num_neighbors', 0))
+            if cfg['graph_gen_kwargs'].get('cell_size') is None:
+                raise ValueError(
+                    "deferred_counts: a %r level needs a cell_size in its "
+                    "graph_gen_kwargs (the capacity form reads nothing back, "
+                    "so it cannot measure the cloud's bounding box)"
+                    % (NEAREST_KEY,))
+        elif cfg['graph_gen_method'] != 'disjointed_rnn_local_graph_v3':
             raise NotImplementedError(
                 "deferred_counts: generator %r has no capacity form"
                 % (cfg['graph_gen_method'],))
+    nearest = [cfg['graph_gen_method'] == NEAREST_KEY for cfg in level_configs]
     n_levels = len(level_configs)
     dev = _device()
     # fan-in caps (training kwargs; any other method name skips the cap like
     # the reference, graph_gen.py:210): seeds drawn here, on the host, in
     # level order -- the draws the host-sized calls would make
     fan_k = [int(cfg['graph_gen_kwargs'].get('num_neighbors', -1) or -1)
-             if cfg['graph_gen_kwargs'].get(
+             if not near and cfg['graph_gen_kwargs'].get(
                  'neighbors_downsample_method', 'random') == 'random' else -1
-             for cfg in level_configs]
+             for cfg, near in zip(level_configs, nearest)]
     capped = any(k > 0 for k in fan_k)
     seeds = [None] * n_levels
     counts = _zero_counts(2 + (4 if capped else 2) * n_levels, dev)
@@ -1025,7 +1166,8 @@ def _multi_level_graph_deferred(points_xyz, base_voxel_size, level_configs,
     n = int(p.shape[0])
     # (with a cap the levels' seeds are drawn where the host-sized calls draw
     # them -- after the keypoints' draws -- so the jobs cannot be made early)
-    overlap = bool(overlap) and not capped and n > 0 and \
+    # (a nearest level has one stage, not a grid and a query: serial order)
+    overlap = bool(overlap) and not capped and not any(nearest) and n > 0 and \
         p.dtype == torch.float32 and n_levels >= 1 and level_configs[0]['graph_level'] == 0 and \
         not np.isclose(scales[0], 0)
     job0 = ov = None
@@ -1068,6 +1210,17 @@ def _multi_level_graph_deferred(points_xyz, base_voxel_size, level_configs,
     else:
         for l, cfg in enumerate(level_configs):
             lvl = cfg['graph_level']
+            if nearest[l]:
+                kw = cfg['graph_gen_kwargs']
+                pts, ctr, _ = _same_precision(coords[lvl], coords[lvl + 1])
+                job = _NearestJob(pts, _lib.count_of(coords[lvl]),
+                                  int(ctr.shape[0]), kw['num_neighbors'],
+                                  kw.get('scale'), kw['cell_size'], caps[l],
+                                  counts[2 + 2 * l:4 + 2 * l],
+                                  hints.edge_hint(l))
+                edges_list[l] = job.run(ctr, _lib.count_of(coords[lvl + 1]))
+                frame.edge_caps[l] = job.edge_cap
+                continue
             edges_list[l] = radius_graph_dyn_device(
                 coords[lvl], coords[lvl + 1], cfg['graph_gen_kwargs']['radius'],
                 cfg['graph_gen_kwargs'].get('scale'), caps[l],
@@ -1212,6 +1365,7 @@ def get_graph_generate_fn(method_name):
     method_map = {
         'disjointed_rnn_local_graph_v3': gen_disjointed_rnn_local_graph_v3,
         'disjointed_knn_local_graph_v3': gen_disjointed_knn_local_graph_v3,
+        NEAREST_KEY: gen_disjointed_nearest_local_graph_v3,
         'multi_level_local_graph_v3': gen_multi_level_local_graph_v3,
     }
     return method_map[method_name]
